@@ -31,6 +31,8 @@ if ROOT not in sys.path:
 FLOP_PER_MEME = {3: 172.42e9,      # fwd+bwd algorithmic FLOPs per meme, config 3
                  5: 1628.9e9}      # config 5: CLIP ViT-L/14@336 (577 tokens) + BERT-large at S = 256
 MFMA_PEAK_TFLOPS = 2500.0         # dense bf16/fp16 MFMA peak, MI355X_MICROARCH.md "Chip-level parameters"
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: all arrays together
+DUMP_PER_PARAM = 8192             # --dump-outputs: elements sampled from each parameter tensor (seeded, the same every run)
 
 
 def parse():
@@ -75,7 +77,12 @@ def parse():
                     help="16-bit storage / MFMA operand type of the towers (same kernels, same MFMA peak).  Default fp16: the "
                          "storage type that meets north_star's 1e-3 logit tolerance (and the reference's own AMP arithmetic, "
                          "Multimodal_example_task2C.py:60-64); the bf16 build is timed beside it (value_bf16)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, correct count, logits, a seeded sample "
+                         "of every updated parameter) as DIR/<name>.npy in float32, to compare two builds output for output")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.seq <= 0:
         a.seq = 256 if a.config == 5 else 128
     return a
@@ -160,6 +167,32 @@ def make_batches(cfg, args, device, rank=0, full_masks=None, n=None):
             for k in range(max(1, args.batches if n is None else n))]
 
 
+def param_sample(module):
+    """A fixed, seeded sample of every parameter of ``module`` (name order, at most DUMP_PER_PARAM elements each), concatenated
+    into one float32 vector: the same elements on every run and for every build whose parameters have the same names and shapes."""
+    g = torch.Generator(device="cpu").manual_seed(20240917)
+    parts = []
+    for _, p in sorted(module.named_parameters(), key=lambda kv: kv[0]):
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_PER_PARAM:
+            idx = torch.randint(0, flat.numel(), (DUMP_PER_PARAM,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    return torch.cat(parts)
+
+
+def dump_outputs(dirname, arrays):
+    """Write ``{name: tensor}`` as dirname/<name>.npy, float32, at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    host = {k: np.ascontiguousarray(v.detach().float().cpu().numpy(), dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
+
+
 def run_steps(step, batches, n, start=0):
     out = None
     for i in range(n):
@@ -204,7 +237,7 @@ def timed_variant(pkg, args, device, dtype=None, full_masks=None, dense_text=Non
     return a.batch * args.steps / dt, dt / args.steps * 1e3
 
 
-def bench_config2(args):
+def bench_config2(args, dump_dir=None):
     """BASELINE.json configs[1]: Subtask 2B, ResNet-50 image-only, 224x224 synthetic, batch 32, one MI355X: images/s of one
     fine-tune step (forward + cross-entropy + backward + fused Adam) through the Trainer-protocol module, replayed as a hipGraph."""
     device = torch.device("cuda", 0)
@@ -222,13 +255,15 @@ def bench_config2(args):
     image, labels = images[0].clone(), labelss[0].clone()          # the graph's static input buffers
     loss_buf = torch.zeros((), device=device)
     turn = [0]
+    last = {}                       # the logits of the last launch (a graph output: replay rewrites them in place)
 
     def launches():                 # everything of a step that is a device launch (capturable)
         opt.zero_grad()
-        loss, _ = model(pixel_values=image, labels=labels)
+        loss, logits = model(pixel_values=image, labels=labels)
         loss.backward()
         opt.launch()
         loss_buf.copy_(loss.detach())
+        last["logits"] = logits.detach()
 
     def one_step():
         k = turn[0] % nb
@@ -265,6 +300,8 @@ def bench_config2(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     value = args.batch * args.steps / dt
+    if dump_dir:
+        dump_outputs(dump_dir, {"loss": loss_buf.reshape(1), "logits": last["logits"], "params_sample": param_sample(model)})
     flop_per_image = 24.5e9          # fwd + bwd, BASELINE.md section 2
     out = {"metric": "images/sec (fine-tune step) ResNet-50 224x224 bs=32 (BASELINE configs[1], Subtask 2B)", "value": round(value, 2),
            "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -278,7 +315,7 @@ def bench_config2(args):
            "roofline": {"bound": "mfma", "kernel": "whole step (implicit conv GEMMs + BatchNorm passes)",
                         "achieved": round(flop_per_image * value / 1e12, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                         "frac": round(flop_per_image * value / (MFMA_PEAK_TFLOPS * 1e12), 4), "traffic": None}}
-    del graph, opt, model
+    del graph, opt, model, last
     torch.cuda.empty_cache()
     return out
 
@@ -288,7 +325,7 @@ def main():
     if args.config == 2:
         if not torch.cuda.is_available():
             raise SystemExit("bench.py needs an MI355X (no CPU fallback for the product path)")
-        print(json.dumps(bench_config2(args)), flush=True)
+        print(json.dumps(bench_config2(args, dump_dir=args.dump_outputs)), flush=True)
         return
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -361,6 +398,9 @@ def main():
         dt = float(t)
     final_loss = float(loss)
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:      # before the roofline replay below rewrites the step's buffers
+        dump_outputs(args.dump_outputs, {"loss": loss, "ncorrect": step.plan.buf["ncorrect"], "logits": step.plan.buf["logits"],
+                                         "params_sample": param_sample(model)})
     value = args.batch * world * args.steps / dt
 
     out = None
