@@ -164,6 +164,9 @@ int mh_colsum_partials_f32(const MhColsumJob* jobs /*host*/, int n_jobs, int n_p
  *         is computed inside (workspace delta f32 [B][H][S]).
  *   rng != NULL, drop_p > 0: dropout on the probabilities (attention_probs_dropout_prob); mask element index
  *         ((b*H + h)*S + q)*S + k; the backward regenerates the same mask.
+ *   A query with no key to attend to (key_mask all zeros for its sequence, e.g. the pooled row mh_pack_plan keeps for an
+ *         empty mask row) gets out = 0 and lse = -inf, and contributes no gradient (its dq row is 0, and keys it sees are all
+ *         masked).  BertSelfAttention would instead average V over all S positions; the packed form has dropped those rows.
  * ------------------------------------------------------------------------------------------ */
 int mh_attn_fwd(const void* qkv, const int64_t* key_mask, void* out, float* lse, int B, int S, int H,
                 const uint32_t* rng, float drop_p, uint32_t drop_stream, mh_stream_t stream);

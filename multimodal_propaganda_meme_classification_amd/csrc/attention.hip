@@ -232,7 +232,10 @@ MH_DEV void attn_fwd_body(const AttnArgs& A, const int bx, const int gx, const i
             int64_t km[NTL];
 #pragma unroll
             for (int t = 0; t < NTL; ++t) km[t] = 1;
-            if (key_mask) {      // (uniform branch, unconditional clamped loads inside: the tiles' mask words in flight together)
+            // (uniform branch, unconditional clamped loads inside: the tiles' mask words in flight together.  Sb == 0 -- a sequence
+            //  of no rows in a caller's packed plan -- reads nothing: the clamp would give row r0 = cu[b], which may be cu[B], one
+            //  past the last packed row)
+            if (key_mask && Sb > 0) {
 #pragma unroll
                 for (int t = 0; t < NTL; ++t) km[t] = key_mask[r0 + max(min(t * TILE + tid, Sb - 1), 0)];
             }
@@ -363,7 +366,9 @@ MH_DEV void attn_fwd_body(const AttnArgs& A, const int bx, const int gx, const i
         }
         if (!active) continue;
         l += mh_xor_partner<32>(l, (unsigned)lane);
-        const float inv = 1.0f / l;
+        // no key to attend to (the sequence's key mask is all zeros: every sub-tile skipped, l == 0): out = 0 and
+        // lse = -inf (include/memehip.h), not 0 * inf = NaN
+        const float inv = l > 0.f ? 1.0f / l : 0.f;
         store_rows_from_T(out + r0 * H * HD + hh * HD, (size_t)H * HD, wq0, Sb, lane, o, inv);
         const int q = wq0 + (lane & 31);
         if (h == 0 && q < Sb) lse[((size_t)b * H + hh) * S + q] = (m + __builtin_amdgcn_logf(l)) * LN2;
