@@ -2,10 +2,11 @@
 // 16-bit convolution WITHOUT an im2col panel in HBM (torchvision ResNet-50 as wired at Multimodal_example_task2C.txt:164,183;
 // the 3x3 panels were 9x the activation bytes, the 7x7 stem panel 360 MB per step).  See include/memehip.h ("implicit GEMM").
 //
-// Same 128x128x64 tile, 8 waves of 64x32, two LDS stages filled by LDS-DMA (buffer_load ... lds), one barrier per K tile as
-// gemm_kernel<.,.,1,8>.  The im2col matrix exists only as ADDRESSES: the per-lane source offset of every 16-byte LDS-DMA
-// chunk (8 consecutive channels of one filter tap of one pixel) is computed from (pixel, tap); taps that fall into the
-// padding get an offset beyond the buffer's num_records, which the buffer load turns into zeros.
+// The tile core is gemm_kernel's (gemm_tile.h): 128x128x64 tile, 8 waves of 64x32, the same two-stage K loop over LDS-DMA
+// stages, so a convolution gives the bits of the GEMM over its explicit im2col matrix.  What is this kernel's own: the XCD split,
+// how a K stage is issued, and the epilogues.  The im2col matrix exists only as ADDRESSES: the per-lane source offset of every
+// 16-byte LDS-DMA chunk (8 consecutive channels of one filter tap of one pixel) is computed from (pixel, tap); taps that fall
+// into the padding get an offset beyond the buffer's num_records, which the buffer load turns into zeros.
 //   forward : Y[(b,ho,wo)][co] = sum_{tap,ci} X[b][ho*s-p+kh][wo*s-p+kw][ci] * Wk[co][(tap,ci)]     A implicit, B = Wk (K-contiguous)
 //   dgrad   : dX[(b,h,w)][ci]  = sum_{tap',co} dY[b][h-p'+kh'][w-p'+kw'][co] * Wk[co][(flip(tap'),ci)]   (stride 1, p' = KH-1-p)
 //             A implicit over dY, B = the tap's [Cout][Cin] slice of Wk read K-strided
@@ -20,7 +21,6 @@
 namespace {
 using namespace mh_tile;
 
-constexpr int NW = 8, NWM = 2, NWN = 4, NI = 4, NJ = 2;      // waves: 2 along M x 4 along N, 64x32 each (gemm.hip variant 4)
 constexpr int RED_BYTES = 8 * 2 * 128 * 4;                   // BatchNorm column partials: 4 row quarters (forward) / 8 waves (dgrad) x {sum, sum2} x 128 columns
 constexpr int CONV_LDS = LDS_BYTES + RED_BYTES;
 constexpr uint32_t OOB = 0x80000000u;                        // >= num_records of every operand (sizes are checked < 2 GiB)
@@ -118,17 +118,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_gemm_kernel(const ConvGr
         t -= ks * per;
     }
     int tm, tn;
-    if (a.group_m <= 1) {
-        tm = t / a.tiles_n;
-        tn = t - tm * a.tiles_n;
-    } else {
-        const int per_group = a.group_m * a.tiles_n;
-        const int g = t / per_group;
-        const int r = t - g * per_group;
-        const int rows = min(a.group_m, a.tiles_m - g * a.group_m);
-        tn = r / rows;
-        tm = g * a.group_m + (r - tn * rows);
-    }
+    tile_coords(a.tiles_n, a.tiles_m, a.group_m, t, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     const bool split = (MODE == MODE_WGRAD) || a.nsplit > 1;      // f32 slab per K chunk, summed by a finishing launch
     const int kbeg = split ? ks * a.kchunk : 0;
@@ -136,7 +126,6 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_gemm_kernel(const ConvGr
     const int nk = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm0 = (wave / NWN) * (NI * 16), wn0 = (wave % NWN) * (NJ * 16);
     const __amdgpu_buffer_rsrc_t rs = mh_rsrc(a.src, a.src_bytes);
     const __amdgpu_buffer_rsrc_t rr = mh_rsrc(a.reg, a.reg_bytes);
     const int taps = a.KH * a.KW;
@@ -256,43 +245,11 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_gemm_kernel(const ConvGr
     };
 
     f32x4 acc[NI][NJ];
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    if (nk > 0) issue(0, smem);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        char* cur = smem + (kt & 1) * STAGE_BYTES;
-        char* nxt = smem + ((kt + 1) & 1) * STAGE_BYTES;
-        if (kt + 1 < nk) issue(kt + 1, nxt);
-        const char* la = cur;
-        const char* lb = cur + BM * BK * 2;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            h16x8 fa[NI], fb[NJ];
-#pragma unroll
-            for (int i = 0; i < NI; ++i) fa[i] = read_frag<LA>(la, wm0 + i * 16, kk, lane);
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) fb[j] = read_frag<LB>(lb, wn0 + j * 16, kk, lane);
-#pragma unroll
-            for (int i = 0; i < NI; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[i][j] = MH_MFMA_16x16x32(fa[i], fb[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
+    k_loop<LA, LB>(acc, smem, nk, wave, lane, issue);
 
     // ---- epilogue: accumulators -> f32 staging tile -> 16-byte stores ---------------------------------------------------
     float* cs = (float*)smem;
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                cs[cs_index(wm0 + i * 16 + (lane >> 4) * 4 + r, wn0 + j * 16 + (lane & 15))] = acc[i][j][r];
+    stage_acc(cs, acc, wave, lane);
     __syncthreads();
     const float alpha = a.alpha;
     // GEMM row -> row of the output tensor (identity, or the parity-class scatter of a strided convolution's input gradient)
@@ -305,18 +262,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_gemm_kernel(const ConvGr
     const int ptiles = a.part_tiles > 0 ? a.part_tiles : a.tiles_m;
     if (split) {
         float* slab = (float*)(MODE == MODE_WGRAD ? a.out : (void*)a.part) + (size_t)ks * (size_t)a.M * (size_t)a.ldc;
-#pragma unroll
-        for (int it = 0; it < BM * 16 / (NW * 64); ++it) {
-            const int q = it * NW * 64 + tid;
-            const int row = q >> 4, cc = q & 15;
-            const int gm = m0 + row, gn = n0 + cc * 8;
-            if (gm >= a.M || gn >= a.N) continue;
-            const f32x4 x0 = *(const f32x4*)(cs + cs_index(row, cc * 8));
-            const f32x4 x1 = *(const f32x4*)(cs + cs_index(row, cc * 8 + 4));
-            float* c = slab + (size_t)gm * a.ldc + gn;
-            *(f32x4*)c = x0 * alpha;
-            *(f32x4*)(c + 4) = x1 * alpha;
-        }
+        store_slab(slab, cs, alpha, m0, n0, a.M, a.N, a.ldc, tid);
         return;
     }
     if (MODE == MODE_DGRAD && a.bn_z) {
@@ -551,11 +497,7 @@ int splitk_for(int tiles, int K) {
     int sp = 256 / tiles;
     if (sp > nk / 8) sp = nk / 8;
     if (sp > 8) sp = 8;
-    for (; sp > 1; --sp) {      // every chunk must hold K tiles (chunk = ceil(nk / sp) tiles)
-        const int kc = (nk + sp - 1) / sp;
-        if ((nk + kc - 1) / kc == sp) break;
-    }
-    return sp < 1 ? 1 : sp;
+    return ksplit_fit(K, sp);
 }
 
 template <int MODE, bool UNI>
@@ -602,16 +544,6 @@ int geom_check(const MhConvGeom* g, int& Ho, int& Wo) {
     return MH_OK;
 }
 
-int group_m_setting() {
-    static int group_m = -1;
-    if (group_m < 0) {
-        const char* e = getenv("MEMEHIP_GEMM_GROUP_M");
-        group_m = e ? atoi(e) : 8;
-        if (group_m < 0 || group_m > 64) group_m = 8;
-    }
-    return group_m;
-}
-
 }  // namespace
 
 extern "C" int mh_conv_splitk(const MhConvGeom* g, int dgrad) {
@@ -640,9 +572,8 @@ int finish_split(const ConvArgs& a, void* y, float* bn_part, hipStream_t s, cons
     return mh_launch_status();
 }
 void set_split(ConvArgs& a, int nsplit, float* workspace) {
-    const int nk = a.K / BK;
     a.nsplit = nsplit;
-    a.kchunk = (nk + nsplit - 1) / nsplit * BK;
+    a.kchunk = ksplit_chunk(a.K, nsplit);      // (a.K % BK == 0 on both split paths)
     a.total_tiles = a.tiles_m * a.tiles_n * nsplit;
     a.part = workspace;          // the split kernel writes its f32 slabs here ([nsplit][M][ldc = N])
 }
@@ -801,7 +732,7 @@ int wgrad_args(const void* dy, const void* x, float* slabs, int ksplit, float al
     a.M = g->Cout; a.N = g->KH * g->KW * g->C; a.K = a.Mpix;
     a.ldreg = g->Cout; a.ldc = g->ldk; a.Cw = g->C;
     a.tiles_m = (a.M + BM - 1) / BM; a.tiles_n = (a.N + BN - 1) / BN;
-    const int kc = ((a.K + ksplit - 1) / ksplit + BK - 1) / BK * BK;
+    const int kc = ksplit_chunk(a.K, ksplit);
     if ((a.K + kc - 1) / kc != ksplit) return MH_ESHAPE;          // an empty split: use mh_gemm_ksplit_for(B*Ho*Wo, want)
     a.kchunk = kc; a.nsplit = ksplit;
     a.total_tiles = a.tiles_m * a.tiles_n * ksplit;

@@ -40,27 +40,6 @@ MH_DEV void trace_stamp(const GemmGroup& g, int k) {
     if (g.trace && threadIdx.x == 0) g.trace[(size_t)blockIdx.x * 4 + k] = wall_clock64();
 }
 
-// local tile index -> (row tile, column tile).  n-fastest order makes the ~64 tiles an XCD runs at once span
-// 3-4 row panels x ALL column tiles: every K step touches the whole of B (3.5-4.7 MB at N = 2304 / 3072, K = 768),
-// which together with the A panels overflows the XCD's 4-MB L2.  Blocked order: GROUP_M row panels x 8 column
-// tiles at once = 8 + 8 operand panels, each re-used 8 times while it is hot.
-MH_DEV void tile_coords(int tiles_n, int tiles_m, int group_m, int lt, int& tm, int& tn);
-MH_DEV void tile_coords(const DevProblem& d, int group_m, int lt, int& tm, int& tn) { tile_coords(d.tiles_n, d.tiles_m, group_m, lt, tm, tn); }      // (lab kernels)
-MH_DEV void tile_coords(int tiles_n, int tiles_m, int group_m, int lt, int& tm, int& tn) {
-    if (group_m <= 1) {
-        tm = lt / tiles_n;
-        tn = lt % tiles_n;
-        return;
-    }
-    const int per_group = group_m * tiles_n;
-    const int g = lt / per_group;
-    const int r = lt - g * per_group;
-    const int rows = min(group_m, tiles_m - g * group_m);
-    tn = r / rows;
-    tm = g * group_m + (r - tn * rows);
-}
-
-
 // ---- epilogue: f32 tile in LDS -> bias / GELU / gelu' / residual -> 16-B coalesced stores ----------
 // The 16-bit epilogue operands (residual, gelu' pre-activation) are fetched BEFORE the accumulators go through
 // LDS (epilogue_prefetch), so their HBM latency hides behind the LDS transpose + barrier instead of stalling
@@ -238,7 +217,6 @@ MH_DEV void epilogue_rows(const MhGemmProblem& P, const float* cs, int m0, int n
 // ---------------------------------------------------------------------------------------------------------------------
 template <int LA, int LB, bool DROP>
 __global__ __launch_bounds__(512, 4) void gemm_kernel(const GemmGroup g) {
-    constexpr int NW = 8, NWM = 2, NWN = 4, NI = BM / NWM / 16, NJ = BN / NWN / 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     // ---- which tile ----------------------------------------------------------------------------
@@ -321,7 +299,6 @@ __global__ __launch_bounds__(512, 4) void gemm_kernel(const GemmGroup g) {
     const int kbeg = ksplit_idx * kchunk;                       // 0 without split-K
     const int kend = kchunk > 0 ? min(K, kbeg + kchunk) : K;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm0 = (wave / NWN) * (NI * 16), wn0 = (wave % NWN) * (NJ * 16);
 
     const uint32_t a_bytes = (LA == 0) ? (uint32_t)((M - 1) * P.lda + K) * 2u
                                        : (uint32_t)((K - 1) * P.lda + M) * 2u;
@@ -330,11 +307,7 @@ __global__ __launch_bounds__(512, 4) void gemm_kernel(const GemmGroup g) {
     const __amdgpu_buffer_rsrc_t ra = mh_rsrc(P.A, a_bytes);
     const __amdgpu_buffer_rsrc_t rb = mh_rsrc(P.B, b_bytes);
 
-    f32x4 acc[NI][NJ];
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // weight gradient: the bias gradient = row sums of A, one more MFMA per A fragment against ones (column tile 0, waves of column 0)
     f32x4 accb[NI];
 #pragma unroll
     for (int i = 0; i < NI; ++i) accb[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -346,39 +319,20 @@ __global__ __launch_bounds__(512, 4) void gemm_kernel(const GemmGroup g) {
     const int nk = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
     // (static s_setprio(1) for waves 4-7 -- the younger half of the workgroup, MI355X_MICROARCH.md "two waves per SIMD" item 4 -- measured:
     //  10.12-10.18 ms per step against 10.09-10.11, same box, three alternations: nothing)
-    dma_tile<LA, 16 / NW>(ra, P.lda, m0, kbeg, wave, lane, smem);
-    dma_tile<LB, 16 / NW>(rb, P.ldb, n0, kbeg, wave, lane, smem + BM * BK * 2);
-    __syncthreads();
-    trace_stamp(g, 1);
-    for (int kt = 0; kt < nk; ++kt) {
-        char* cur = smem + (kt & 1) * STAGE_BYTES;
-        char* nxt = smem + ((kt + 1) & 1) * STAGE_BYTES;
-        if (kt + 1 < nk) {
-            dma_tile<LA, 16 / NW>(ra, P.lda, m0, kbeg + (kt + 1) * BK, wave, lane, nxt);
-            dma_tile<LB, 16 / NW>(rb, P.ldb, n0, kbeg + (kt + 1) * BK, wave, lane, nxt + BM * BK * 2);
-        }
-        const char* la = cur;
-        const char* lb = cur + BM * BK * 2;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            h16x8 fa[NI], fb[NJ];
-#pragma unroll
-            for (int i = 0; i < NI; ++i) fa[i] = read_frag<LA>(la, wm0 + i * 16, kk, lane);
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) fb[j] = read_frag<LB>(lb, wn0 + j * 16, kk, lane);
-#pragma unroll
-            for (int i = 0; i < NI; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j)
-                    acc[i][j] = MH_MFMA_16x16x32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+    f32x4 acc[NI][NJ];
+    k_loop<LA, LB>(
+        acc, smem, nk, wave, lane,
+        [&](int kt, char* st) {
+            dma_tile<LA, 16 / NW>(ra, P.lda, m0, kbeg + kt * BK, wave, lane, st);
+            dma_tile<LB, 16 / NW>(rb, P.ldb, n0, kbeg + kt * BK, wave, lane, st + BM * BK * 2);
+        },
+        [&](const h16x8 (&fa)[NI]) {
             if (do_rowsum) {
 #pragma unroll
-                for (int i = 0; i < NI; ++i)
-                    accb[i] = MH_MFMA_16x16x32(fa[i], ones, accb[i], 0, 0, 0);
+                for (int i = 0; i < NI; ++i) accb[i] = MH_MFMA_16x16x32(fa[i], ones, accb[i], 0, 0, 0);
             }
-        }
-        __syncthreads();
-    }
+        },
+        [&] { trace_stamp(g, 1); });
 
     // ---- epilogue --------------------------------------------------------------------------------
     trace_stamp(g, 2);
@@ -387,35 +341,16 @@ __global__ __launch_bounds__(512, 4) void gemm_kernel(const GemmGroup g) {
         for (int i = 0; i < NI; ++i)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int row = m0 + wm0 + i * 16 + (lane >> 4) * 4 + r;
+                const int row = m0 + wave_m0(wave) + i * 16 + (lane >> 4) * 4 + r;
                 if (row < M) P.rowsum[row] = accb[i][r] * (P.alpha == 0.f ? 1.0f : P.alpha);
             }
     }
-    float* cs = (float*)smem;  // [128][128] f32 staging tile (the main loop ended with a barrier)
-    auto stage_acc = [&]() {
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    cs[cs_index(wm0 + i * 16 + (lane >> 4) * 4 + r, wn0 + j * 16 + (lane & 15))] = acc[i][j][r];
-    };
+    float* cs = (float*)smem;  // [128][128] f32 staging tile
     if (kchunk > 0) {       // split-K partial: plain f32 store of alpha * acc into this split's slab, no epilogue operands
-        stage_acc();
+        stage_acc(cs, acc, wave, lane);
         __syncthreads();
         float* slab = (float*)P.C + (size_t)ksplit_idx * (size_t)P.M * (size_t)P.ldc;
-        const float alpha = P.alpha == 0.f ? 1.0f : P.alpha;
-        for (int q = tid; q < BM * 16; q += NW * 64) {
-            const int row = q >> 4, cc = q & 15;
-            const int gm = m0 + row, gn = n0 + cc * 8;
-            if (gm >= M || gn >= N) continue;
-            const f32x4 x0 = *(const f32x4*)(cs + cs_index(row, cc * 8));
-            const f32x4 x1 = *(const f32x4*)(cs + cs_index(row, cc * 8 + 4));
-            float* c = slab + (size_t)gm * P.ldc + gn;
-            *(f32x4*)c = x0 * alpha;
-            *(f32x4*)(c + 4) = x1 * alpha;
-        }
+        store_slab(slab, cs, P.alpha == 0.f ? 1.0f : P.alpha, m0, n0, M, N, P.ldc, tid);
         trace_stamp(g, 3);
         return;
     }
@@ -423,7 +358,7 @@ __global__ __launch_bounds__(512, 4) void gemm_kernel(const GemmGroup g) {
     //  across the main loop cost more than the remaining exposed latency)
     EpiPrefetch<BM, NW * 64> pf;
     epilogue_prefetch<BM, NW * 64>(P, m0, n0, tid, M, pf);
-    stage_acc();
+    stage_acc(cs, acc, wave, lane);
     __syncthreads();
     epilogue_rows<BM, NW * 64, DROP, 1>(P, cs, m0, n0, tid, M, &pf);
     trace_stamp(g, 3);
@@ -453,8 +388,6 @@ int launch(const GemmGroup& g, hipStream_t s) {
     return launch2<LA, LB, false>(g, s);
 }
 
-int g_group_m = -1;        // MEMEHIP_GEMM_GROUP_M: L2 blocking of the tile order (default 8)
-
 }  // namespace
 
 extern "C" int mh_gemm_bf16_grouped(const MhGemmProblem* problems, int n_problems, int a_kmajor,
@@ -471,11 +404,6 @@ extern "C" int mh_gemm_bf16_grouped(const MhGemmProblem* problems, int n_problem
         if (rc != LAB_NOT_MINE) return rc;
     }
 #endif
-    if (g_group_m < 0) {
-        const char* e = getenv("MEMEHIP_GEMM_GROUP_M");
-        g_group_m = e ? atoi(e) : 8;
-        if (g_group_m < 0 || g_group_m > 64) g_group_m = 8;
-    }
     GemmGroup g;
     g.n = n_problems;
     int total = 0;
@@ -500,7 +428,7 @@ extern "C" int mh_gemm_bf16_grouped(const MhGemmProblem* problems, int n_problem
             if (!(p.flags & MH_GEMM_OUT_F32) || (p.flags & (MH_GEMM_ACCUM | MH_GEMM_GELU)) || p.bias || p.residual || p.aux || p.mul ||
                 p.rowsum || p.rows_dev || p.drop_rng)
                 return MH_EINVAL;
-            const int kc = ((p.K + p.ksplit - 1) / p.ksplit + BK - 1) / BK * BK;
+            const int kc = ksplit_chunk(p.K, p.ksplit);
             g.d[i].kchunk = kc;
             splits = (p.K + kc - 1) / kc;          // splits that actually hold rows (<= ksplit); the caller zero-fills the rest
             if (splits != p.ksplit) return MH_ESHAPE;
@@ -508,7 +436,7 @@ extern "C" int mh_gemm_bf16_grouped(const MhGemmProblem* problems, int n_problem
         total += g.d[i].tiles_m * g.d[i].tiles_n * splits;
     }
     g.total_tiles = total;
-    g.group_m = g_group_m;
+    g.group_m = group_m_setting();
     g.pad_ = 0;
     g.trace = g_trace;
     g.sk_partial = nullptr;
@@ -523,13 +451,7 @@ extern "C" int mh_gemm_bf16_grouped(const MhGemmProblem* problems, int n_problem
     return MH_EINVAL;  // (1,0) is not needed by the path
 }
 
-extern "C" int mh_gemm_ksplit_for(int K, int want) {
-    for (int sp = want; sp > 1; --sp) {
-        const int kc = ((K + sp - 1) / sp + BK - 1) / BK * BK;
-        if ((K + kc - 1) / kc == sp) return sp;
-    }
-    return 1;
-}
+extern "C" int mh_gemm_ksplit_for(int K, int want) { return ksplit_fit(K, want); }
 
 // profiling knob: with a device buffer of 4 x 8 bytes per workgroup of the largest launch, the kernel records 100-MHz stamps per
 // workgroup {entry, first K stage landed, main loop done, epilogue stores issued}; NULL switches it off (tools/gemm_timeline.py)

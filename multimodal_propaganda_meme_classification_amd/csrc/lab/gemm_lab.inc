@@ -2,6 +2,9 @@
 // dispatched kernels of gemm.hip on this path's shapes (DESIGN.md section 5).  Not part of the product: this file is
 // only compiled into libmemehip_lab*.so (`make LAB=1`, -DMH_LAB), which tools/ load through MEMEHIP_LIB for A/B runs.
 // Included by gemm.hip inside its anonymous namespace, after the shared helpers.
+constexpr int NTHREADS = 256;      // the 4-wave kernels' register staging
+using mh_tile::tile_coords;
+MH_DEV void tile_coords(const DevProblem& d, int group_m, int lt, int& tm, int& tn) { tile_coords(d.tiles_n, d.tiles_m, group_m, lt, tm, tn); }
 // ---- global -> registers (4 x 16 B per thread per operand) ------------------------------------
 template <int KMAJOR>
 MH_DEV void load_tile(__amdgpu_buffer_rsrc_t r, int ld, int r0, int k0, int tid, i32x4 (&v)[4]) {

@@ -47,7 +47,8 @@ def _run(*cmd):
 def code_object(obj: str, tmp: str) -> str:
     fat = os.path.join(tmp, os.path.basename(obj) + ".fat")
     co = os.path.join(tmp, os.path.basename(obj) + ".co")
-    _run(f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj)
+    # (an explicit output file: without one objcopy rewrites `obj` in place, and every guard run would make `make` relink)
+    _run(f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj, os.path.join(tmp, "objcopy.out"))
     _run(f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}", f"--targets={TARGET}", f"--output={co}")
     return co
 
