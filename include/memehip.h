@@ -668,6 +668,36 @@ int mh_cast_bf16_f32(const void* src, float* dst, int64_t n, mh_stream_t stream)
  * in[w][i]) with the sum in fp32 and a fixed order -- the shards received by the all-to-all, accumulated on receipt. */
 int mh_sum_shards_16(const void* in /*[W][shard]*/, void* out /*[shard]*/, int W, int64_t shard, mh_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Autoregressive decode (decode.hip): BLIP image captioning, one new token per row and step
+ * (BlipForConditionalGeneration.generate, greedy; Multimodal_example_task2C.py:195-256).  Every per-step state is read
+ * on the device, so one step is captured once as a hipGraph and replayed per token.  Deterministic (fixed-order sums).
+ *
+ * mh_attn_decode: one query per (row b, head h) against T cached keys / values, head dim 64, scale 1/8, f32 online softmax.
+ *   q  : 16-bit, (b, h) at q + b*ldq + h*64
+ *   k,v: 16-bit, key j of (b, h) at k + b*ld_b + j*ld_t + h*64 (v likewise)
+ *   t_dev == NULL: T keys (cross-attention over a fixed memory, e.g. 577 image tokens).
+ *   t_dev != NULL: self-attention over a cache of capacity T: this step's k of (b, h) at kv_new + b*ld_new + h*64 and its
+ *                  v H*64 elements further are stored into slot t = t_dev[0] first, and keys 0..t attend.
+ *   out: 16-bit, (b, h) at out + b*ldo + h*64.
+ *   nsplit > 1: the keys are cut into nsplit chunks (rows * heads too few to fill the chip); partials (m, l, acc) go to
+ *               workspace f32 [B*H][nsplit][66] and a second launch combines them in split order.  nsplit <= 64.
+ *   ldq, ld_t, ld_b, ld_new multiples of 8; bases 16-byte aligned.
+ * mh_decode_embed: y[b] = LayerNorm(word[ids[b]] + pos[t_dev[0]]) (f32 tables [V][D], [P][D]), 16-bit out [B][D], D <= 2048.
+ * mh_greedy_step: one launch per step over f32 logits [B][ldl] (columns >= V are never chosen; ties go to the lowest index).
+ *   state int32[4] = {t, arrival counter (0), rows finished, output length once all rows finished (0 before)}.
+ *   Column c = t + 1 of out_ids int64 [B][ld_out] receives the prompt token (c < prompt_len, read from out_ids itself), pad_id
+ *   (row finished before), or the argmax, which marks the row finished when it is eos_id.  next_ids[b] = that token; t += 1.
+ * ------------------------------------------------------------------------------------------ */
+int mh_attn_decode(const void* q, int ldq, void* k, void* v, int64_t ld_b, int ld_t, const void* kv_new, int ld_new,
+                   const int32_t* t_dev, int T, void* out, int ldo, float* workspace, int nsplit, int B, int H,
+                   mh_stream_t stream);
+int mh_decode_embed(const int64_t* ids /*[B]*/, const int32_t* t_dev, const float* word, const float* pos, const float* gamma,
+                    const float* beta, void* y, int B, int D, int V, int P, float eps, mh_stream_t stream);
+int mh_greedy_step(const float* logits, int ldl, int V, int B, int64_t* out_ids, int ld_out, int64_t* next_ids,
+                   int32_t* finished /*[B]*/, int32_t* state /*[4]*/, int prompt_len, int64_t eos_id, int64_t pad_id,
+                   mh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

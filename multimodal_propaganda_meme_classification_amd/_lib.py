@@ -209,6 +209,10 @@ _PROTOS = {
     "mh_cast_f32_bf16": [c_void_p, c_void_p, c_int64, c_void_p],
     "mh_cast_bf16_f32": [c_void_p, c_void_p, c_int64, c_void_p],
     "mh_sum_shards_16": [c_void_p, c_void_p, c_int, c_int64, c_void_p],
+    "mh_attn_decode": [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                       c_void_p, c_int, c_int, c_int, c_void_p],
+    "mh_decode_embed": [c_void_p] * 7 + [c_int] * 4 + [c_float, c_void_p],
+    "mh_greedy_step": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p],
     "mh_version": [],
     "mh_status_str": [c_int],
 }

@@ -1,0 +1,394 @@
+"""BLIP image captioning (``BlipForConditionalGeneration.generate``, greedy) on the HIP kernels: the caption tower of Kevin's model.
+
+The reference captions every image of every split inside ``MultimodalDataset.__init__`` (``Multimodal_example_task2C.py:195-256``):
+``Salesforce/blip-image-captioning-large`` in fp16, the prompt ``"a meme of"``, batches of 64, ``generate(..., max_new_tokens=128)``.
+``BlipCaptioner`` holds that model's parameters under transformers' state_dict names (``vision_model.*``, ``text_decoder.bert.*``,
+``text_decoder.cls.predictions.*``), so its checkpoint loads ``strict=True``, and ``generate`` returns the same token ids.
+
+Launch plan (activations are 16-bit row matrices, ``compute_dtype`` selects the bf16 or the fp16 library):
+
+* vision tower, forward only: ``mh_patchify`` + the patch GEMM, ``mh_vit_assemble_fwd`` (class token + positions), per pre-LN layer
+  LayerNorm -> QKV GEMM -> ``mh_attn_fwd`` -> projection GEMM (+ residual) -> LayerNorm -> fc1 (erf-GELU) -> fc2 (+ residual); then
+  ``post_layernorm``;
+* every decoder layer's cross-attention k / v over the image rows: grouped GEMMs, once per batch, into ``[B][577][k | v]``;
+* the decode step, one token per row: ``mh_decode_embed`` (word[id] + pos[t], LayerNorm); per layer the packed QKV GEMM,
+  ``mh_attn_decode`` (self: stores this step's k / v into cache slot t, attends 0..t), out-proj + residual, LayerNorm, cross Q GEMM,
+  ``mh_attn_decode`` (cross, 577 keys), out-proj + residual, LayerNorm, FFN (GELU epilogue), FFN + residual, LayerNorm; then the
+  LM-head transform (GEMM + GELU, LayerNorm), the decoder GEMM into f32 logits (vocabulary padded to a multiple of 128 with zero
+  rows) and ``mh_greedy_step``.  The prompt goes through the same step one token at a time (causal: the same result as a prefill).
+* The step reads t, the input ids and the finished flags on the device, so it is captured once as a single-stream hipGraph and
+  replayed per token; the host reads the "all rows finished" word every ``poll_every`` steps.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+import torch.nn as nn
+
+from . import _lib, ops
+
+F32, I32, I64 = torch.float32, torch.int32, torch.int64
+
+_TEXT_DEFAULTS = dict(vocab_size=30524, hidden_size=768, encoder_hidden_size=768, intermediate_size=3072, num_hidden_layers=12,
+                      num_attention_heads=8, max_position_embeddings=512, layer_norm_eps=1e-12, hidden_act="gelu",
+                      bos_token_id=30522, pad_token_id=0, sep_token_id=102)
+_VISION_DEFAULTS = dict(hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12, image_size=384,
+                        patch_size=16, layer_norm_eps=1e-5, hidden_act="gelu", num_channels=3)
+
+
+def _section(cfg, name, defaults):
+    sub = cfg.get(name) if isinstance(cfg, dict) else getattr(cfg, name)
+    if sub is None:
+        sub = {}
+    if not isinstance(sub, dict):
+        sub = sub.to_dict()
+    return {k: sub.get(k, v) for k, v in defaults.items()}
+
+
+def _lin(i, o):
+    return nn.Linear(i, o)
+
+
+class _VisionLayer(nn.Module):
+    def __init__(self, D, I, eps):
+        super().__init__()
+        self.self_attn = nn.Module()
+        self.self_attn.qkv = _lin(D, 3 * D)
+        self.self_attn.projection = _lin(D, D)
+        self.layer_norm1 = nn.LayerNorm(D, eps=eps)
+        self.mlp = nn.Module()
+        self.mlp.fc1 = _lin(D, I)
+        self.mlp.fc2 = _lin(I, D)
+        self.layer_norm2 = nn.LayerNorm(D, eps=eps)
+
+
+class _TextAttention(nn.Module):
+    def __init__(self, D, Dkv, eps):
+        super().__init__()
+        self.self = nn.Module()
+        self.self.query = _lin(D, D)
+        self.self.key = _lin(Dkv, D)
+        self.self.value = _lin(Dkv, D)
+        self.output = nn.Module()
+        self.output.dense = _lin(D, D)
+        self.output.LayerNorm = nn.LayerNorm(D, eps=eps)
+
+
+class _TextLayer(nn.Module):
+    def __init__(self, D, Denc, I, eps):
+        super().__init__()
+        self.attention = _TextAttention(D, D, eps)
+        self.crossattention = _TextAttention(D, Denc, eps)
+        self.intermediate = nn.Module()
+        self.intermediate.dense = _lin(D, I)
+        self.output = nn.Module()
+        self.output.dense = _lin(I, D)
+        self.output.LayerNorm = nn.LayerNorm(D, eps=eps)
+
+
+class BlipCaptioner(nn.Module):
+    """``BlipForConditionalGeneration`` (vision tower + text decoder + LM head) for greedy captioning on the HIP kernels."""
+
+    def __init__(self, text: dict, vision: dict, compute_dtype: str = "fp16"):
+        super().__init__()
+        if compute_dtype not in ("bf16", "fp16"):
+            raise ValueError(f"compute_dtype must be 'bf16' or 'fp16', got {compute_dtype!r}")
+        for nm, c in (("text", text), ("vision", vision)):
+            if c["hidden_size"] % c["num_attention_heads"] or c["hidden_size"] // c["num_attention_heads"] != 64:
+                raise ValueError(f"{nm}: head dim must be 64 (hidden_size / num_attention_heads)")
+            if c["hidden_size"] % 128 or c["intermediate_size"] % 128:
+                raise ValueError(f"{nm}: hidden_size and intermediate_size must be multiples of 128")
+            if c["hidden_act"] != "gelu":
+                raise ValueError(f"{nm}: only the erf GELU ('gelu') is implemented, got {c['hidden_act']!r}")
+        if text["encoder_hidden_size"] != vision["hidden_size"]:
+            raise ValueError("text encoder_hidden_size must equal the vision hidden_size")
+        if vision["patch_size"] % 8 or vision["image_size"] % vision["patch_size"] or vision["num_channels"] != 3:
+            raise ValueError("vision: 3 channels, patch_size a multiple of 8 dividing image_size")
+        self.text_cfg, self.vision_cfg, self.compute_dtype = dict(text), dict(vision), compute_dtype
+        Dv, Iv, ps = vision["hidden_size"], vision["intermediate_size"], vision["patch_size"]
+        n_pos = (vision["image_size"] // ps) ** 2 + 1
+        self.vision_model = nn.Module()
+        emb = nn.Module()
+        emb.class_embedding = nn.Parameter(torch.randn(1, 1, Dv) * 0.02)
+        emb.patch_embedding = nn.Conv2d(3, Dv, kernel_size=ps, stride=ps)
+        emb.position_embedding = nn.Parameter(torch.randn(1, n_pos, Dv) * 0.02)
+        self.vision_model.embeddings = emb
+        self.vision_model.encoder = nn.Module()
+        self.vision_model.encoder.layers = nn.ModuleList(
+            [_VisionLayer(Dv, Iv, vision["layer_norm_eps"]) for _ in range(vision["num_hidden_layers"])])
+        self.vision_model.post_layernorm = nn.LayerNorm(Dv, eps=vision["layer_norm_eps"])
+        D, V = text["hidden_size"], text["vocab_size"]
+        eps = text["layer_norm_eps"]
+        self.text_decoder = nn.Module()
+        bert = nn.Module()
+        bert.embeddings = nn.Module()
+        bert.embeddings.word_embeddings = nn.Embedding(V, D)
+        bert.embeddings.position_embeddings = nn.Embedding(text["max_position_embeddings"], D)
+        bert.embeddings.LayerNorm = nn.LayerNorm(D, eps=eps)
+        bert.encoder = nn.Module()
+        bert.encoder.layer = nn.ModuleList([_TextLayer(D, text["encoder_hidden_size"], text["intermediate_size"], eps)
+                                            for _ in range(text["num_hidden_layers"])])
+        self.text_decoder.bert = bert
+        cls = nn.Module()
+        cls.predictions = nn.Module()
+        cls.predictions.bias = nn.Parameter(torch.zeros(V))
+        cls.predictions.transform = nn.Module()
+        cls.predictions.transform.dense = _lin(D, D)
+        cls.predictions.transform.LayerNorm = nn.LayerNorm(D, eps=eps)
+        cls.predictions.decoder = _lin(D, V)
+        self.text_decoder.cls = cls
+        self._pack = None
+        self._pack_key = None
+        self._states = {}
+
+    @classmethod
+    def from_config(cls, cfg, compute_dtype: str = "fp16", device="cpu") -> "BlipCaptioner":
+        """``cfg``: a transformers ``BlipConfig`` or its ``to_dict()``; missing fields take BlipConfig's defaults."""
+        text, vision = _section(cfg, "text_config", _TEXT_DEFAULTS), _section(cfg, "vision_config", _VISION_DEFAULTS)
+        with torch.device(device):
+            return cls(text, vision, compute_dtype)
+
+    # ---- 16-bit GEMM operands (rebuilt when a parameter changed) --------------------------------------------------------------
+    def _T16(self):
+        return torch.float16 if self.compute_dtype == "fp16" else torch.bfloat16
+
+    def _packed(self):
+        params = list(self.parameters())
+        key = tuple((p.data_ptr(), p._version) for p in params)
+        if self._pack is not None and self._pack_key == key:
+            return self._pack
+        T16 = self._T16()
+
+        def w16(*ws):
+            return torch.cat([w.detach() for w in ws], 0).to(T16).contiguous()
+
+        def f32(*bs):
+            return torch.cat([b.detach().reshape(-1) for b in bs], 0).to(F32).contiguous()
+
+        def ln(m):
+            return f32(m.weight), f32(m.bias)
+
+        with torch.no_grad():
+            vm = self.vision_model
+            pe = vm.embeddings.patch_embedding
+            pk = {"patch": (w16(pe.weight.reshape(pe.out_channels, -1)), f32(pe.bias)),
+                  "cls": f32(vm.embeddings.class_embedding), "pos": f32(vm.embeddings.position_embedding),
+                  "post": ln(vm.post_layernorm), "vis": [], "txt": []}
+            for L in vm.encoder.layers:
+                pk["vis"].append((ln(L.layer_norm1), w16(L.self_attn.qkv.weight), f32(L.self_attn.qkv.bias),
+                                  w16(L.self_attn.projection.weight), f32(L.self_attn.projection.bias), ln(L.layer_norm2),
+                                  w16(L.mlp.fc1.weight), f32(L.mlp.fc1.bias), w16(L.mlp.fc2.weight), f32(L.mlp.fc2.bias)))
+            bert = self.text_decoder.bert
+            pk["word"] = f32(bert.embeddings.word_embeddings.weight).view(-1, self.text_cfg["hidden_size"])
+            pk["tpos"] = f32(bert.embeddings.position_embeddings.weight).view(-1, self.text_cfg["hidden_size"])
+            pk["emb_ln"] = ln(bert.embeddings.LayerNorm)
+            for L in bert.encoder.layer:
+                sa, ca = L.attention, L.crossattention
+                pk["txt"].append(dict(
+                    wqkv=w16(sa.self.query.weight, sa.self.key.weight, sa.self.value.weight),
+                    bqkv=f32(sa.self.query.bias, sa.self.key.bias, sa.self.value.bias),
+                    wo=w16(sa.output.dense.weight), bo=f32(sa.output.dense.bias), ln1=ln(sa.output.LayerNorm),
+                    wcq=w16(ca.self.query.weight), bcq=f32(ca.self.query.bias),
+                    wckv=w16(ca.self.key.weight, ca.self.value.weight), bckv=f32(ca.self.key.bias, ca.self.value.bias),
+                    wco=w16(ca.output.dense.weight), bco=f32(ca.output.dense.bias), ln2=ln(ca.output.LayerNorm),
+                    wi=w16(L.intermediate.dense.weight), bi=f32(L.intermediate.dense.bias),
+                    wout=w16(L.output.dense.weight), bout=f32(L.output.dense.bias), ln3=ln(L.output.LayerNorm)))
+            pr = self.text_decoder.cls.predictions
+            V, D = pr.decoder.weight.shape
+            Vp = (V + 127) // 128 * 128
+            wdec = torch.zeros((Vp, D), dtype=T16, device=pr.decoder.weight.device)
+            wdec[:V] = pr.decoder.weight.detach().to(T16)
+            bdec = torch.zeros(Vp, dtype=F32, device=wdec.device)
+            bdec[:V] = pr.decoder.bias.detach().to(F32)
+            pk["head"] = (w16(pr.transform.dense.weight), f32(pr.transform.dense.bias), ln(pr.transform.LayerNorm), wdec, bdec)
+        self._pack, self._pack_key = pk, key
+        self._states = {}
+        return pk
+
+    # ---- vision tower ---------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def vision_forward(self, pixel_values: torch.Tensor) -> torch.Tensor:
+        """``vision_model(pixel_values)[0]`` (after ``post_layernorm``): 16-bit [B * (1 + patches), D]."""
+        if not pixel_values.is_cuda:
+            raise _lib.MemehipError("BlipCaptioner runs on the HIP device only (no CPU fallback): move the batch with .to(device)")
+        vc = self.vision_cfg
+        S = vc["image_size"]
+        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, S, S):
+            raise ValueError(f"pixel_values must be [B, 3, {S}, {S}] (the config's image_size; no interpolate_pos_encoding)")
+        pk = self._packed()
+        B = pixel_values.shape[0]
+        D, H, ps, eps = vc["hidden_size"], vc["num_attention_heads"], vc["patch_size"], vc["layer_norm_eps"]
+        Np = (S // ps) ** 2
+        T16 = self._T16()
+        patches = ops.patchify(pixel_values.detach().to(F32).contiguous(), ps, dtype=T16)
+        proj = ops.linear_fwd(patches, pk["patch"][0], bias=pk["patch"][1])
+        x = torch.empty((B * (Np + 1), D), dtype=T16, device=pixel_values.device)
+        ops.vit_assemble_fwd(proj, pk["cls"], pk["pos"], x, B, Np, D)
+        for (g1, b1), wqkv, bqkv, wo, bo, (g2, b2), w1, bb1, w2, bb2 in pk["vis"]:
+            h, _, _ = ops.layernorm_fwd(x, g1, b1, eps)
+            qkv = ops.linear_fwd(h, wqkv, bias=bqkv)
+            a, _ = ops.attn_fwd(qkv, None, B, Np + 1, H)
+            x = ops.linear_fwd(a, wo, bias=bo, residual=x)
+            h, _, _ = ops.layernorm_fwd(x, g2, b2, eps)
+            f = ops.linear_fwd(h, w1, bias=bb1, gelu=True)
+            x = ops.linear_fwd(f, w2, bias=bb2, residual=x)
+        y, _, _ = ops.layernorm_fwd(x, *pk["post"], eps)
+        return y
+
+    # ---- decoder state and one step -------------------------------------------------------------------------------------------
+    def _state(self, B: int, cap: int, device):
+        key = (B, cap, str(device))
+        if key in self._states:
+            return self._states[key]
+        tc, T16 = self.text_cfg, self._T16()
+        D, I, H, nl = tc["hidden_size"], tc["intermediate_size"], tc["num_attention_heads"], tc["num_hidden_layers"]
+        Ni = (self.vision_cfg["image_size"] // self.vision_cfg["patch_size"]) ** 2 + 1
+        Vp = self._pack["head"][3].shape[0]
+        e = lambda *s, dt=T16: torch.empty(s, dtype=dt, device=device)
+        ns_self, ns_cross = ops.decode_splits(B, H, cap), ops.decode_splits(B, H, Ni)
+        st = dict(B=B, cap=cap, Ni=Ni, ns_self=ns_self, ns_cross=ns_cross,
+                  cache=[torch.zeros((B, cap, 2 * D), dtype=T16, device=device) for _ in range(nl)],
+                  ckv=[e(B * Ni, 2 * D) for _ in range(nl)],
+                  x=e(B, D), x1=e(B, D), s=e(B, D), ctx=e(B, D), q=e(B, D), qkv=e(B, 3 * D), ffn=e(B, I), h=e(B, D),
+                  mean=e(B, dt=F32), rstd=e(B, dt=F32), logits=e(B, Vp, dt=F32),
+                  ws=e(B * H * max(ns_self, ns_cross, 1) * 66, dt=F32),
+                  out_ids=e(B, cap, dt=I64), next_ids=e(B, dt=I64), finished=e(B, dt=I32), sv=e(4, dt=I32), graph=None)
+        self._states = {key: st}          # one live batch shape at a time (the caches are large)
+        return st
+
+    def _step(self, st):
+        pk, tc = self._pack, self.text_cfg
+        B, cap, Ni = st["B"], st["cap"], st["Ni"]
+        D, H, eps = tc["hidden_size"], tc["num_attention_heads"], tc["layer_norm_eps"]
+        t = st["sv"][0:1]
+        x, x1, s, ctx, q, qkv, ffn, h = (st[k] for k in ("x", "x1", "s", "ctx", "q", "qkv", "ffn", "h"))
+        mean, rstd, ws = st["mean"], st["rstd"], st["ws"]
+        ops.decode_embed(st["next_ids"], t, pk["word"], pk["tpos"], *pk["emb_ln"], eps, x)
+        qkv_flat = qkv.view(-1)
+        for lw, cache, ckv in zip(pk["txt"], st["cache"], st["ckv"]):
+            cf, kf = cache.view(-1), ckv.view(-1)
+            ops.linear_fwd(x, lw["wqkv"], bias=lw["bqkv"], out=qkv)
+            ops.attn_decode(qkv, cf, cf[D:], ctx, B, H, cap, 3 * D, cap * 2 * D, 2 * D, D, t_dev=t, kv_new=qkv_flat[D:], ld_new=3 * D,
+                            nsplit=st["ns_self"], workspace=ws)
+            ops.linear_fwd(ctx, lw["wo"], bias=lw["bo"], residual=x, out=s)
+            ops.layernorm_fwd(s, *lw["ln1"], eps, y=x1, mean=mean, rstd=rstd)
+            ops.linear_fwd(x1, lw["wcq"], bias=lw["bcq"], out=q)
+            ops.attn_decode(q, kf, kf[D:], ctx, B, H, Ni, D, Ni * 2 * D, 2 * D, D, nsplit=st["ns_cross"], workspace=ws)
+            ops.linear_fwd(ctx, lw["wco"], bias=lw["bco"], residual=x1, out=s)
+            ops.layernorm_fwd(s, *lw["ln2"], eps, y=x1, mean=mean, rstd=rstd)
+            ops.linear_fwd(x1, lw["wi"], bias=lw["bi"], gelu=True, out=ffn)
+            ops.linear_fwd(ffn, lw["wout"], bias=lw["bout"], residual=x1, out=s)
+            ops.layernorm_fwd(s, *lw["ln3"], eps, y=x, mean=mean, rstd=rstd)
+        wt, bt, lnh, wdec, bdec = pk["head"]
+        ops.linear_fwd(x, wt, bias=bt, gelu=True, out=h)
+        ops.layernorm_fwd(h, *lnh, eps, y=x1, mean=mean, rstd=rstd)
+        Vp = wdec.shape[0]
+        ops.gemm_grouped([ops.Gemm(x1, wdec, st["logits"], B, Vp, D, D, D, Vp, bias=bdec)], False, False)
+        ops.greedy_step(st["logits"], tc["vocab_size"], st["out_ids"], st["next_ids"], st["finished"], st["sv"], st["P"],
+                        tc["sep_token_id"], tc["pad_token_id"])
+
+    def _prepare(self, pixel_values, prompt, cap):
+        """vision tower, cross k / v of every layer, and the step's state for this prompt (int64 [B, P] on the device)."""
+        img = self.vision_forward(pixel_values)
+        B, P = prompt.shape
+        st = self._state(B, cap, pixel_values.device)
+        st["P"] = P
+        D = self.text_cfg["hidden_size"]
+        gs = [ops.Gemm(img, lw["wckv"], ckv, img.shape[0], 2 * D, img.shape[1], img.shape[1], img.shape[1], 2 * D, bias=lw["bckv"])
+              for lw, ckv in zip(self._pack["txt"], st["ckv"])]
+        for i in range(0, len(gs), _lib.MH_GEMM_MAX_GROUP):
+            ops.gemm_grouped(gs[i:i + _lib.MH_GEMM_MAX_GROUP], False, False)
+        st["out_ids"].fill_(self.text_cfg["pad_token_id"])
+        st["out_ids"][:, :P] = prompt
+        st["next_ids"].copy_(prompt[:, 0])
+        st["finished"].zero_()
+        st["sv"].zero_()
+        return st
+
+    def _run(self, st, steps: int, graph: bool, poll_every: int, record=None):
+        """``steps`` decode steps (stops early once every row has finished, checked every ``poll_every`` steps)."""
+        for i in range(steps):
+            if i == 0 or not graph:
+                self._step(st)
+            else:
+                if st["graph"] is None or st["graph_P"] != st["P"]:
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        self._step(st)
+                    st["graph"], st["graph_P"] = g, st["P"]
+                st["graph"].replay()
+            if record is not None:
+                record.append(st["logits"][:, :self.text_cfg["vocab_size"]].clone())
+            if i + 1 < steps and (i + 1) % poll_every == 0 and int(st["sv"][3]) != 0:
+                break
+
+    # ---- public surface -------------------------------------------------------------------------------------------------------
+    def _prompt(self, pixel_values, input_ids, attention_mask):
+        B = pixel_values.shape[0]
+        tc = self.text_cfg
+        if input_ids is None:
+            ids = torch.tensor([[tc["bos_token_id"], tc["sep_token_id"]]], dtype=I64).repeat(B, 1)
+        else:
+            ids = torch.as_tensor(input_ids).to(I64).clone()
+        if ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] < 2:
+            raise ValueError("input_ids must be [B, L] with L >= 2 (the processor's prompt ends with [SEP], which generate drops)")
+        if attention_mask is not None and bool((torch.as_tensor(attention_mask) == 0).any()):
+            raise ValueError("prompt attention masks with zeros are not implemented (every prompt of a batch has the same length)")
+        ids[:, 0] = tc["bos_token_id"]
+        return ids[:, :-1]
+
+    @torch.no_grad()
+    def generate(self, pixel_values: torch.Tensor, input_ids: Optional[torch.Tensor] = None, attention_mask=None,
+                 max_new_tokens: int = 20, *, graph: bool = True, poll_every: int = 8, num_beams: int = 1, do_sample: bool = False,
+                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_length: int = 0, min_new_tokens: int = 0,
+                 interpolate_pos_encoding: bool = False) -> torch.LongTensor:
+        """``BlipForConditionalGeneration.generate(pixel_values, input_ids, attention_mask, max_new_tokens=...)`` under greedy
+        decoding: ``input_ids[:, 0]`` becomes ``bos_token_id``, the last prompt token is dropped, rows that emitted eos
+        (``sep_token_id``) continue with ``pad_token_id``, and the output ends at the step where the last row finished (or after
+        ``max_new_tokens``).  ``graph=False`` runs the same launches without the hipGraph."""
+        if num_beams != 1:
+            raise ValueError("beam search (num_beams > 1) is not implemented")
+        if do_sample:
+            raise ValueError("sampling is not implemented (greedy decoding only)")
+        if repetition_penalty != 1.0:
+            raise ValueError("repetition_penalty != 1 is not implemented")
+        if no_repeat_ngram_size:
+            raise ValueError("no_repeat_ngram_size is not implemented")
+        if min_length or min_new_tokens:
+            raise ValueError("min_length / min_new_tokens > 0 are not implemented")
+        if interpolate_pos_encoding:
+            raise ValueError("interpolate_pos_encoding is not implemented: pixel_values must have the config's image_size")
+        if int(max_new_tokens) < 1 or int(poll_every) < 1:
+            raise ValueError("max_new_tokens and poll_every must be >= 1")
+        S = self.vision_cfg["image_size"]
+        if not isinstance(pixel_values, torch.Tensor) or pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, S, S):
+            raise ValueError(f"pixel_values must be [B, 3, {S}, {S}] (the config's image_size; no interpolate_pos_encoding)")
+        prompt = self._prompt(pixel_values, input_ids, attention_mask)
+        if not pixel_values.is_cuda or not next(self.parameters()).is_cuda:
+            raise _lib.MemehipError("BlipCaptioner runs on the HIP device only (no CPU fallback): move the model and batch with .to(device)")
+        prompt = prompt.to(pixel_values.device)
+        P = prompt.shape[1]
+        cap = P + int(max_new_tokens)
+        if cap > self.text_cfg["max_position_embeddings"]:
+            raise ValueError("prompt + max_new_tokens exceeds max_position_embeddings")
+        self._packed()
+        st = self._prepare(pixel_values, prompt, cap)
+        self._run(st, P - 1 + int(max_new_tokens), graph, int(poll_every))
+        sv = st["sv"].cpu()
+        length = int(sv[3]) if int(sv[3]) else min(cap, int(sv[0]) + 1)
+        return st["out_ids"][:, :length].clone()
+
+    @torch.no_grad()
+    def teacher_forced_logits(self, pixel_values: torch.Tensor, input_ids: torch.Tensor, graph: bool = False) -> torch.Tensor:
+        """f32 [B, L, vocab]: the LM-head logits after each token of ``input_ids`` (used as given, no bos substitution), fed one
+        per step through the decode step -- ``text_decoder(input_ids, encoder_hidden_states=vision(pixel_values)[0]).logits``."""
+        if not pixel_values.is_cuda:
+            raise _lib.MemehipError("BlipCaptioner runs on the HIP device only (no CPU fallback)")
+        ids = torch.as_tensor(input_ids).to(I64).to(pixel_values.device)
+        B, L = ids.shape
+        self._packed()
+        st = self._prepare(pixel_values, ids, L + 1)
+        rec = []
+        self._run(st, L, graph, L + 1, record=rec)
+        return torch.stack(rec, 1)

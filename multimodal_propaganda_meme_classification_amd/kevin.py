@@ -2,8 +2,9 @@
 
 * ``KevinMultimodalDataset`` (:208-304) -- the organizers' dataset plus the caption stream: dict keys ``id, text, text_mask,
   caption_text, caption_text_mask, image[, label]``.  The reference generates the captions with BLIP inside ``__init__``
-  (``ImageCaptioning``, :195-206, out of this path's scope): here they are passed in (``captions``: one string per sample, e.g. the
-  reference's own BLIP output) or produced by a caller-supplied ``caption_fn(list of image paths) -> list of str``.
+  (``ImageCaptioning``, :195-206): here they are passed in (``captions``: one string per sample) or produced by a
+  ``caption_fn(list of image paths) -> list of str`` -- ``blip_caption_fn(processor, captioner)`` is the reference's BLIP captioning
+  on the HIP kernels (``blip.BlipCaptioner``; ``BlipImageCaptioning`` is its ``ImageCaptioning``).
 * ``train / test / evaluate`` (:688-871): the same loops -- focal loss called as ``criterion(output, labels, alpha=0.25, gamma=2.0,
   reduction='mean')``, gradient norm + clip, ``scheduler.step()`` per batch, accuracy from ``sigmoid(output) > 0.5``; ``test``
   returns ``(loss, accuracy, macro_f1, optimal_threshold)`` with the threshold at the ROC point of maximum ``tpr - fpr``
@@ -45,8 +46,8 @@ class KevinMultimodalDataset(Dataset):
         self.max_seq_len, self.image_size, self.image_root, self.synthetic_images = max_seq_len, image_size, image_root, synthetic_images
         if captions is None:
             if caption_fn is None:
-                raise ValueError("KevinMultimodalDataset needs `captions` (one string per sample) or a `caption_fn`: the BLIP captioner "
-                                 "of the reference (ImageCaptioning) is outside this package")
+                raise ValueError("KevinMultimodalDataset needs `captions` (one string per sample) or a `caption_fn`, e.g. "
+                                 "blip_caption_fn(processor, captioner) (the reference's ImageCaptioning on blip.BlipCaptioner)")
             captions = caption_fn([os.path.join(image_root, p) for p in self.image_data])
         self.precalculated_captions = list(captions)
         if len(self.precalculated_captions) != len(self.ids):
@@ -76,6 +77,43 @@ class KevinMultimodalDataset(Dataset):
         if not self.is_test:
             fdata["label"] = torch.tensor(self.labels[index], dtype=torch.long)
         return fdata
+
+
+class BlipImageCaptioning:
+    """The reference's ``ImageCaptioning`` (``Multimodal_example_task2C.py:195-206``) on ``blip.BlipCaptioner``: the same
+    ``generate_caption(images, texts) -> list of str``, greedy with ``max_new_tokens=128``.  The caller supplies the
+    ``BlipProcessor`` (image preprocessing, prompt tokens and decoding; there is no tokenizer or hub access here) and the captioner
+    holding the ``blip-image-captioning-large`` weights (``BlipCaptioner.from_config(cfg, device=...)`` +
+    ``load_state_dict(BlipForConditionalGeneration state_dict)``)."""
+
+    def __init__(self, processor, captioner, max_new_tokens: int = 128, graph: bool = True):
+        self.processor, self.model, self.max_new_tokens, self.graph = processor, captioner, int(max_new_tokens), graph
+        self.device = next(captioner.parameters()).device
+
+    def generate_caption(self, images, texts):
+        inputs = self.processor(images, texts, return_tensors="pt", padding=True)
+        ids = self.model.generate(inputs["pixel_values"].to(self.device, torch.float32), inputs["input_ids"], inputs.get("attention_mask"),
+                                  max_new_tokens=self.max_new_tokens, graph=self.graph)
+        return [self.processor.decode(c, skip_special_tokens=True) for c in ids.cpu()]
+
+
+def blip_caption_fn(processor, captioner, prompt: str = "a meme of", batch_size: int = 64, max_new_tokens: int = 128,
+                    image_loader: Optional[Callable] = None) -> Callable:
+    """``caption_fn(paths) -> list of str`` for ``KevinMultimodalDataset``: the reference's ``precompute_captions`` (:235-251) --
+    images opened as RGB in batches of ``batch_size`` and captioned with ``prompt`` -- on ``BlipImageCaptioning``."""
+    cap = BlipImageCaptioning(processor, captioner, max_new_tokens=max_new_tokens)
+    if image_loader is None:
+        def image_loader(path):
+            from PIL import Image
+            return Image.open(path).convert("RGB")
+
+    def caption_fn(paths):
+        out = []
+        for i in range(0, len(paths), batch_size):
+            imgs = [image_loader(p) for p in paths[i:i + batch_size]]
+            out.extend(cap.generate_caption(imgs, [prompt] * len(imgs)))
+        return out
+    return caption_fn
 
 
 def kevin_collate(items):

@@ -599,3 +599,75 @@ def sum_shards_16(shards, out, W: int):
     shard = out.numel()
     assert shards.numel() >= W * shard and shards.dtype == out.dtype
     check(_L(out).mh_sum_shards_16(_p(shards), _p(out), int(W), shard, _stream()), "mh_sum_shards_16")
+
+
+# ---------------------------------------------------------------------------------------------
+# autoregressive decode (decode.hip; blip.BlipCaptioner)
+# ---------------------------------------------------------------------------------------------
+
+def decode_splits(B: int, H: int, T: int) -> int:
+    """Key splits of mh_attn_decode: 1 when the B*H workgroups fill the chip's 256 CUs, else enough chunks of >= 64 keys to
+    reach about 256 workgroups (B = 1, H = 12: 12 workgroups -> up to 22 splits of a long cache)."""
+    if B * H >= 256:
+        return 1
+    return max(1, min(64, -(-256 // (B * H)), -(-T // 64)))
+
+
+def _i32(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32):
+        raise _lib.MemehipError(f"{name}: expected a device int32 tensor")
+    return t
+
+
+def attn_decode(q, k, v, out, B, H, T, ldq, ld_b, ld_t, ldo, t_dev=None, kv_new=None, ld_new=0, nsplit=None, workspace=None):
+    """mh_attn_decode: out[b, h] = softmax(q[b, h] . k[b, h, :T]^T / 8) v[b, h, :T] (16-bit views with element strides; see the
+    header).  t_dev (device int32 [1]) selects the self-attention form: kv_new's k / v rows are stored into slot t first and keys
+    0..t attend (T = the cache capacity).  nsplit None: decode_splits(B, H, T); a workspace is allocated when it is > 1."""
+    for nm, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        _chk(t, BF16, nm, False)
+    if len({q.dtype, k.dtype, v.dtype, out.dtype}) != 1:
+        raise TypeError("attn_decode: q, k, v, out must share one 16-bit dtype")
+    if t_dev is not None:
+        _i32(t_dev, "t_dev")
+        _chk(kv_new, BF16, "kv_new", False)
+        if kv_new.dtype != q.dtype or kv_new.numel() < (B - 1) * ld_new + 2 * H * 64:
+            raise ValueError("attn_decode: kv_new smaller than B / ld_new / H imply")
+    if q.numel() < (B - 1) * ldq + H * 64 or out.numel() < (B - 1) * ldo + H * 64:
+        raise ValueError("attn_decode: q / out smaller than B / ld / H imply")
+    need = (B - 1) * ld_b + (T - 1) * ld_t + H * 64
+    if k.numel() < need or v.numel() < need:
+        raise ValueError("attn_decode: k / v smaller than B / T / strides imply")
+    nsplit = decode_splits(B, H, T) if nsplit is None else int(nsplit)
+    if nsplit > 1:
+        if workspace is None:
+            workspace = torch.empty(B * H * nsplit * 66, dtype=F32, device=q.device)
+        _chk(workspace, F32, "workspace")
+        if workspace.numel() < B * H * nsplit * 66:
+            raise ValueError("attn_decode: workspace smaller than B * H * nsplit * 66")
+    check(_L(q).mh_attn_decode(_p(q), int(ldq), _p(k), _p(v), int(ld_b), int(ld_t), _p(kv_new), int(ld_new), _p(t_dev), int(T), _p(out),
+                               int(ldo), _p(workspace) if nsplit > 1 else None, nsplit, int(B), int(H), _stream()), "mh_attn_decode")
+    return out
+
+
+def decode_embed(ids, t_dev, word, pos, gamma, beta, eps, y):
+    """mh_decode_embed: y[b] = LayerNorm(word[ids[b]] + pos[t]) (16-bit [B, D])."""
+    _chk(ids, I64, "ids"), _i32(t_dev, "t_dev"), _chk(word, F32, "word"), _chk(pos, F32, "pos")
+    _chk(gamma, F32, "gamma"), _chk(beta, F32, "beta"), _chk(y, BF16, "y")
+    B = ids.numel()
+    V, D = word.shape
+    if pos.shape[1] != D or gamma.numel() != D or beta.numel() != D or y.numel() < B * D:
+        raise ValueError("decode_embed: table / output widths disagree")
+    check(_L(y).mh_decode_embed(_p(ids), _p(t_dev), _p(word), _p(pos), _p(gamma), _p(beta), _p(y), B, D, V, pos.shape[0], float(eps),
+                                _stream()), "mh_decode_embed")
+    return y
+
+
+def greedy_step(logits, V, out_ids, next_ids, finished, state, prompt_len, eos_id, pad_id):
+    """mh_greedy_step over f32 logits [B, ldl] (ldl >= V): see include/memehip.h."""
+    _chk(logits, F32, "logits"), _chk(out_ids, I64, "out_ids"), _chk(next_ids, I64, "next_ids")
+    _i32(finished, "finished"), _i32(state, "state")
+    B, ldl = logits.shape
+    if out_ids.dim() != 2 or out_ids.shape[0] != B or next_ids.numel() < B or finished.numel() < B or state.numel() < 4 or V > ldl:
+        raise ValueError("greedy_step: shapes disagree")
+    check(_lib.load().mh_greedy_step(_p(logits), ldl, int(V), B, _p(out_ids), out_ids.shape[1], _p(next_ids), _p(finished), _p(state),
+                                     int(prompt_len), int(eos_id), int(pad_id), _stream()), "mh_greedy_step")
