@@ -4,13 +4,19 @@ Adam) of the Subtask-2C dual encoder, ViT-B/16 + BERT-base(V=64000), 224x224 + 1
 per GPU (BASELINE.json configs[2]; configs[3] = the same per-GPU work on N GPUs, weak scaling).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --full          # + roofline, the secondary lines, cpu_baseline
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0).  Inputs are synthetic and already resident in HBM when the timed
 region starts; a "step" is one pass of the hot path over one batch.
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: nothing
+else.  Whatever takes runs of its own comes with --full:
 `roofline` prices the dominant kernel (the grouped bf16 MFMA GEMM with the largest share of the
 step) from HIP events recorded around each of its launches on the launch stream, in an
 instrumented eager replay of the same prepared launches right after the timed region.
+`value_<variant>` / `ms_per_step_<variant>` (single GPU, config 3) time the same step under other
+switches (other storage type, all-ones masks, dense text rows, unguarded / clipped / dropout
+variants, one resident batch) and BASELINE configs 5 and 2.
 `cpu_baseline` times the CPU oracle (oracle/meme_oracle.py, a port -- the reference itself cannot
 run here) on a bounded sample of the same workload on this host's cores.
 """
@@ -46,11 +52,14 @@ def parse():
                     help="BASELINE.json configuration: 3 = ViT-B/16 + BERT-base (the headline metric), "
                          "5 = CLIP ViT-L/14@336 + BERT-large, seq 256, 2 = Subtask-2B ResNet-50 image-only (single GPU)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the dominant kernel's roofline (instrumented replay), the "
+                         "secondary lines and the CPU baseline.  Without it a run prints the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=32)
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary lines (other storage type, all-ones masks, dense text rows, unguarded / clipped / dropout "
-                         "variants, configs 5 and 2)")
+                    help="with --full: skip the secondary lines (other storage type, all-ones masks, dense text rows, unguarded / "
+                         "clipped / dropout variants, configs 5 and 2)")
     ap.add_argument("--batches", type=int, default=8,
                     help="distinct synthetic batches resident in HBM, loaded in turn (one device-to-device copy per step inside the timed "
                          "region): other token ids, other ragged masks every step, as a DataLoader would hand over; 1 = replay one batch")
@@ -76,7 +85,7 @@ def parse():
     ap.add_argument("--dtype", choices=("bf16", "fp16"), default="fp16",
                     help="16-bit storage / MFMA operand type of the towers (same kernels, same MFMA peak).  Default fp16: the "
                          "storage type that meets north_star's 1e-3 logit tolerance (and the reference's own AMP arithmetic, "
-                         "Multimodal_example_task2C.py:60-64); the bf16 build is timed beside it (value_bf16)")
+                         "Multimodal_example_task2C.py:60-64); the bf16 build is timed beside it with --full (value_bf16)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (loss, correct count, logits, a seeded sample "
                          "of every updated parameter) as DIR/<name>.npy in float32, to compare two builds output for output")
@@ -320,6 +329,59 @@ def bench_config2(args, dump_dir=None):
     return out
 
 
+def gemm_roofline(plan, args, value, world, dyn_scale):
+    """`roofline` of the dominant kernel: an instrumented eager replay of the step's prepared launches on the launch stream.
+    ``dyn_scale`` = live / allocated text rows (the text launches are sized for batch*seq rows and clamp on the device)."""
+    stream = torch.cuda.current_stream().cuda_stream
+    tags = ("gemm<0,0>", "gemm<0,1>", "gemm<1,1>")
+    per_tag = {}
+    for tag in tags:
+        recs = []
+        for _ in range(3):
+            plan.fwd.run_timed(stream, tag, recs, dyn_scale)
+            plan.loss.run(stream)
+            for seg in plan.bwd:
+                seg.run_timed(stream, tag, recs, dyn_scale)
+        torch.cuda.synchronize()
+        ms = [e0.elapsed_time(e1) for e0, e1, _ in recs]
+        per_tag[tag] = dict(launches=len(recs) // 3, total_ms=sum(ms) / 3, flops=sum(w for _, _, w in recs) / 3)
+    dom = max(per_tag, key=lambda k: per_tag[k]["total_ms"])
+    d = per_tag[dom]
+    achieved = d["flops"] / (d["total_ms"] * 1e-3) / 1e12
+    # HBM bytes per launch of that kernel: from the committed rocprofv3 --pmc passes (FETCH_SIZE x2 + WRITE_SIZE,
+    # tools/traffic_from_pmc.py); PMC counters cannot be read from inside the process
+    traffic = None
+    traffic_src = None
+    try:
+        tpath = next(pth for pth in (os.path.join(ROOT, "profiles", f) for f in ("r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"))
+                     if os.path.exists(pth))
+        traffic_src = os.path.relpath(tpath, ROOT)
+        tj = json.load(open(tpath))["kernels"]
+        pref = f"gemm_kernel<{dom[5]}, {dom[7]},"
+        hit = [v for k, v in tj.items() if k.startswith(pref)]
+        if hit and not args.tiny and args.batch == 32 and args.config == 3:
+            traffic = max(hit, key=lambda v: v["launches_sampled"])["hbm_bytes_per_launch"]
+    except Exception:
+        traffic = None
+    flop_per_meme = FLOP_PER_MEME[args.config] if not args.tiny else plan.gemm_flops / args.batch
+    # FLOPs actually executed: the GEMM work of the text rows that were packed away is not counted
+    flop_exec_per_meme = flop_per_meme - plan.gemm_flops_dyn * (1.0 - dyn_scale) / args.batch
+    return {"bound": "mfma", "kernel": f"gemm_kernel{dom[4:]} (grouped {args.dtype} MFMA GEMM)",
+            "achieved": round(achieved, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
+            "traffic_source": (f"{traffic_src}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command "
+                               "(FETCH x2, KiB -> bytes; tools/collect_profiles.sh), per launch of this kernel; "
+                               "PMC counters cannot be read from inside the process") if traffic is not None else None,
+            "method": "HIP events around every launch of the kernel on its launch stream, in an eager one-stream "
+                      "replay of the step's prepared launches right after the timed region (3 replays averaged)",
+            "launches_per_step": d["launches"], "avg_launch_us": round(d["total_ms"] / d["launches"] * 1e3, 2),
+            "flops_per_launch": round(d["flops"] / d["launches"]),
+            "all_gemm_kernels": {k: {"ms_per_step": round(v["total_ms"], 3),
+                                     "tflops": round(v["flops"] / (v["total_ms"] * 1e-3) / 1e12, 1)}
+                                 for k, v in per_tag.items()},
+            "step_mfma_frac": round(flop_exec_per_meme * value / world / (MFMA_PEAK_TFLOPS * 1e12), 4)}
+
+
 def main():
     args = parse()
     if args.config == 2:
@@ -405,46 +467,11 @@ def main():
 
     out = None
     if rank == 0:
-        # ---- roofline of the dominant kernel: instrumented eager replay on the launch stream -------
         plan = step.plan
-        stream = torch.cuda.current_stream().cuda_stream
         # padding-free text tower: the text launches are sized for batch*seq rows and clamp to the live rows on the device
         max_rows = args.batch * args.seq
         live_rows = int(plan.buf["pk.n_rows"]) if plan.packed else max_rows
-        dyn_scale = live_rows / max_rows
-        tags = ("gemm<0,0>", "gemm<0,1>", "gemm<1,1>")
-        per_tag = {}
-        for tag in tags:
-            recs = []
-            for _ in range(3):
-                plan.fwd.run_timed(stream, tag, recs, dyn_scale)
-                plan.loss.run(stream)
-                for seg in plan.bwd:
-                    seg.run_timed(stream, tag, recs, dyn_scale)
-            torch.cuda.synchronize()
-            ms = [e0.elapsed_time(e1) for e0, e1, _ in recs]
-            per_tag[tag] = dict(launches=len(recs) // 3, total_ms=sum(ms) / 3, flops=sum(w for _, _, w in recs) / 3)
-        dom = max(per_tag, key=lambda k: per_tag[k]["total_ms"])
-        d = per_tag[dom]
-        achieved = d["flops"] / (d["total_ms"] * 1e-3) / 1e12
-        # HBM bytes per launch of that kernel: from the committed rocprofv3 --pmc passes (FETCH_SIZE x2 + WRITE_SIZE,
-        # tools/traffic_from_pmc.py); PMC counters cannot be read from inside the process
-        traffic = None
-        traffic_src = None
-        try:
-            tpath = next(pth for pth in (os.path.join(ROOT, "profiles", f) for f in ("r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"))
-                         if os.path.exists(pth))
-            traffic_src = os.path.relpath(tpath, ROOT)
-            tj = json.load(open(tpath))["kernels"]
-            pref = f"gemm_kernel<{dom[5]}, {dom[7]},"
-            hit = [v for k, v in tj.items() if k.startswith(pref)]
-            if hit and not args.tiny and args.batch == 32 and args.config == 3:
-                traffic = max(hit, key=lambda v: v["launches_sampled"])["hbm_bytes_per_launch"]
-        except Exception:
-            traffic = None
-        flop_per_meme = FLOP_PER_MEME[args.config] if not args.tiny else plan.gemm_flops / args.batch
-        # FLOPs actually executed: the GEMM work of the text rows that were packed away is not counted
-        flop_exec_per_meme = flop_per_meme - plan.gemm_flops_dyn * (1.0 - dyn_scale) / args.batch
+        roofline = gemm_roofline(plan, args, value, world, live_rows / max_rows) if args.full else None
         out = {
             "metric": ("memes/sec (fine-tune step) ViT-B/16+BERT-base bs=32, 1/2/4/8 MI355X" if args.config == 3 else
                        "memes/sec (fine-tune step) CLIP ViT-L/14@336 + BERT-large seq=256 (BASELINE configs[4])"),
@@ -482,25 +509,12 @@ def main():
                                     "that never received a gradient are the identity under Adam and are skipped: bit-identical)",
                        "text_rows": (f"padding-free: {live_rows} of {max_rows} token rows live on rank 0 (attention_mask != 0), "
                                      "padded positions never computed") if plan.packed else f"dense: all {max_rows} rows computed"},
-            "roofline": {"bound": "mfma", "kernel": f"gemm_kernel{dom[4:]} (grouped {args.dtype} MFMA GEMM)",
-                         "achieved": round(achieved, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
-                         "traffic_source": (f"{traffic_src}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command "
-                                            "(FETCH x2, KiB -> bytes; tools/collect_profiles.sh), per launch of this kernel; "
-                                            "PMC counters cannot be read from inside the process") if traffic is not None else None,
-                         "method": "HIP events around every launch of the kernel on its launch stream, in an eager one-stream "
-                                   "replay of the step's prepared launches right after the timed region (3 replays averaged)",
-                         "launches_per_step": d["launches"], "avg_launch_us": round(d["total_ms"] / d["launches"] * 1e3, 2),
-                         "flops_per_launch": round(d["flops"] / d["launches"]),
-                         "all_gemm_kernels": {k: {"ms_per_step": round(v["total_ms"], 3),
-                                                  "tflops": round(v["flops"] / (v["total_ms"] * 1e-3) / 1e12, 1)}
-                                              for k, v in per_tag.items()},
-                         "step_mfma_frac": round(flop_exec_per_meme * value / world / (MFMA_PEAK_TFLOPS * 1e12), 4)},
+            **({"roofline": roofline} if roofline is not None else {}),
             # the tolerance every storage type is held to on THIS configuration (config 3, batch 32) by the GPU suite
             "parity": {"fp16": {"tol_logits": 1e-3, "test": "tests/test_round2_gpu.py::test_config3_batch32_matches_the_fixture[fp16]"},
                        "bf16": {"tol_logits": 8e-3, "test": "tests/test_round2_gpu.py::test_config3_batch32_matches_the_fixture[bf16]"}},
         }
-        if world == 1 and not args.force_ddp and not args.no_extras and not args.tiny and args.config == 3:
+        if args.full and world == 1 and not args.force_ddp and not args.no_extras and not args.tiny and args.config == 3:
             # secondary lines, same K / W, same batch: the other 16-bit storage type (fp16 meets north_star's 1e-3 on the
             # logits, see "parity"), SURVEY 8d's all-ones masks, the reference's dense text rows; fp16 WITHOUT overflow protection
             # (round 2's headline mode), the Trainer / Kevin clip at 1.0 (needs the global norm: no optimizer-in-backward), the
@@ -523,7 +537,7 @@ def main():
             c2 = bench_config2(args)
             out["value_config2"], out["ms_per_step_config2"], out["unit_config2"] = c2["value"], c2["ms_per_step"], c2["unit"]
             out["roofline_config2"] = dict(c2["roofline"], workload=c2["config"]["workload"])
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if args.config == 5:      # 1.6 TFLOP per meme: a batch of 32 would take the host cores an hour
                 out["cpu_baseline"] = cpu_baseline(1, args.seq, args.tiny, warm=1, timed=2, config=5)
             else:

@@ -9,7 +9,7 @@ TAG=${1:-prof}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="--no-extras --no-cpu-baseline"
+B="--full --no-extras --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats/run -- python bench.py --steps 5 --warmup 2 $B > $OUT/stats.log 2>&1
 echo "stats done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_seq/run -- python bench.py --steps 5 --warmup 2 --no-graph --no-overlap-wgrad --no-overlap-opt $B > $OUT/stats_seq.log 2>&1
@@ -20,5 +20,5 @@ rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write/run 
 echo "write done"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d $OUT/sq/run -- python bench.py --steps 2 --warmup 1 --no-graph --no-overlap-wgrad --no-overlap-opt $B > $OUT/sq.log 2>&1
 echo "sq done"
-python bench.py > $OUT/bench_default.log 2>&1
+python bench.py --full > $OUT/bench_default.log 2>&1
 tail -1 $OUT/bench_default.log | cut -c1-300

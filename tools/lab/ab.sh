@@ -1,10 +1,10 @@
 #!/bin/bash
 # One parameterised A/B script (replaces the exp_*.sh family; their commands are recorded in tools/lab/RESULTS.md).
 #   tools/lab/ab.sh <tag> <reps> [bench.py args ...] -- NAME=ENV[,ENV...] [-- NAME=ENV...] ...
-# Alternates `python bench.py <args>` runs under the given environments on ONE box, <reps> times, and prints ms/step, value and the
-# sequential-replay GEMM times of each.  NAME `baseline` runs the same command inside the same-box baseline worktree instead
+# Alternates `python bench.py <args>` runs under the given environments on ONE box, <reps> times, and prints ms/step, value and (with
+# --full) the sequential-replay GEMM times of each.  NAME `baseline` runs the same command inside the same-box baseline worktree instead
 #   (git worktree add -f .ab_baseline <commit> && make -C .ab_baseline/multimodal_propaganda_meme_classification_amd/csrc -j8).
-# Example:  tools/lab/ab.sh r4x 3 --no-extras --no-cpu-baseline --steps 60 --warmup 10 -- baseline= -- head= -- nograph=MEMEHIP_X=1
+# Example:  tools/lab/ab.sh r4x 3 --full --no-extras --no-cpu-baseline --steps 60 --warmup 10 -- baseline= -- head= -- nograph=MEMEHIP_X=1
 TAG=$1; REPS=$2; shift 2
 ARGS=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do ARGS+=("$1"); shift; done
 VARIANTS=(); while [ $# -gt 0 ]; do [ "$1" = "--" ] || VARIANTS+=("$1"); shift; done
