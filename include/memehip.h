@@ -316,7 +316,9 @@ int mh_vit_assemble_bwd(const void* dx /*bf16 [B][Np+1][D]*/, void* dproj /*bf16
  * mh_head_bwd consumes dlogits [B][C] (f32) and produces all head grads (f32, overwritten) and
  *   d_text_hidden / d_image_hidden rows (bf16, written into the [T][D] gradient buffers at the
  *   pooled token rows; the other rows must be zero-filled by the caller).
- * mh_ce_fwd_bwd: loss (scalar f32), dlogits = (softmax - onehot)/B, n_correct (argmax == label).
+ * mh_ce_fwd_bwd: loss (scalar f32), dlogits = (softmax - onehot)/B, n_correct (argmax == label, first maximum wins).
+ *   A label outside [0, C) -- nn.CrossEntropyLoss's ignore_index -100 included -- is read as class 0 (it is NOT ignored:
+ *   the loss, dlogits and n_correct are those of label 0, and the mean stays over all B rows).
  * ------------------------------------------------------------------------------------------ */
 typedef struct MhHeadParams {
     const float *Wt, *bt;   /* bert_fc   [P][Dt], [P] */
@@ -390,6 +392,8 @@ int mh_focal_fwd_bwd(const float* logits, int ld, const float* targets /*f32 [B]
  *   launch: z = A B^T + bias is kept in bn_z (for the backward), training mode normalises with the batch statistics
  *   (biased variance), saves mean / rstd and updates the running statistics (unbiased variance, momentum) exactly as
  *   mh_bn1d_fwd does; eval mode uses the running statistics.
+ *   B = 1 (M = 1) in training mode is accepted, where nn.BatchNorm1d raises: the batch variance is 0, so the output is
+ *   beta (ReLU'd), and the running variance takes the biased variance 0 in place of the undefined unbiased one.
  * ------------------------------------------------------------------------------------------ */
 #define MH_F32_ACCUM 1
 #define MH_F32_TANH 2
@@ -406,7 +410,8 @@ int mh_gemm_f32(const MhGemmF32* p /*host*/, int a_kmajor, int b_kmajor, mh_stre
 /* out[d] = scale * sum_r x[r][d] (bias gradients; fixed summation order) */
 int mh_colsum_f32(const float* x, int ld, float* out, int rows, int D, float scale, mh_stream_t stream);
 /* Sequence poolings over the last hidden state h f32 [B][S][D]:
- *   max   : out[b][d] = max_s h ; arg = the first maximising s ; bwd writes dh (all of it) from dout and arg
+ *   max   : out[b][d] = max_s h ; arg = the first maximising s (a NaN propagates as in torch.max: the first NaN along s
+ *           wins) ; bwd writes dh (all of it) from dout and arg
  *   mean  : out = sum_s h m / clamp(sum_s m, 1e-9) with the int64 attention mask m [B][S]
  *   attn  : u = tanh(h W1^T + b1) comes from mh_gemm_f32(MH_F32_TANH); scores = u . w2 + b2 + (1 - m) * -1e9;
  *           p = softmax_s (saved [B][S]); out = sum_s p h.  bwd: du [B][S][A] (feed the two GEMMs for dW1 / dh),

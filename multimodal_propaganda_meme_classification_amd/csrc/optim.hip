@@ -80,9 +80,11 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
         f32x4 mv = *(const f32x4*)(m + 4 * i);
         f32x4 vv = *(const f32x4*)(v + 4 * i);
         if (overflow) {
-            // guarded update (optimizer-in-backward: the slice is updated before the global norm can exist): elements whose
-            // gradient is not finite keep their parameters and moments, and the step is reported through *overflow so that
-            // mh_adam_skip_account counts it and backs the loss scale off
+            // guarded update (optimizer-in-backward: the slice is updated before the global norm can exist): a 4-element vector
+            // with any non-finite gradient keeps the parameters, moments and shadow words of ALL FOUR elements (the unit of the
+            // test is the vector, not the element), and the step is reported through *overflow so that mh_adam_skip_account
+            // counts it and backs the loss scale off.  (The test is on the sum of the four |g|: a finite vector whose sum passes 3e38
+            // counts as not finite too.)
             const float a = fabsf(gv[0]) + fabsf(gv[1]) + fabsf(gv[2]) + fabsf(gv[3]);
             if (!(a <= 3.0e38f)) {
                 *overflow = ordinal;
@@ -203,7 +205,7 @@ __global__ __launch_bounds__(256) void adam_rows_kernel(float* __restrict__ p, f
         const size_t base = (size_t)row * D;
         for (int c = lane * 4; c < D; c += 256) {
             const f32x4 gv = *(const f32x4*)(g + base + c);
-            if (overflow) {
+            if (overflow) {      // (as in adam_kernel: the whole 4-element vector keeps its parameters and moments)
                 const float a = fabsf(gv[0]) + fabsf(gv[1]) + fabsf(gv[2]) + fabsf(gv[3]);
                 if (!(a <= 3.0e38f)) {
                     *overflow = ordinal;

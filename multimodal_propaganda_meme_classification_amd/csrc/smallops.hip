@@ -240,7 +240,8 @@ __global__ __launch_bounds__(256) void colsum_f32_kernel(const float* __restrict
 // ---------------------------------------------------------------------------------------------------
 // sequence poolings over h [B][S][D] f32 (LLMWithClassificationHead, Multimodal_example_task2C.py:362-392)
 // ---------------------------------------------------------------------------------------------------
-// max over s (first maximum wins, as torch.max returns for ties on CPU); arg kept for the backward
+// max over s (first maximum wins, as torch.max returns for ties on CPU); arg kept for the backward.  NaN propagates as in
+// torch.max: the first NaN along s is the result and its position the arg
 __global__ __launch_bounds__(256) void pool_max_fwd_kernel(const float* __restrict__ h, float* __restrict__ out,
                                                            int32_t* __restrict__ arg, int B, int S, int D) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(256) void pool_max_fwd_kernel(const float* __restri
     int am = 0;
     for (int s = 1; s < S; ++s) {
         const float v = p[(size_t)s * D];
-        if (v > m) { m = v; am = s; }
+        if (v > m || (v != v && m == m)) { m = v; am = s; }
     }
     out[idx] = m;
     arg[idx] = am;
