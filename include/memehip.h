@@ -683,13 +683,16 @@ int mh_sum_shards_16(const void* in /*[W][shard]*/, void* out /*[shard]*/, int W
  *   k,v: 16-bit, key j of (b, h) at k + b*ld_b + j*ld_t + h*64 (v likewise)
  *   t_dev == NULL: T keys (cross-attention over a fixed memory, e.g. 577 image tokens).
  *   t_dev != NULL: self-attention over a cache of capacity T: this step's k of (b, h) at kv_new + b*ld_new + h*64 and its
- *                  v H*64 elements further are stored into slot t = t_dev[0] first, and keys 0..t attend.
+ *                  v H*64 elements further are stored into slot t = t_dev[0] first, and keys 0..t attend.  t >= T (the
+ *                  cache is full): nothing is stored and the cached keys 0..T-1 attend, without this step's k / v.
  *   out: 16-bit, (b, h) at out + b*ldo + h*64.
  *   nsplit > 1: the keys are cut into nsplit chunks (rows * heads too few to fill the chip); partials (m, l, acc) go to
  *               workspace f32 [B*H][nsplit][66] and a second launch combines them in split order.  nsplit <= 64.
  *   ldq, ld_t, ld_b, ld_new multiples of 8; bases 16-byte aligned.
  * mh_decode_embed: y[b] = LayerNorm(word[ids[b]] + pos[t_dev[0]]) (f32 tables [V][D], [P][D]), 16-bit out [B][D], D <= 2048.
- * mh_greedy_step: one launch per step over f32 logits [B][ldl] (columns >= V are never chosen; ties go to the lowest index).
+ *   An id outside [0, V) reads row 0 (id < 0) or V-1 (id >= V); t outside [0, P) reads row 0 or P-1 likewise.
+ * mh_greedy_step: one launch per step over f32 logits [B][ldl] (columns >= V are never chosen; ties go to the lowest index;
+ *   NaN ranks above every number, so a row holding a NaN picks its first NaN, and an all -inf row picks 0: torch.argmax).
  *   state int32[4] = {t, arrival counter (0), rows finished, output length once all rows finished (0 before)}.
  *   Column c = t + 1 of out_ids int64 [B][ld_out] receives the prompt token (c < prompt_len, read from out_ids itself), pad_id
  *   (row finished before), or the argmax, which marks the row finished when it is eos_id.  next_ids[b] = that token; t += 1.

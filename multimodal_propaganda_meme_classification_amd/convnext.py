@@ -17,9 +17,10 @@ Launch plan, activations NHWC 16-bit = row matrices ``[B*H*W][C]``:
   permutation, 1x the activation bytes) + GEMM (+bias);
 * ``AdaptiveAvgPool2d(1)``: ``mh_avgpool_fwd`` (f32).
 
-Stage 1 has 96 channels and the GEMM contracts in tiles of 64: its first Linear runs with K = 128 over the ``[M][96]`` LayerNorm
-output (row pitch 96) against a weight whose columns 96..127 are zero -- the extra 32 columns of a row are the next row's first
-32 values, multiplied by zeros; the buffer carries 64 zero elements behind the last row.
+Stage 1 has 96 channels and the GEMM contracts in tiles of 64: its first Linear runs with K = 128 against a weight whose columns
+96..127 are zero, over the LayerNorm output re-pitched to 128 columns whose last 32 are zero (``mh_im2col_nhwc`` with a 1x1
+window).  Contracting the pitch-96 rows directly would multiply the next row's first 32 values by those zero columns: a NaN or
+Inf in the first pixel of image b+1 then made image b's last pixel, and so its pooled features, NaN (0 x NaN = NaN).
 """
 from __future__ import annotations
 
@@ -141,8 +142,9 @@ class ConvNeXtTiny(nn.Module):
         if not image.is_cuda:
             raise _lib.MemehipError("ConvNeXtTiny runs on the HIP device only (no CPU fallback): move the batch with .to(device)")
         B, Cc, H, W = image.shape
-        if Cc != 3 or H % 32 or W % 32:
-            raise ValueError("ConvNeXtTiny expects [B, 3, H, W] images with H and W multiples of 32")
+        step = 4 << (len(self.dims) - 1)          # the stem's 4 and a factor 2 per downsampling layer: 32 for convnext_tiny
+        if Cc != 3 or H % step or W % step:
+            raise ValueError(f"ConvNeXtTiny expects [B, 3, H, W] images with H and W multiples of {step}")
         lib = self._lib()
         T16 = torch.float16 if self.compute_dtype == "fp16" else torch.bfloat16
         pk = self._packed(T16)
@@ -162,11 +164,11 @@ class ConvNeXtTiny(nn.Module):
                 if kp == d:
                     n, _, _ = ops.layernorm_fwd(t, g, be, 1e-6)
                     hid = ops.linear_fwd(n, w1, bias=b1, gelu=True)
-                else:      # 96 channels: contract over 128 columns of the pitch-96 rows against zero-padded weight columns
-                    flat = torch.zeros(M * d + 64, dtype=T16, device=dev)
-                    ops.layernorm_fwd(t, g, be, 1e-6, y=flat[:M * d].view(M, d))
-                    hid = torch.empty((M, 4 * d), dtype=T16, device=dev)
-                    ops.gemm_grouped([ops.Gemm(flat, w1, hid, M, 4 * d, kp, d, kp, 4 * d, bias=b1, gelu=True)], False, False)
+                else:      # 96 channels: LayerNorm rows re-pitched to 128 with zero columns (1x1 im2col), contracted over K = 128
+                    n, _, _ = ops.layernorm_fwd(t, g, be, 1e-6)
+                    padded = torch.empty((M, kp), dtype=T16, device=dev)
+                    check(lib.mh_im2col_nhwc(n.data_ptr(), padded.data_ptr(), B, h, w, d, 1, 1, 1, 0, kp, _stream()), "mh_im2col_nhwc")
+                    hid = ops.linear_fwd(padded, w1, bias=b1, gelu=True)
                 x = ops.linear_fwd(hid, w2, bias=b2, residual=x)
             if si + 1 < len(self.dims):
                 g, be, wk, bk = pk[("down", si)]

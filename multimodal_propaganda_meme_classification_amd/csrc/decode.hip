@@ -26,7 +26,7 @@ struct DecodeArgs {
     h16* k;                // k of (b, h, j) at k + b*ld_b + j*ld_t + h*64 (v likewise)
     h16* v;
     const h16* kv_new;     // self form: this step's k of (b, h) at kv_new + b*ld_new + h*64, its v H*64 further
-    const int32_t* t_dev;  // self form: the slot of this step (keys 0..t attend); NULL: T keys
+    const int32_t* t_dev;  // self form: the slot of this step (keys 0..t attend; t >= T: no store, keys 0..T-1); NULL: T keys
     h16* out;              // out of (b, h) at out + b*ldo + h*64
     float* ws;             // nsplit > 1: [B*H][nsplit][DEC_WS]
     int64_t ld_b;
@@ -201,8 +201,13 @@ __global__ void __launch_bounds__(256) decode_embed_kernel(const int64_t* ids, c
     }
 }
 
-// (value, index) order of the argmax: larger value first, then the lower index (torch.argmax's first maximum)
-MH_DEV bool arg_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+// (value, index) order of the argmax: larger value first, then the lower index (torch.argmax's first maximum); NaN ranks above
+// every number, as in torch.argmax (a row holding a NaN yields its first NaN)
+MH_DEV bool arg_better(float v, int i, float bv, int bi) {
+    const bool vn = v != v, bn = bv != bv;
+    if (vn || bn) return vn && (!bn || i < bi);
+    return v > bv || (v == bv && i < bi);
+}
 
 // state words: [0] t (the position this step consumed), [1] arrival counter (0 between launches), [2] rows finished,
 // [3] output length once every row has finished (0 before)

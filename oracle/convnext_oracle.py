@@ -72,34 +72,42 @@ def _ln2d(x, w, b, eps=1e-6):      # LayerNorm2d: over the channels of NCHW
     return F.layer_norm(x.permute(0, 2, 3, 1), (x.shape[1],), w, b, eps).permute(0, 3, 1, 2)
 
 
-def convnext_features(p: Params, image: torch.Tensor, depths=DEPTHS, dims=DIMS) -> torch.Tensor:
-    """``model.features(image)``: f32 [B, dims[-1], H/32, W/32]."""
-    x = F.conv2d(image, p["features.0.0.weight"], p["features.0.0.bias"], stride=4)
-    x = _ln2d(x, p["features.0.1.weight"], p["features.0.1.bias"])
+def convnext_features(p: Params, image: torch.Tensor, depths=DEPTHS, dims=DIMS, storage=None) -> torch.Tensor:
+    """``model.features(image)``: f32 [B, dims[-1], H/32, W/32].  ``storage`` = torch.float16 / torch.bfloat16 inserts the 16-bit
+    STORAGE rounding of the HIP tower (convnext.ConvNeXtTiny): the image and the stem / Linear / downsampling weights (layer scale
+    folded into the second Linear first, as _packed does), and every stored activation -- stem and LayerNorm outputs, the depthwise
+    output, the GELU hidden, each block output and each downsampling output.  Arithmetic between store points stays f32."""
+    q = (lambda t: t.to(storage).to(t.dtype)) if storage is not None else (lambda t: t)
+    x = F.conv2d(q(image), q(p["features.0.0.weight"]), p["features.0.0.bias"], stride=4)
+    x = q(_ln2d(q(x), p["features.0.1.weight"], p["features.0.1.bias"]))
     li = 1
     for si, (n, d) in enumerate(zip(depths, dims)):
         for bi in range(n):
-            q = f"features.{li}.{bi}."
-            t = F.conv2d(x, p[q + "block.0.weight"], p[q + "block.0.bias"], padding=3, groups=d)
+            k = f"features.{li}.{bi}."
+            t = q(F.conv2d(x, p[k + "block.0.weight"], p[k + "block.0.bias"], padding=3, groups=d))
             t = t.permute(0, 2, 3, 1)
-            t = F.layer_norm(t, (d,), p[q + "block.2.weight"], p[q + "block.2.bias"], 1e-6)
-            t = F.linear(t, p[q + "block.3.weight"], p[q + "block.3.bias"])
-            t = F.gelu(t)
-            t = F.linear(t, p[q + "block.5.weight"], p[q + "block.5.bias"])
-            t = t.permute(0, 3, 1, 2)
-            x = x + p[q + "layer_scale"] * t
+            t = q(F.layer_norm(t, (d,), p[k + "block.2.weight"], p[k + "block.2.bias"], 1e-6))
+            t = q(F.gelu(F.linear(t, q(p[k + "block.3.weight"]), p[k + "block.3.bias"])))
+            if storage is not None:
+                ls = p[k + "layer_scale"].reshape(d)
+                t = F.linear(t, q(ls[:, None] * p[k + "block.5.weight"]), ls * p[k + "block.5.bias"]).permute(0, 3, 1, 2)
+                x = q(x + t)
+            else:
+                t = F.linear(t, p[k + "block.5.weight"], p[k + "block.5.bias"])
+                t = t.permute(0, 3, 1, 2)
+                x = x + p[k + "layer_scale"] * t
         li += 1
         if si + 1 < len(dims):
-            q = f"features.{li}."
-            x = _ln2d(x, p[q + "0.weight"], p[q + "0.bias"])
-            x = F.conv2d(x, p[q + "1.weight"], p[q + "1.bias"], stride=2)
+            k = f"features.{li}."
+            x = q(_ln2d(x, p[k + "0.weight"], p[k + "0.bias"]))
+            x = q(F.conv2d(x, q(p[k + "1.weight"]), p[k + "1.bias"], stride=2))
             li += 1
     return x
 
 
-def convnext_pooled_features(p: Params, image: torch.Tensor, depths=DEPTHS, dims=DIMS) -> torch.Tensor:
+def convnext_pooled_features(p: Params, image: torch.Tensor, depths=DEPTHS, dims=DIMS, storage=None) -> torch.Tensor:
     """``avgpool(features(image)).flatten(1)``: what extract_feat.py:58,62 stores per image."""
-    return convnext_features(p, image, depths, dims).mean(dim=(2, 3))
+    return convnext_features(p, image, depths, dims, storage).mean(dim=(2, 3))
 
 
 def to_hf_state_dict(p: Params, depths=DEPTHS, dims=DIMS) -> Params:
