@@ -258,10 +258,13 @@ int mh_image_normalize_u8(const uint8_t* src, float* dst, int B, int H, int W, c
  *   fixed point -- horizontal pass into a uint8 image, then the vertical pass; the host supplies, per image and output
  *   pixel, the source window {first, count} and the 22-bit integer coefficients (data.pil_resample_coeffs: PIL's
  *   precompute_coeffs / normalize_coeffs_8bpc), so the output equals PIL's bit for bit.  Only the output window asked for
- *   (the centre crop) is computed; `flip` (uint8 [B] or NULL) mirrors the output (RandomHorizontalFlip).
+ *   (the centre crop) is computed; `flip` (uint8 [B] or NULL) mirrors the output (RandomHorizontalFlip).  `vfirst` (uint8 [B] or
+ *   NULL): images that take the vertical pass first, as Pillow's Image.resize does for a source with h > 100 w whose height shrinks
+ *   (data.pil_resize_vertical_first); the 8-bit intermediate image makes the two orders differ by one grey level.
  *     arena: the batch's images back to back, uint8 [h][w][3] each at src_off[b]; hw int32 [B][2];
- *     xbounds / ybounds int32 [B][OW|OH][2]; xcoef / ycoef int32 [B][OW|OH][KX|KY]; tmp uint8 [B][max_h][OW][3];
- *     out uint8 [B][OH][OW][3].
+ *     xbounds / ybounds int32 [B][OW|OH][2]; xcoef / ycoef int32 [B][OW|OH][KX|KY];
+ *     tmp uint8 [B][max(max_h * OW, OH * max_w)][3]: per image [h][OW] (horizontal first) or [OH][w] (vertical first); max_h >= every
+ *     h, max_w >= the w of every vertical-first image (not read when vfirst is NULL); out uint8 [B][OH][OW][3].
  * mh_image_jitter_rotate_u8: ColorJitter (brightness / contrast / saturation / hue factors, per-image op order packed 2 bits
  *   per step: 0 brightness, 1 contrast, 2 saturation, 3 hue) with PIL's arithmetic on uint8 -- ImageEnhance = ImagingBlend in
  *   float32 (product and sum rounded separately), the hue op = Pillow's 8-bit RGB -> HSV -> RGB round trip with the H band shifted
@@ -273,7 +276,8 @@ int mh_image_normalize_u8(const uint8_t* src, float* dst, int B, int H, int W, c
  *   factors are drawn on the host. */
 int mh_image_resample_u8(const uint8_t* arena, const int64_t* src_off, const int32_t* hw, const int32_t* xbounds,
                          const int32_t* xcoef, int KX, const int32_t* ybounds, const int32_t* ycoef, int KY, const uint8_t* flip,
-                         uint8_t* tmp, uint8_t* out, int B, int max_h, int OH, int OW, mh_stream_t stream);
+                         const uint8_t* vfirst, uint8_t* tmp, uint8_t* out, int B, int max_h, int max_w, int OH, int OW,
+                         mh_stream_t stream);
 int mh_image_luma_sum_u8(const uint8_t* img, unsigned long long* sums, int B, int HW, mh_stream_t stream);
 int mh_image_jitter_rotate_u8(const uint8_t* in, uint8_t* scratch, uint8_t* out, const void* params, unsigned long long* lsum,
                               int B, int H, int W, mh_stream_t stream);

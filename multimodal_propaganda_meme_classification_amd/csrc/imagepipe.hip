@@ -4,7 +4,8 @@
 //   Kevin      (Multimodal_example_task2C.py:222-235): Resize((224,224)) -> RandomHorizontalFlip -> ColorJitter(.1,.1,.1,.1)
 //                                                      -> RandomRotation(15) -> ToTensor -> Normalize
 // Resize is PIL's antialiased bilinear resample restated in its own 8-bit fixed point (22 fractional bits, horizontal pass
-// into a uint8 image, then the vertical pass): the host computes the per-output-pixel windows and integer coefficients with
+// into a uint8 image, then the vertical pass -- the other way round for the images Image.resize itself takes vertical-first,
+// h > 100 w with a shrinking height, which the host marks per image): the host computes the per-output-pixel windows and integer coefficients with
 // PIL's formulas (data.pil_resample_coeffs), the kernels do the integer sums, so the result equals PIL's bit for bit; the
 // centre crop only restricts which output pixels are computed.  ToTensor + Normalize: mh_image_normalize_u8 (embed.hip).
 #include "common.h"
@@ -15,53 +16,65 @@ constexpr int PRECISION_BITS = 22;      // PIL ImagingResample: 32 - 8 - 2
 
 MH_DEV uint8_t clip8(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
-// horizontal pass: tmp[b][y][xo][c] = clip8((2^21 + sum_k src[b][y][x0 + k][c] * coef[b][xo][k]) >> 22), y < h_b
-__global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t* __restrict__ arena, const int64_t* __restrict__ src_off,
-                                                         const int32_t* __restrict__ hw, const int32_t* __restrict__ bounds,
-                                                         const int32_t* __restrict__ coef, int K, uint8_t* __restrict__ tmp,
-                                                         int max_h, int OW) {
-    const int b = blockIdx.y;
-    const int h = hw[2 * b], w = hw[2 * b + 1];
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= h * OW) return;
-    const int y = idx / OW, xo = idx % OW;
-    const uint8_t* row = arena + src_off[b] + (size_t)y * w * 3;
-    const int x0 = bounds[((size_t)b * OW + xo) * 2], n = bounds[((size_t)b * OW + xo) * 2 + 1];
-    const int32_t* k = coef + ((size_t)b * OW + xo) * K;
+// one 22-bit fixed-point window sum over n pixels `stride` bytes apart, rounded and clipped as ImagingResample does
+MH_DEV void window_sum(const uint8_t* p, size_t stride, const int32_t* k, int n, uint8_t* o) {
     int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
-    for (int i = 0; i < n; ++i) {
-        const uint8_t* p = row + (size_t)(x0 + i) * 3;
+    for (int i = 0; i < n; ++i, p += stride) {
         s0 += p[0] * k[i];
         s1 += p[1] * k[i];
         s2 += p[2] * k[i];
     }
-    uint8_t* o = tmp + (((size_t)b * max_h + y) * OW + xo) * 3;
     o[0] = clip8(s0 >> PRECISION_BITS);
     o[1] = clip8(s1 >> PRECISION_BITS);
     o[2] = clip8(s2 >> PRECISION_BITS);
 }
-// vertical pass (+ optional horizontal flip of the OUTPUT): out[b][yo][xo][c]
-__global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t* __restrict__ tmp, const int32_t* __restrict__ bounds,
-                                                         const int32_t* __restrict__ coef, int K, const uint8_t* __restrict__ flip,
-                                                         uint8_t* __restrict__ out, int max_h, int OH, int OW) {
+// first pass.  Horizontal (the usual order): tmp[b][y][xo][c] = clip8((2^21 + sum_k src[b][y][x0 + k][c] * xcoef[b][xo][k]) >> 22),
+// y < h_b.  An image with vfirst[b] set takes the vertical pass first, as Image.resize does for h > 100 w when the height shrinks:
+// tmp[b][yo][x][c] = clip8((2^21 + sum_k src[b][y0 + k][x][c] * ycoef[b][yo][k]) >> 22), x < w_b.  Each image owns tstride bytes of tmp.
+__global__ __launch_bounds__(256) void resample_pass1_kernel(const uint8_t* __restrict__ arena, const int64_t* __restrict__ src_off,
+                                                             const int32_t* __restrict__ hw, const int32_t* __restrict__ xbounds,
+                                                             const int32_t* __restrict__ xcoef, int KX, const int32_t* __restrict__ ybounds,
+                                                             const int32_t* __restrict__ ycoef, int KY, const uint8_t* __restrict__ vfirst,
+                                                             uint8_t* __restrict__ tmp, size_t tstride, int OH, int OW) {
+    const int b = blockIdx.y;
+    const int h = hw[2 * b], w = hw[2 * b + 1];
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const uint8_t* src = arena + src_off[b];
+    if (vfirst && vfirst[b]) {
+        if (idx >= OH * w) return;
+        const int yo = idx / w, x = idx % w;
+        const int y0 = ybounds[((size_t)b * OH + yo) * 2], n = ybounds[((size_t)b * OH + yo) * 2 + 1];
+        window_sum(src + ((size_t)y0 * w + x) * 3, (size_t)w * 3, ycoef + ((size_t)b * OH + yo) * KY, n,
+                   tmp + (size_t)b * tstride + ((size_t)yo * w + x) * 3);
+        return;
+    }
+    if (idx >= h * OW) return;
+    const int y = idx / OW, xo = idx % OW;
+    const int x0 = xbounds[((size_t)b * OW + xo) * 2], n = xbounds[((size_t)b * OW + xo) * 2 + 1];
+    window_sum(src + ((size_t)y * w + x0) * 3, 3, xcoef + ((size_t)b * OW + xo) * KX, n,
+               tmp + (size_t)b * tstride + ((size_t)y * OW + xo) * 3);
+}
+// second pass, the other axis (+ optional horizontal flip of the OUTPUT): out[b][yo][xo][c]
+__global__ __launch_bounds__(256) void resample_pass2_kernel(const uint8_t* __restrict__ tmp, const int32_t* __restrict__ hw,
+                                                             const int32_t* __restrict__ xbounds, const int32_t* __restrict__ xcoef, int KX,
+                                                             const int32_t* __restrict__ ybounds, const int32_t* __restrict__ ycoef, int KY,
+                                                             const uint8_t* __restrict__ vfirst, const uint8_t* __restrict__ flip,
+                                                             uint8_t* __restrict__ out, size_t tstride, int OH, int OW) {
     const int b = blockIdx.y;
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= OH * OW) return;
     const int yo = idx / OW, xo = idx % OW;
-    const int y0 = bounds[((size_t)b * OH + yo) * 2], n = bounds[((size_t)b * OH + yo) * 2 + 1];
-    const int32_t* k = coef + ((size_t)b * OH + yo) * K;
-    int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
-    for (int i = 0; i < n; ++i) {
-        const uint8_t* p = tmp + (((size_t)b * max_h + y0 + i) * OW + xo) * 3;
-        s0 += p[0] * k[i];
-        s1 += p[1] * k[i];
-        s2 += p[2] * k[i];
-    }
     const int xd = (flip && flip[b]) ? OW - 1 - xo : xo;
     uint8_t* o = out + (((size_t)b * OH + yo) * OW + xd) * 3;
-    o[0] = clip8(s0 >> PRECISION_BITS);
-    o[1] = clip8(s1 >> PRECISION_BITS);
-    o[2] = clip8(s2 >> PRECISION_BITS);
+    const uint8_t* t = tmp + (size_t)b * tstride;
+    if (vfirst && vfirst[b]) {
+        const int w = hw[2 * b + 1];
+        const int x0 = xbounds[((size_t)b * OW + xo) * 2], n = xbounds[((size_t)b * OW + xo) * 2 + 1];
+        window_sum(t + ((size_t)yo * w + x0) * 3, 3, xcoef + ((size_t)b * OW + xo) * KX, n, o);
+        return;
+    }
+    const int y0 = ybounds[((size_t)b * OH + yo) * 2], n = ybounds[((size_t)b * OH + yo) * 2 + 1];
+    window_sum(t + ((size_t)y0 * OW + xo) * 3, (size_t)OW * 3, ycoef + ((size_t)b * OH + yo) * KY, n, o);
 }
 
 // PIL "L" conversion of an RGB pixel (ImagingConvert rgb2l): (R*19595 + G*38470 + B*7471 + 0x8000) >> 16
@@ -108,8 +121,9 @@ struct JitterParams {
 };
 
 // adjust_hue on one pixel exactly as torchvision does it on a PIL image: RGB -> HSV (Pillow Convert.c rgb2hsv_row: 8-bit H, S, V),
-// H += shift (mod 256), HSV -> RGB (Convert.c hsv2rgb).  float where the C code has float, double where it has double; checked
-// against PIL over all 2^24 colours (tests/test_host_cpu.py pins the same arithmetic written in numpy, the GPU test the kernel).
+// H += shift (mod 256), HSV -> RGB (Convert.c hsv2rgb).  float where the C code has float, double where it has double.
+// tests/test_image_pipeline_paths_gpu.py runs this kernel over all 2^24 colours against PIL for eight shifts; tests/test_host_cpu.py pins
+// the same arithmetic written in numpy (data.hue_shift_u8_reference) on a 1024 x 1024 image.
 MH_DEV void apply_hue(int& r, int& g, int& b, int shift) {
     const int maxc = max(r, max(g, b)), minc = min(r, min(g, b));
     int uh = 0, us = 0;
@@ -199,15 +213,17 @@ __global__ __launch_bounds__(256) void jitter_rotate_kernel(const uint8_t* __res
 
 extern "C" int mh_image_resample_u8(const uint8_t* arena, const int64_t* src_off, const int32_t* hw, const int32_t* xbounds,
                                     const int32_t* xcoef, int KX, const int32_t* ybounds, const int32_t* ycoef, int KY,
-                                    const uint8_t* flip, uint8_t* tmp, uint8_t* out, int B, int max_h, int OH, int OW,
-                                    mh_stream_t stream) {
+                                    const uint8_t* flip, const uint8_t* vfirst, uint8_t* tmp, uint8_t* out, int B, int max_h, int max_w,
+                                    int OH, int OW, mh_stream_t stream) {
     if (!arena || !src_off || !hw || !xbounds || !xcoef || !ybounds || !ycoef || !tmp || !out) return MH_EINVAL;
-    if (B < 1 || max_h < 1 || OH < 1 || OW < 1 || KX < 1 || KY < 1) return MH_ESHAPE;
+    if (B < 1 || max_h < 1 || OH < 1 || OW < 1 || KX < 1 || KY < 1 || max_w < (vfirst ? 1 : 0)) return MH_ESHAPE;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(resample_h_kernel, dim3((max_h * OW + 255) / 256, B), dim3(256), 0, s, arena, src_off, hw, xbounds, xcoef, KX, tmp,
-                       max_h, OW);
-    hipLaunchKernelGGL(resample_v_kernel, dim3((OH * OW + 255) / 256, B), dim3(256), 0, s, tmp, ybounds, ycoef, KY, flip, out, max_h, OH,
-                       OW);
+    // per image: [max_h][OW] pixels (horizontal pass first) or [OH][max_w] (vertical pass first), whichever is larger
+    const size_t px1 = (size_t)max_h * OW, px1v = vfirst ? (size_t)OH * max_w : 0, px = px1 > px1v ? px1 : px1v;
+    hipLaunchKernelGGL(resample_pass1_kernel, dim3((unsigned)((px + 255) / 256), B), dim3(256), 0, s, arena, src_off, hw, xbounds, xcoef, KX,
+                       ybounds, ycoef, KY, vfirst, tmp, px * 3, OH, OW);
+    hipLaunchKernelGGL(resample_pass2_kernel, dim3((OH * OW + 255) / 256, B), dim3(256), 0, s, tmp, hw, xbounds, xcoef, KX, ybounds, ycoef,
+                       KY, vfirst, flip, out, px * 3, OH, OW);
     return mh_launch_status();
 }
 

@@ -208,20 +208,33 @@ def pil_resample_coeffs(in_size: int, out_size: int, first: int = 0, count: Opti
     return bounds, coefs
 
 
-def resample_u8_reference(img: np.ndarray, bx, cx, by, cy) -> np.ndarray:
-    """numpy statement of what mh_image_resample_u8 computes (horizontal pass into uint8, then vertical): tests only."""
-    h = img.shape[0]
-    tmp = np.zeros((h, bx.shape[0], 3), dtype=np.uint8)
-    for xo in range(bx.shape[0]):
-        x0, n = bx[xo]
-        acc = (1 << (_PRECISION_BITS - 1)) + (img[:, x0:x0 + n, :].astype(np.int64) * cx[xo, :n][None, :, None]).sum(1)
-        tmp[:, xo] = np.clip(acc >> _PRECISION_BITS, 0, 255)
-    out = np.zeros((by.shape[0], bx.shape[0], 3), dtype=np.uint8)
-    for yo in range(by.shape[0]):
-        y0, n = by[yo]
-        acc = (1 << (_PRECISION_BITS - 1)) + (tmp[y0:y0 + n].astype(np.int64) * cy[yo, :n][:, None, None]).sum(0)
-        out[yo] = np.clip(acc >> _PRECISION_BITS, 0, 255)
-    return out
+def pil_resize_vertical_first(h: int, w: int, out_h: int) -> bool:
+    """Pillow's Image.resize (PIL/Image.py, 12.2.0) runs the vertical pass first, as a resize of its own, for a source more than
+    100 times as tall as wide whose height shrinks; every other source goes through ImagingResample's horizontal-then-vertical
+    order.  The intermediate image is uint8 either way, so the two orders differ by one grey level on many pixels."""
+    return h > w * 100 and out_h < h
+
+
+def resample_u8_reference(img: np.ndarray, bx, cx, by, cy, vertical_first: bool = False) -> np.ndarray:
+    """numpy statement of what mh_image_resample_u8 computes (horizontal pass into uint8, then vertical; the other way round
+    with ``vertical_first``): tests only."""
+    def horizontal(a):
+        out = np.zeros((a.shape[0], bx.shape[0], 3), dtype=np.uint8)
+        for xo in range(bx.shape[0]):
+            x0, n = bx[xo]
+            acc = (1 << (_PRECISION_BITS - 1)) + (a[:, x0:x0 + n, :].astype(np.int64) * cx[xo, :n][None, :, None]).sum(1)
+            out[:, xo] = np.clip(acc >> _PRECISION_BITS, 0, 255)
+        return out
+
+    def vertical(a):
+        out = np.zeros((by.shape[0], a.shape[1], 3), dtype=np.uint8)
+        for yo in range(by.shape[0]):
+            y0, n = by[yo]
+            acc = (1 << (_PRECISION_BITS - 1)) + (a[y0:y0 + n].astype(np.int64) * cy[yo, :n][:, None, None]).sum(0)
+            out[yo] = np.clip(acc >> _PRECISION_BITS, 0, 255)
+        return out
+
+    return horizontal(vertical(img)) if vertical_first else vertical(horizontal(img))
 
 
 def pil_rotate_fixed_coeffs(angle_deg: float, w: int, h: int):
@@ -280,7 +293,8 @@ class DeviceImagePipeline:
     returns the f32 [B, 3, S, S] normalised batch:
 
     * ``mode="center_crop"``: Resize(resize) -> CenterCrop(image_size) -> ToTensor -> Normalize (organizers,
-      Multimodal_example_task2C.txt:37-41), bit-identical to the PIL path (``load_image``);
+      Multimodal_example_task2C.txt:37-41), bit-identical to the PIL path (``load_image``), the sources Pillow resizes
+      vertical-first included (``pil_resize_vertical_first``);
     * ``mode="stretch"``: Resize((S, S)) (Kevin, Multimodal_example_task2C.py:224); ``augment=True`` adds
       RandomHorizontalFlip, ColorJitter(0.1, 0.1, 0.1, 0.1) and RandomRotation(15) with PIL's uint8 arithmetic; the random
       factors come from ``generator`` (torchvision's own RNG stream cannot be reproduced)."""
@@ -303,12 +317,13 @@ class DeviceImagePipeline:
         return buf
 
     def _plan(self, h, w):
+        """(x bounds, x coefs), (y bounds, y coefs), vertical pass first"""
         S = self.S
         if self.mode == "stretch":
-            return pil_resample_coeffs(w, S), pil_resample_coeffs(h, S)
+            return pil_resample_coeffs(w, S), pil_resample_coeffs(h, S), pil_resize_vertical_first(h, w, S)
         nw, nh = resized_size(w, h, self.resize)
         left, top, _, _ = center_crop_box(nw, nh, S)
-        return pil_resample_coeffs(w, nw, left, S), pil_resample_coeffs(h, nh, top, S)
+        return pil_resample_coeffs(w, nw, left, S), pil_resample_coeffs(h, nh, top, S), pil_resize_vertical_first(h, w, nh)
 
     def __call__(self, images, params: Optional[dict] = None) -> torch.Tensor:
         """``params`` (tests / reproducing a given draw): dict(flip=[B] bool, factors=[B, 4] (brightness, contrast, saturation, hue),
@@ -323,14 +338,16 @@ class DeviceImagePipeline:
         KX = max(p[0][1].shape[1] for p in plans)
         KY = max(p[1][1].shape[1] for p in plans)
         max_h = max(a.shape[0] for a in arrs)
+        vfirst = np.array([p[2] for p in plans], dtype=np.uint8)
+        max_w = max([a.shape[1] for a, v in zip(arrs, vfirst) if v], default=0)
         sizes = [a.size for a in arrs]
         offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
         total = int(sum(sizes))
-        # ---- one pinned arena: pixels | offsets | sizes | x bounds | x coefs | y bounds | y coefs | flips | jitter params
+        # ---- one pinned arena: pixels | offsets | sizes | x bounds | x coefs | y bounds | y coefs | flips | jitter params | vertical-first flags
         meta = [offs.view(np.uint8), np.array([[a.shape[0], a.shape[1]] for a in arrs], dtype=np.int32).view(np.uint8)]
         xb = np.zeros((B, S, 2), np.int32); xc = np.zeros((B, S, KX), np.int32)
         yb = np.zeros((B, S, 2), np.int32); yc = np.zeros((B, S, KY), np.int32)
-        for b, ((bx, cx), (by, cy)) in enumerate(plans):
+        for b, ((bx, cx), (by, cy), _) in enumerate(plans):
             xb[b], yb[b] = bx, by
             xc[b, :, :cx.shape[1]], yc[b, :, :cy.shape[1]] = cx, cy
         flips = np.zeros(B, np.uint8)
@@ -361,7 +378,7 @@ class DeviceImagePipeline:
                 if co is not None:
                     jit[b, 6:12] = co
             self.last_params = dict(flip=flips.copy(), factors=fac.copy(), order=orders, angle=list(angles))
-        parts = meta + [x.view(np.uint8).reshape(-1) for x in (xb, xc, yb, yc)] + [flips, jit.view(np.uint8).reshape(-1)]
+        parts = meta + [x.view(np.uint8).reshape(-1) for x in (xb, xc, yb, yc)] + [flips, jit.view(np.uint8).reshape(-1), vfirst]
         starts, pos = [], (total + 63) // 64 * 64
         for p_ in parts:
             starts.append(pos)
@@ -386,12 +403,13 @@ class DeviceImagePipeline:
         self._pinned[akey + ".event"] = ev
         base = dev.data_ptr()
         ptr = lambda i: base + starts[i]
-        tmp = torch.empty((B, max_h, S, 3), dtype=torch.uint8, device=self.device)
+        tmp = torch.empty((B, max(max_h * S, S * max_w), 3), dtype=torch.uint8, device=self.device)
         out = torch.empty((B, S, S, 3), dtype=torch.uint8, device=self.device)
         lib = _lib.load()
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(lib.mh_image_resample_u8(base, ptr(0), ptr(1), ptr(2), ptr(3), KX, ptr(4), ptr(5), KY,
-                                            ptr(6) if self.augment else None, tmp.data_ptr(), out.data_ptr(), B, max_h, S, S, stream),
+                                            ptr(6) if self.augment else None, ptr(8) if max_w else None, tmp.data_ptr(),
+                                            out.data_ptr(), B, max_h, max_w, S, S, stream),
                    "mh_image_resample_u8")
         if self.augment:
             scratch, out2 = torch.empty_like(out), torch.empty_like(out)

@@ -223,14 +223,17 @@ def test_image_projection_name_is_configurable():
 def test_pil_resample_restatement_is_bit_exact():
     """data.pil_resample_coeffs (PIL's precompute_coeffs / normalize_coeffs_8bpc restated) + the two-pass uint8 arithmetic the
     HIP kernels run (data.resample_u8_reference) against PIL's own Image.resize(BILINEAR): every pixel equal, for down- and
-    up-scaling, for the centre-crop window of Resize(256) and for Resize((224, 224))."""
+    up-scaling, for the centre-crop window of Resize(256) and for Resize((224, 224)).  Pillow (12.2.0, PIL/Image.py resize) takes
+    the vertical pass first for h > 100 w when the height shrinks; data.pil_resize_vertical_first restates that rule, and both
+    sides of it are pinned here at output sizes 32, 224 and 336."""
     from PIL import Image
-    from multimodal_propaganda_meme_classification_amd.data import (center_crop_box, pil_resample_coeffs, resample_u8_reference,
-                                                                    resized_size)
+    from multimodal_propaganda_meme_classification_amd.data import (center_crop_box, pil_resample_coeffs, pil_resize_vertical_first,
+                                                                    resample_u8_reference, resized_size)
     rng = np.random.default_rng(0)
     for (h, w) in ((300, 400), (427, 640), (97, 131), (1000, 333)):
         img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
         nw, nh = resized_size(w, h, 256)
+        assert not pil_resize_vertical_first(h, w, nh) and not pil_resize_vertical_first(h, w, 224)
         ref = np.asarray(Image.fromarray(img).resize((nw, nh), Image.BILINEAR))
         left, top, _, _ = center_crop_box(nw, nh, 224)
         got = resample_u8_reference(img, *pil_resample_coeffs(w, nw, left, 224), *pil_resample_coeffs(h, nh, top, 224))
@@ -238,6 +241,35 @@ def test_pil_resample_restatement_is_bit_exact():
         ref2 = np.asarray(Image.fromarray(img).resize((224, 224), Image.BILINEAR))
         got2 = resample_u8_reference(img, *pil_resample_coeffs(w, 224), *pil_resample_coeffs(h, 224))
         assert np.array_equal(got2, ref2), (h, w)
+    # tall, narrow sources on both sides of h = 100 w (Resize((S, S))), and their transposes (never vertical-first)
+    want_vf = {(3000, 17): True, (2000, 17): True, (1701, 17): True, (1700, 17): False, (1000, 8): True, (801, 8): True,
+               (800, 8): False, (600, 8): False, (4000, 25): True, (2501, 25): True, (2500, 25): False, (2000, 25): False,
+               (4000, 40): False, (3000, 40): False, (101, 1): True, (100, 1): False, (17, 3000): False, (17, 4000): False}
+    differ = 0
+    for (h, w), vf in want_vf.items():
+        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        for S in (32, 224, 336):
+            assert pil_resize_vertical_first(h, w, S) == (vf and S < h), (h, w, S)
+            ref = np.asarray(Image.fromarray(img).resize((S, S), Image.BILINEAR))
+            plan = pil_resample_coeffs(w, S) + pil_resample_coeffs(h, S)
+            got = resample_u8_reference(img, *plan, vertical_first=pil_resize_vertical_first(h, w, S))
+            assert np.array_equal(got, ref), (h, w, S)
+            differ += int(not np.array_equal(resample_u8_reference(img, *plan, vertical_first=not pil_resize_vertical_first(h, w, S)), ref))
+    assert differ > len(want_vf)          # the order matters: the other one misses PIL on most of these sources
+    # the rule needs a shrinking height: 150 x 1 -> 224 (taller than 100 w, but enlarged) stays horizontal-first, and the centre-crop
+    # path (Resize(256): the short side grows to 256, so a tall source's height only shrinks when w > 256) meets it at w = 257
+    img = rng.integers(0, 256, (150, 1, 3), dtype=np.uint8)
+    assert not pil_resize_vertical_first(150, 1, 224)
+    assert np.array_equal(resample_u8_reference(img, *pil_resample_coeffs(1, 224), *pil_resample_coeffs(150, 224)),
+                          np.asarray(Image.fromarray(img).resize((224, 224), Image.BILINEAR)))
+    h, w = 25701, 257
+    img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    nw, nh = resized_size(w, h, 256)
+    assert pil_resize_vertical_first(h, w, nh)
+    left, top, _, _ = center_crop_box(nw, nh, 224)
+    ref = np.asarray(Image.fromarray(img).resize((nw, nh), Image.BILINEAR))[top:top + 224, left:left + 224]
+    got = resample_u8_reference(img, *pil_resample_coeffs(w, nw, left, 224), *pil_resample_coeffs(h, nh, top, 224), vertical_first=True)
+    assert np.array_equal(got, ref)
 
 
 def test_kevin_dataset_keys_and_collate_on_the_host():

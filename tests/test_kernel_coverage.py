@@ -13,9 +13,6 @@ ALLOWLIST = {
     "mh_gemm_ksplit_for": "host-only arithmetic: the split-K chunk count",
     "mh_bn2d_workspace_elems": "host-only workspace-size query",
     "mh_version": "host-only: the library's version word",
-    "mh_image_resample_u8": "called by data.py's device pipeline, bit-exact against PIL in test_next_rows_gpu.py",
-    "mh_image_luma_sum_u8": "called by data.py's device pipeline, bit-exact against PIL in test_next_rows_gpu.py",
-    "mh_image_jitter_rotate_u8": "called by data.py's device pipeline, bit-exact against PIL in test_next_rows_gpu.py",
 }
 
 

@@ -576,7 +576,7 @@ def test_device_image_pipeline_equals_the_pil_path(pkg, tmp_path):
                 ref = ImageEnhance.Color(ref).enhance(f[2])
         d = np.abs(np.asarray(ref).astype(int) - pipe2.last_u8[b].cpu().numpy().astype(int))
         assert d.max() == 0, (b, perm, int(d.max()), float((d > 0).mean()))     # bit-exact since round 3 (the blend's product and sum are rounded separately, as in ImagingBlend)
-    # rotation: 90 degrees is an exact permutation of the pixels
+    # identity jitter at angle 0 is the resize itself, flipped or not
     pipe3 = DeviceImagePipeline(224, mode="stretch", augment=True, device="cuda", generator=torch.Generator().manual_seed(7),
                                 jitter=(0.0, 0.0, 0.0, 0.0), degrees=0.0)
     base = pipe3(imgs[:2])
@@ -586,6 +586,11 @@ def test_device_image_pipeline_equals_the_pil_path(pkg, tmp_path):
     g7 = torch.Generator().manual_seed(7)
     fl = (torch.rand(2, generator=g7) < 0.5).numpy()
     assert np.array_equal(base_u8[0].cpu().numpy(), ref0[:, ::-1] if fl[0] else ref0)          # identity jitter, angle 0
+    # rotation: 90 degrees is an exact permutation of the pixels (np.rot90: counter-clockwise, as Image.rotate)
+    pipe3(imgs[:2], params=dict(flip=[0, 1], factors=[[1.0, 1.0, 1.0, 0.0]] * 2, order=[[0, 1, 2, 3]] * 2, angle=[90.0, 90.0]))
+    ref1 = np.asarray(imgs[1].convert("RGB").resize((224, 224), Image.BILINEAR))
+    assert np.array_equal(pipe3.last_u8[0].cpu().numpy(), np.rot90(ref0))
+    assert np.array_equal(pipe3.last_u8[1].cpu().numpy(), np.rot90(ref1[:, ::-1]))
 
 
 def test_device_jitter_hue_and_rotation_equal_torchvisions_pil_path(pkg, tmp_path):
