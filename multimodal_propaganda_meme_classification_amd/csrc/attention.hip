@@ -795,26 +795,6 @@ __global__ __launch_bounds__(448) void attn_fwd_dual_kernel(const AttnArgs A, co
         attn_fwd_body<4, 2, DROP_B>(Bp, 0, 1, blockIdx.y - nA, smem);
     }
 }
-template <bool DROP_B>
-__global__ __launch_bounds__(448) void attn_bwd_dq_dual_kernel(const AttnArgs A, const AttnArgs Bp, const int nA) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if ((int)blockIdx.y < nA) {
-        attn_bwd_dq_body<7, 0, false>(A, 0, 1, blockIdx.y, smem);
-    } else {
-        if (threadIdx.x >= 256) return;
-        attn_bwd_dq_body<4, 2, DROP_B>(Bp, 0, 1, blockIdx.y - nA, smem);
-    }
-}
-template <bool DROP_B>
-__global__ __launch_bounds__(448) void attn_bwd_dkv_dual_kernel(const AttnArgs A, const AttnArgs Bp, const int nA) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if ((int)blockIdx.y < nA) {
-        attn_bwd_dkv_body<7, 0, false>(A, 0, 1, blockIdx.y, smem);
-    } else {
-        if (threadIdx.x >= 256) return;
-        attn_bwd_dkv_body<4, 2, DROP_B>(Bp, 0, 1, blockIdx.y - nA, smem);
-    }
-}
 
 // The whole backward of a layer pair in ONE launch: workgroup roles [dQ of A | dK,dV of A | dQ of B | dK,dV of B].
 // The dK/dV workgroups compute their own delta (OWN_DELTA), so no role waits for another; the dQ and dK/dV sweeps --
@@ -1040,93 +1020,15 @@ __global__ __launch_bounds__(256) void attn_bwd_merged_single_kernel(const AttnA
 }
 
 // ---- launch helpers ----------------------------------------------------------------------------------
-// resident when S <= 256 (NT_RES = 2 for S <= 128, else 4); the 32-row tiles of a head are dealt to
-// `split` workgroups of 4 waves (split chosen so that every wave has work and the grid fills 256 CUs)
-template <typename K>
-void set_lds(K kern, int bytes) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+// Every kernel goes out through here.  KERN is one instantiation; THREADS (its __launch_bounds__) and LDS (its dynamic LDS
+// bytes) are template arguments because an instantiation has one value of each wherever it is launched from.  The
+// instantiation's dynamic-LDS limit is raised to LDS the first time it is launched.
+template <auto KERN, int THREADS, int LDS, typename... Args>
+void launch(dim3 grid, hipStream_t s, const Args&... args) {
+    static const hipError_t raised = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    (void)raised;
+    hipLaunchKernelGGL(KERN, grid, dim3(THREADS), LDS, s, args...);
 }
-// sequences up to this length keep a head's whole K/V (or Q/dO) resident in LDS in the BACKWARD kernels
-// (96-128 KB per workgroup at S = 197); env MEMEHIP_ATTN_BWD_RESIDENT_MAX overrides for A/B runs
-int bwd_resident_max() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("MEMEHIP_ATTN_BWD_RESIDENT_MAX");
-        v = e ? atoi(e) : 128;   // measured: at S = 197 the 24-KB streaming kernels co-schedule better with the side-stream GEMMs
-    }
-    return v;
-}
-// MEMEHIP_ATTN_BWD_MERGED: 0 = dQ launch then dK/dV launch (round 1), 1 = one launch, text heads streaming,
-// 2 = one launch, text heads resident (default).  Measured in the step (same box, 30 steps): 10.05 / 10.01 / 10.00 ms --
-// the side-stream weight-gradient GEMMs already fill the holes of the two-launch form, so the merge returns little.
-int bwd_merged_mode() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("MEMEHIP_ATTN_BWD_MERGED");
-        v = e ? atoi(e) : 2;
-        if (v < 0 || v > 2) v = 2;
-    }
-    return v;
-}
-bool seven_waves() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("MEMEHIP_ATTN_SEVEN_WAVES");
-        v = e ? atoi(e) : 1;
-    }
-    return v != 0;
-}
-bool fwd_seven_waves() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("MEMEHIP_ATTN_FWD_SEVEN_WAVES");
-        v = e ? atoi(e) : 1;
-    }
-    return v != 0;
-}
-// one-pass backward for 129..224-token heads (default on); mh_attn_set_onepass(0) / MEMEHIP_ATTN_ONEPASS=0 restore the two sweeps
-int g_onepass = -1;
-bool onepass_on() {
-    if (g_onepass < 0) {
-        const char* e = getenv("MEMEHIP_ATTN_ONEPASS");
-        g_onepass = e ? atoi(e) : 2;      // 2 = both towers in ONE launch (attn_bwd_onepass_dual_kernel; default), 1 = two launches
-        // (same box, 60 steps, two repetitions, ms per step: two sweeps 9.98 / 10.00, one pass in two launches 9.95 / 9.99, in one launch 9.90 / 9.85)
-    }
-    return g_onepass != 0;
-}
-int split_for(int S) {
-    const int tiles32 = (S + 31) / 32;
-    return tiles32 > 4 ? 2 : 1;
-}
-
-}  // namespace
-
-#define ATTN_LAUNCH(KERN, NW_, NT_, GRID, LDS, ARGS)                                                      \
-    do {                                                                                                 \
-        if (dr) {                                                                                        \
-            static bool once_t = (set_lds(KERN<NW_, NT_, true>, LDS), true);                             \
-            (void)once_t;                                                                                \
-            hipLaunchKernelGGL((KERN<NW_, NT_, true>), GRID, dim3(NW_ * 64), LDS, s, ARGS);              \
-        } else {                                                                                         \
-            static bool once_f = (set_lds(KERN<NW_, NT_, false>, LDS), true);                            \
-            (void)once_f;                                                                                \
-            hipLaunchKernelGGL((KERN<NW_, NT_, false>), GRID, dim3(NW_ * 64), LDS, s, ARGS);             \
-        }                                                                                                \
-    } while (0)
-#define ATTN_LAUNCH_DUAL(KERN, LDS, GRID, A_, B_, NA_)                                                   \
-    do {                                                                                                 \
-        if (dr) {                                                                                        \
-            static bool once_t = (set_lds(KERN<true>, LDS), true);                                       \
-            (void)once_t;                                                                                \
-            hipLaunchKernelGGL((KERN<true>), GRID, dim3(448), LDS, s, A_, B_, NA_);                      \
-        } else {                                                                                         \
-            static bool once_f = (set_lds(KERN<false>, LDS), true);                                      \
-            (void)once_f;                                                                                \
-            hipLaunchKernelGGL((KERN<false>), GRID, dim3(448), LDS, s, A_, B_, NA_);                     \
-        }                                                                                                \
-    } while (0)
-
-namespace {
 
 int check_problem(const MhAttnProblem& p, bool bwd) {
     if (!p.qkv || !p.out || !p.lse) return MH_EINVAL;
@@ -1155,66 +1057,61 @@ constexpr int lds_fwd(int nt) { return 2 * (nt > 0 ? nt : 1) * IMG + 2 * (nt > 0
 constexpr int lds_dq(int nt) { return 3 * (nt > 0 ? nt : 1) * IMG + 2 * (nt > 0 ? nt : 1) * TILE * 4 + 64; }
 constexpr int lds_dkv(int nt) { return 4 * (nt > 0 ? nt : 1) * IMG + 3 * (nt > 0 ? nt : 1) * TILE * 4; }
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
+// a launch whose workgroups take different roles gets the largest of the roles' sizes
+constexpr int LDS_FWD_DUAL = cmax(lds_fwd(4), lds_fwd(2));
+constexpr int LDS_BWD_TEXT = cmax(lds_dq(2), lds_dkv(2));
+constexpr int LDS_BWD_DUAL = cmax(cmax(lds_dq(0), lds_dkv(0)), LDS_BWD_TEXT);
 
+// ---- one problem: `dr` picks the DROP twin --------------------------------------------------------------
+template <int NW, int NT_RES>
+void fwd_one(bool dr, dim3 grid, hipStream_t s, const AttnArgs& a) {
+    dr ? launch<attn_fwd_kernel<NW, NT_RES, true>, NW * 64, lds_fwd(NT_RES)>(grid, s, a)
+       : launch<attn_fwd_kernel<NW, NT_RES, false>, NW * 64, lds_fwd(NT_RES)>(grid, s, a);
+}
+// the dQ sweep, then the dK/dV sweep (it reads the delta the dQ sweep wrote)
+template <int NW, int NT_RES>
+void bwd_sweeps(bool dr, dim3 grid, hipStream_t s, const AttnArgs& a) {
+    dr ? launch<attn_bwd_dq_kernel<NW, NT_RES, true>, NW * 64, lds_dq(NT_RES)>(grid, s, a)
+       : launch<attn_bwd_dq_kernel<NW, NT_RES, false>, NW * 64, lds_dq(NT_RES)>(grid, s, a);
+    dr ? launch<attn_bwd_dkv_kernel<NW, NT_RES, true>, NW * 64, lds_dkv(NT_RES)>(grid, s, a)
+       : launch<attn_bwd_dkv_kernel<NW, NT_RES, false>, NW * 64, lds_dkv(NT_RES)>(grid, s, a);
+}
+
+// Up to 256 rows the forward keeps a head's whole K and V in LDS (NT_RES tiles of 64 rows) and the query axis is split so
+// that every wave has a 32-row tile to work on.
 void launch_fwd(const MhAttnProblem& p, hipStream_t s) {
     const AttnArgs a = to_args(p);
     const bool dr = has_drop(p);
     const int S = p.S, BH = p.B * p.H;
-    if (S <= 128) ATTN_LAUNCH(attn_fwd_kernel, 4, 2, dim3(split_for(S), BH), lds_fwd(2), a);
-    else if (S <= 224 && fwd_seven_waves()) ATTN_LAUNCH(attn_fwd_kernel, 7, 4, dim3(1, BH), lds_fwd(4), a);
-    else if (S <= 256) ATTN_LAUNCH(attn_fwd_kernel, 4, 4, dim3(split_for(S), BH), lds_fwd(4), a);
-    else ATTN_LAUNCH(attn_fwd_kernel, 4, 0, dim3((S + 127) / 128, BH), lds_fwd(0), a);
+    if (S <= 128) fwd_one<4, 2>(dr, dim3(1, BH), s, a);
+    else if (S <= 224) fwd_one<7, 4>(dr, dim3(1, BH), s, a);   // ViT-B/16: 197 tokens = 7 tiles of 32, one 7-wave workgroup per head
+    else if (S <= 256) fwd_one<4, 4>(dr, dim3(2, BH), s, a);   // 8 tiles of 32: two 4-wave workgroups per head
+    else fwd_one<4, 0>(dr, dim3((S + 127) / 128, BH), s, a);   // streaming: one workgroup per 128 queries
 }
 
+// Backward of a 129..224-token head in one pass (attn_bwd_onepass_kernel), set by mh_attn_set_onepass: 2 = and, in a dual
+// pair, the text tower's sweeps ride in the same launch; 1 = the text tower gets a launch of its own; 0 = the two sweeps.
+int g_onepass = 2;
 bool onepass_fits(const MhAttnProblem& p) {
-    return onepass_on() && p.S > 128 && p.S <= OP_ROWS && !p.key_mask && !p.cu && !has_drop(p);
+    return g_onepass != 0 && p.S > 128 && p.S <= OP_ROWS && !p.key_mask && !p.cu && !has_drop(p);
 }
-void launch_onepass(const AttnArgs& a, int BH, hipStream_t s) {
-    static bool once = (set_lds(attn_bwd_onepass_kernel, OP_LDS), true);
-    (void)once;
-    hipLaunchKernelGGL(attn_bwd_onepass_kernel, dim3(BH), dim3(448), OP_LDS, s, a);
-}
+void launch_onepass(const AttnArgs& a, int BH, hipStream_t s) { launch<attn_bwd_onepass_kernel, 448, OP_LDS>(dim3(BH), s, a); }
 
+// Only heads of up to 128 rows keep Q / dO (K / V) resident in the backward sweeps: at 197 rows that would be 96-128 KB per
+// workgroup, and the 24-KB streaming kernels co-schedule better with the side-stream weight-gradient GEMMs.
 void launch_bwd(const MhAttnProblem& p, hipStream_t s) {
     const AttnArgs a = to_args(p);
     const bool dr = has_drop(p);
     const int S = p.S, BH = p.B * p.H;
-    const int rmax = bwd_resident_max();
-    if (onepass_fits(p)) {
-        launch_onepass(a, BH, s);
-        return;
-    }
-    if (S <= 128 && S <= rmax) {
-        const dim3 grid(split_for(S), BH);
-        ATTN_LAUNCH(attn_bwd_dq_kernel, 4, 2, grid, lds_dq(2), a);
-        ATTN_LAUNCH(attn_bwd_dkv_kernel, 4, 2, grid, lds_dkv(2), a);
-    } else if (S <= 256 && S <= rmax) {
-        const dim3 grid(split_for(S), BH);
-        ATTN_LAUNCH(attn_bwd_dq_kernel, 4, 4, grid, lds_dq(4), a);
-        ATTN_LAUNCH(attn_bwd_dkv_kernel, 4, 4, grid, lds_dkv(4), a);
-    } else if (S > 128 && S <= 224 && seven_waves()) {
-        // ViT-B/16 (197 tokens = 7 tiles of 32): one 7-wave workgroup per head, every wave busy, K/V (Q/dO) streamed once
-        const dim3 grid(1, BH);
-        ATTN_LAUNCH(attn_bwd_dq_kernel, 7, 0, grid, lds_dq(0), a);
-        ATTN_LAUNCH(attn_bwd_dkv_kernel, 7, 0, grid, lds_dkv(0), a);
-    } else {
-        const dim3 grid((S + 127) / 128, BH);
-        ATTN_LAUNCH(attn_bwd_dq_kernel, 4, 0, grid, lds_dq(0), a);
-        ATTN_LAUNCH(attn_bwd_dkv_kernel, 4, 0, grid, lds_dkv(0), a);
-    }
+    if (onepass_fits(p)) launch_onepass(a, BH, s);
+    else if (S <= 128) bwd_sweeps<4, 2>(dr, dim3(1, BH), s, a);
+    else if (S <= 224) bwd_sweeps<7, 0>(dr, dim3(1, BH), s, a);   // 7 tiles of 32: one 7-wave workgroup per head, every wave busy, K/V (Q/dO) streamed once
+    else bwd_sweeps<4, 0>(dr, dim3((S + 127) / 128, BH), s, a);
 }
 
-bool dual_off() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("MEMEHIP_ATTN_DUAL");
-        v = (e && atoi(e) == 0) ? 1 : 0;
-    }
-    return v != 0;
-}
 // two problems that fit the dual kernels: A = 129..224 tokens without dropout (ViT), B = <= 128 tokens (text)
 bool dual_pair(const MhAttnProblem* p, int n, int& ia, int& ib) {
-    if (n != 2 || dual_off() || !seven_waves() || !fwd_seven_waves() || bwd_resident_max() < 128) return false;
+    if (n != 2) return false;
     for (int k = 0; k < 2; ++k) {
         const MhAttnProblem &a = p[k], &b = p[1 - k];
         if (a.S > 128 && a.S <= 224 && !has_drop(a) && b.S <= 128) {
@@ -1237,17 +1134,9 @@ extern "C" int mh_attn_fwd_grouped(const MhAttnProblem* p, int n, mh_stream_t st
     if (dual_pair(p, n, ia, ib)) {
         const AttnArgs A = to_args(p[ia]), Bp = to_args(p[ib]);
         const int nA = p[ia].B * p[ia].H, nB = p[ib].B * p[ib].H;
-        const bool dr = has_drop(p[ib]);
-        constexpr int L = cmax(lds_fwd(4), lds_fwd(2));
-        if (dr) {
-            static bool once_t = (set_lds(attn_fwd_dual_kernel<4, true>, L), true);
-            (void)once_t;
-            hipLaunchKernelGGL((attn_fwd_dual_kernel<4, true>), dim3(1, nA + nB), dim3(448), L, s, A, Bp, nA);
-        } else {
-            static bool once_f = (set_lds(attn_fwd_dual_kernel<4, false>, L), true);
-            (void)once_f;
-            hipLaunchKernelGGL((attn_fwd_dual_kernel<4, false>), dim3(1, nA + nB), dim3(448), L, s, A, Bp, nA);
-        }
+        const dim3 grid(1, nA + nB);
+        has_drop(p[ib]) ? launch<attn_fwd_dual_kernel<4, true>, 448, LDS_FWD_DUAL>(grid, s, A, Bp, nA)
+                        : launch<attn_fwd_dual_kernel<4, false>, 448, LDS_FWD_DUAL>(grid, s, A, Bp, nA);
     } else {
         for (int i = 0; i < n; ++i) launch_fwd(p[i], s);
     }
@@ -1264,61 +1153,22 @@ extern "C" int mh_attn_bwd_grouped(const MhAttnProblem* p, int n, mh_stream_t st
         const AttnArgs A = to_args(p[ia]), Bp = to_args(p[ib]);
         const int nA = p[ia].B * p[ia].H, nB = p[ib].B * p[ib].H;
         const bool dr = has_drop(p[ib]);
-        const int mode = bwd_merged_mode();
-        if (onepass_fits(p[ia])) {
-            // ViT heads: one pass, one workgroup per head; text heads: their two sweeps as the roles of one launch
-            constexpr int L = cmax(lds_dq(2), lds_dkv(2));
-            if (g_onepass == 2) {
-                if (dr) {
-                    static bool o7 = (set_lds(attn_bwd_onepass_dual_kernel<2, true>, OP_LDS), true);
-                    (void)o7;
-                    hipLaunchKernelGGL((attn_bwd_onepass_dual_kernel<2, true>), dim3(1, nA + 2 * nB), dim3(448), OP_LDS, s, A, Bp, nA, nB);
-                } else {
-                    static bool o8 = (set_lds(attn_bwd_onepass_dual_kernel<2, false>, OP_LDS), true);
-                    (void)o8;
-                    hipLaunchKernelGGL((attn_bwd_onepass_dual_kernel<2, false>), dim3(1, nA + 2 * nB), dim3(448), OP_LDS, s, A, Bp, nA, nB);
-                }
-                return mh_launch_status();
-            }
-            launch_onepass(A, nA, s);
-            if (dr) {
-                static bool o5 = (set_lds(attn_bwd_merged_single_kernel<2, true>, L), true);
-                (void)o5;
-                hipLaunchKernelGGL((attn_bwd_merged_single_kernel<2, true>), dim3(1, 2 * nB), dim3(256), L, s, Bp, nB);
-            } else {
-                static bool o6 = (set_lds(attn_bwd_merged_single_kernel<2, false>, L), true);
-                (void)o6;
-                hipLaunchKernelGGL((attn_bwd_merged_single_kernel<2, false>), dim3(1, 2 * nB), dim3(256), L, s, Bp, nB);
-            }
-        } else if (mode == 0) {
-            const dim3 grid(1, nA + nB);
-            ATTN_LAUNCH_DUAL(attn_bwd_dq_dual_kernel, cmax(lds_dq(0), lds_dq(2)), grid, A, Bp, nA);
-            ATTN_LAUNCH_DUAL(attn_bwd_dkv_dual_kernel, cmax(lds_dkv(0), lds_dkv(2)), grid, A, Bp, nA);
-        } else {
+        if (!onepass_fits(p[ia])) {
+            // roles [dQ of A | dK,dV of A | dQ of B | dK,dV of B]
             const dim3 grid(1, 2 * (nA + nB));
-            if (mode == 2) {
-                constexpr int L = cmax(cmax(lds_dq(0), lds_dkv(0)), cmax(lds_dq(2), lds_dkv(2)));
-                if (dr) {
-                    static bool o1 = (set_lds(attn_bwd_merged_dual_kernel<2, true>, L), true);
-                    (void)o1;
-                    hipLaunchKernelGGL((attn_bwd_merged_dual_kernel<2, true>), grid, dim3(448), L, s, A, Bp, nA, nB);
-                } else {
-                    static bool o2 = (set_lds(attn_bwd_merged_dual_kernel<2, false>, L), true);
-                    (void)o2;
-                    hipLaunchKernelGGL((attn_bwd_merged_dual_kernel<2, false>), grid, dim3(448), L, s, A, Bp, nA, nB);
-                }
-            } else {
-                constexpr int L = cmax(lds_dq(0), lds_dkv(0));
-                if (dr) {
-                    static bool o3 = (set_lds(attn_bwd_merged_dual_kernel<0, true>, L), true);
-                    (void)o3;
-                    hipLaunchKernelGGL((attn_bwd_merged_dual_kernel<0, true>), grid, dim3(448), L, s, A, Bp, nA, nB);
-                } else {
-                    static bool o4 = (set_lds(attn_bwd_merged_dual_kernel<0, false>, L), true);
-                    (void)o4;
-                    hipLaunchKernelGGL((attn_bwd_merged_dual_kernel<0, false>), grid, dim3(448), L, s, A, Bp, nA, nB);
-                }
-            }
+            dr ? launch<attn_bwd_merged_dual_kernel<2, true>, 448, LDS_BWD_DUAL>(grid, s, A, Bp, nA, nB)
+               : launch<attn_bwd_merged_dual_kernel<2, false>, 448, LDS_BWD_DUAL>(grid, s, A, Bp, nA, nB);
+        } else if (g_onepass == 2) {
+            // roles [one pass of A | dQ of B | dK,dV of B]: the text heads' short chains fill the holes of the ViT heads' launch
+            // instead of paying a launch and a drain of their own
+            const dim3 grid(1, nA + 2 * nB);
+            dr ? launch<attn_bwd_onepass_dual_kernel<2, true>, 448, OP_LDS>(grid, s, A, Bp, nA, nB)
+               : launch<attn_bwd_onepass_dual_kernel<2, false>, 448, OP_LDS>(grid, s, A, Bp, nA, nB);
+        } else {
+            launch_onepass(A, nA, s);
+            const dim3 grid(1, 2 * nB);
+            dr ? launch<attn_bwd_merged_single_kernel<2, true>, 256, LDS_BWD_TEXT>(grid, s, Bp, nB)
+               : launch<attn_bwd_merged_single_kernel<2, false>, 256, LDS_BWD_TEXT>(grid, s, Bp, nB);
         }
     } else {
         for (int i = 0; i < n; ++i) launch_bwd(p[i], s);
@@ -1326,8 +1176,9 @@ extern "C" int mh_attn_bwd_grouped(const MhAttnProblem* p, int n, mh_stream_t st
     return mh_launch_status();
 }
 
+// a negative value restores the default
 extern "C" int mh_attn_set_onepass(int on) {
-    g_onepass = on;
+    g_onepass = on < 0 ? 2 : on;
     return MH_OK;
 }
 

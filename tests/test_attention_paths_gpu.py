@@ -5,8 +5,8 @@ times the kernels' own mask ops.dropout_mask(...) / (1 - p) at element ((b*H + h
 positions, also for the packed form).  A row with no key to attend to (its sequence's key mask is all zeros) has, by the
 convention of include/memehip.h, out = 0, lse = -inf and no gradient; the reference applies the same convention.
 
-Which kernel each case reaches (csrc/attention.hip: launch_fwd ~1159, onepass_fits ~1169, launch_bwd ~1178, dual_pair ~1216,
-mh_attn_fwd_grouped ~1231, mh_attn_bwd_grouped ~1257):
+Which kernel each case reaches (csrc/attention.hip: launch_fwd, onepass_fits, launch_bwd, dual_pair, mh_attn_fwd_grouped,
+mh_attn_bwd_grouped):
 
   S / mask / dropout                         forward                          backward
   ---------------------------------------------------------------------------------------------------------------------
@@ -17,13 +17,12 @@ mh_attn_fwd_grouped ~1231, mh_attn_bwd_grouped ~1257):
   225..256 (225, 255, 256)                   fwd <4, 4>, split 2               4-wave streaming <4, 0>
   S > 256 (257, 300, 577)                    fwd <4, 0> streaming              4-wave streaming <4, 0>
   dropout p = 0.1 (33, 128, 160, 224, 256, 257, masked and not): the DROP = true twin of every row above
-  (the resident-256 backward <4, 4> is dead at the default bwd_resident_max() = 128 and is not reached)
 
   grouped pair (one problem 129..224 without dropout + one <= 128; dual_pair):
     forward                       attn_fwd_dual_kernel<4, DROP_B>
     backward onepass 2            attn_bwd_onepass_dual_kernel<2, DROP_B>
     backward onepass 1            attn_bwd_onepass_kernel + attn_bwd_merged_single_kernel<2, DROP_B>
-    backward onepass 0            attn_bwd_merged_dual_kernel<2, DROP_B> (MEMEHIP_ATTN_BWD_MERGED default 2)
+    backward onepass 0            attn_bwd_merged_dual_kernel<2, DROP_B>
   a pair with S_a = 240 is refused by dual_pair: separate launches of the rows above.
 
 Packed masks hold empty sequences (first, middle, last), one-token sequences, lengths 31 / 32 / 33 / 64 / 65, holes, and
