@@ -317,6 +317,69 @@ def test_ddp_segmented_graph_path_world1(pkg, clip, ddp_mode, rccl_world1):
         assert 4 <= len(g2.graphs) <= len(g2.plan.bwd) + 3   # fwd, opt, gather marker + segments (paired)
 
 
+@pytest.mark.parametrize("ddp_mode", ["stream", "segments", "graph"])
+def test_ddp_schedules_at_full_width_equal_the_sequential_step(pkg, ddp_mode, rccl_world1):
+    """The three data-parallel schedules at real widths -- config 3 with 4 + 4 layers, B = 32, S = 128, fp16 (dynamic loss scale on
+    the device), where a weight-gradient GEMM lasts long enough for a missing cross-stream edge or an Adam slice that overtakes its
+    all-reduce to change numbers -- on the 1-rank RCCL group, against the ONE-STREAM sequential step (no graph, no side stream, Adam
+    after the backward; the reference of tests/test_step_schedules_gpu.py): parameters, 16-bit shadow, both Adam moments, gradients,
+    logits, correct count and loss bit-identical after each of four steps over two alternating batches."""
+    from conftest import parity_log
+    from multimodal_propaganda_meme_classification_amd import ddp
+    O = _oracle()
+    torch.set_num_threads(16)
+    cfg = O.config3("cls")
+    cfg.text.layers = cfg.image.layers = 4
+    B, S = 32, 128
+    params = O.init_params(cfg, 15)
+    models = []
+    for _ in range(2):
+        d = cfg.to_dict()
+        d["compute_dtype"] = "fp16"
+        m = pkg.MultimodalClassifier.from_config(pkg.ModelConfig.from_dict(d), init=False)
+        m.load_state_dict(params)
+        models.append(m.to("cuda").train())
+    m1, m2 = models
+    o1, o2 = pkg.Adam(m1.parameters(), lr=LR, model=m1), pkg.Adam(m2.parameters(), lr=LR, model=m2)
+    ddp.broadcast_parameters(m2.flat_params)
+    red = ddp.GradientReducer(m2.flat_grads)
+    g1 = pkg.GraphedStep(m1, o1, B, S, use_graph=False, overlap_wgrad=False, overlap_optimizer=False)
+    g2 = pkg.GraphedStep(m2, o2, B, S, reducer=red, ddp_mode=ddp_mode)
+    try:
+        assert g1.side is None and not g1.use_graph and not g1.opt_in_bwd
+        assert g2.use_graph and g2.ddp_opt_in_bwd and g2.scaler is not None and g1.scaler is not None
+        batches = []
+        for seed, single in ((16, False), (17, True)):
+            text, image, mask, labels = O.synthetic_batch(cfg, B, S, seed=seed)
+            if single:
+                mask[0, 1:] = 0           # a row with one valid token
+                text[0, 1:] = 0
+            batches.append([t.cuda() for t in (text, image, mask, labels)])
+        n = 0
+        for step in range(4):
+            for g in (g1, g2):
+                g.load_batch(*batches[step % 2])
+            l1, _ = g1.step()
+            l2, _ = g2.step()
+            torch.cuda.synchronize()
+            assert g2.graphs is not None, "the data-parallel step did not replay a hipGraph"
+            pairs = dict(flat_params=(m1.flat_params, m2.flat_params), flat_shadow=(m1.flat_shadow, m2.flat_shadow),
+                         adam_m=(o1._flat["M"], o2._flat["M"]), adam_v=(o1._flat["V"], o2._flat["V"]),
+                         flat_grads=(m1.flat_grads, m2.flat_grads), logits=(g1.plan.buf["logits"], g2.plan.buf["logits"]),
+                         ncorrect=(g1.plan.buf["ncorrect"], g2.plan.buf["ncorrect"]), loss=(l1, l2))
+            for key, (a, b) in pairs.items():
+                assert torch.equal(a, b), f"ddp_mode {ddp_mode}: {key} differs from the sequential step after step {step}: " \
+                                          f"{int((a != b).sum())} of {a.numel()} elements"
+                n += a.numel()
+            assert bool(torch.isfinite(m1.flat_params).all()) and bool(torch.isfinite(l1).all())
+        assert o1.skipped_steps == 0 and o2.skipped_steps == 0
+        parity_log(f"[ddp {ddp_mode}, config 3 at 4 + 4 layers, B 32, S 128, fp16] 4 steps == sequential: {n} elements compared bit for bit")
+    finally:
+        g2.close()
+        g1.close()
+        red.close()
+
+
 def test_capture_survives_the_process_groups_watchdog(pkg):
     """The segment graphs are captured while the process group's watchdog thread may be querying the events of earlier
     collectives (`bench.py --force-ddp` died in hipErrorStreamCaptureInvalidated at its first capture, round 3): every capture of
