@@ -18,7 +18,8 @@ example_scripts/Multimodal_example_task2C.txt:175,183 and the step at :200-223.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Callable, Dict, List, Optional, Tuple
+import os
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -28,9 +29,21 @@ from ._lib import (MH_GEMM_ACCUM, MH_GEMM_DERIV_AUX, MH_GEMM_GELU, MH_GEMM_OUT_F
 from .config import Layout, ModelConfig
 
 BF16, F32, I64 = torch.bfloat16, torch.float32, torch.int64
-import os as _os
-LN_PARTS = int(_os.environ.get("MEMEHIP_LN_PARTS", "512"))     # workgroups (= sets of dgamma/dbeta partials) per LayerNorm backward
-DERIV_AUX = _os.environ.get("MEMEHIP_GEMM_DERIV_AUX", "1") != "0"     # FFN-up epilogue stores gelu'(x) for the backward (A/B: 0 = store x)
+LN_PARTS = int(os.environ.get("MEMEHIP_LN_PARTS", "512"))     # workgroups (= sets of dgamma/dbeta partials) per LayerNorm backward
+DERIV_AUX = os.environ.get("MEMEHIP_GEMM_DERIV_AUX", "1") != "0"     # FFN-up epilogue stores gelu'(x) for the backward (A/B: 0 = store x)
+
+LAUNCH, PY, WAIT = "launch", "py", "wait"
+
+
+class Call(NamedTuple):
+    """One entry of a Segment.  A launch has ``fn``; the two other kinds carry their payload in ``args``."""
+    fn: Optional[Callable]      # prepared C-ABI entry point (called as fn(*args, stream)); None unless kind == LAUNCH
+    args: object                # LAUNCH: the argument tuple; PY: a python callback; WAIT: the name of the segment to wait for
+    name: str                   # C-ABI function name (error messages)
+    tag: str                    # kernel family, for run_timed
+    work: object                # FLOPs or bytes of the launch: a float, or (fixed, per-live-row part at the maximum row count)
+    lane: int                   # 1 = a weight-gradient GEMM, which nothing later in the backward chain reads
+    kind: str = LAUNCH
 
 
 class Segment:
@@ -39,22 +52,22 @@ class Segment:
     def __init__(self, name: str, lib=None):
         self.name = name
         self.lib = lib if lib is not None else _lib.load()
-        self.calls: List[Tuple] = []
+        self.calls: List[Call] = []
 
     def c(self, fn_name: str, *args, tag: Optional[str] = None, work: float = 0.0, lane: int = 0):
-        self.calls.append((getattr(self.lib, fn_name), args, fn_name, tag or fn_name, work, lane))
+        self.calls.append(Call(getattr(self.lib, fn_name), args, fn_name, tag or fn_name, work, lane))
 
     def py(self, fn: Callable[[], None]):
-        self.calls.append((None, fn, "py", "py", 0.0, 0))
+        self.calls.append(Call(None, fn, PY, PY, 0.0, 0, PY))
 
     def wait(self, key: str):
         """On a multi-stream run: the main stream waits for the lane-1 work of segment `key`."""
-        self.calls.append((None, key, "wait", "wait", 0.0, 0))
+        self.calls.append(Call(None, key, WAIT, WAIT, 0.0, 0, WAIT))
 
     def run(self, stream: int):
-        for fn, args, name, _, _, _ in self.calls:
+        for fn, args, name, _, _, _, kind in self.calls:
             if fn is None:
-                if name == "py":
+                if kind == PY:
                     args()
             else:
                 st = fn(*args, stream)
@@ -70,11 +83,11 @@ class Segment:
         mp = main.cuda_stream
         sp = side.cuda_stream if side is not None else mp      # side=None: lane-1 work stays on the main stream
         forked1 = False
-        for fn, args, name, _, _, lane in self.calls:
+        for fn, args, name, _, _, lane, kind in self.calls:
             if fn is None:
-                if name == "py":
+                if kind == PY:
                     args()
-                elif name == "wait":
+                elif kind == WAIT:
                     if args in events:
                         main.wait_event(events.pop(args))
                 continue
@@ -98,11 +111,11 @@ class Segment:
         """Eager replay that brackets every launch tagged `tag` with events on the launch stream;
         appends (start_event, end_event, work) to `out`.  `work` of a launch is (fixed, per-live-row part at the
         maximum row count): dyn_scale = live rows / maximum rows of the packed text tower."""
-        for fn, args, name, t, work, _ in self.calls:
+        for fn, args, name, t, work, _, kind in self.calls:
             if isinstance(work, tuple):
                 work = work[0] + work[1] * dyn_scale
             if fn is None:
-                if name == "py":
+                if kind == PY:
                     args()
                 continue
             if t == tag:
@@ -138,6 +151,10 @@ class Plan:
         self.gemm_flops = 0.0                 # algorithmic GEMM FLOPs of one step (fwd + dgrad + wgrad), no row packed away
         self.gemm_flops_dyn = 0.0             # the part of it that scales with the live rows of the packed text tower
         self.packed = False
+        self.dropout_on = False               # some dropout probability is non-zero in this plan
+        self.features = False                 # False | True | "sequence": where the plan stops (Engine.plan)
+        self.gather = None                    # data parallel: (local, gathered) tensor pairs exchanged before "bwd_embed_tables"
+        self._ln_jobs: Dict[int, list] = {}   # width -> (partials, dgamma, dbeta) of every LayerNorm backward, summed in "bwd_embed"
 
 
 class Engine:
@@ -152,7 +169,6 @@ class Engine:
         self.lib = _lib.load(self.kind)
         self.gscale = cfg.stream_scale          # scale carried by the 16-bit gradient streams
         # padding-free text tower (rows with attention_mask == 0 are never computed); MEMEHIP_PACK_TEXT=0 for A/B runs
-        import os
         self.pack_text = bool(getattr(cfg, "pack_text", True)) and os.environ.get("MEMEHIP_PACK_TEXT", "1") != "0"
         self.plans: Dict[Tuple[int, int], Plan] = {}
         # one byte per word-embedding row: has it ever received a gradient?  (rows that have not keep g = m = v = 0,
@@ -237,7 +253,6 @@ class Engine:
 
     @staticmethod
     def _ln_groups(by_d):
-        import os
         if os.environ.get("MEMEHIP_LN_GROUP", "1") == "0":      # A/B switch: one launch per LayerNorm
             return [(D, [j]) for D, js in by_d.items() for j in js]
         return list(by_d.items())
@@ -355,7 +370,6 @@ class Engine:
         if B > 1024:
             raise ValueError("batch > 1024 not supported by the loss kernel")
         pl = Plan(B, S, self.lib)
-        pl._ln_jobs = {}
         BF16 = self.T16          # every 16-bit buffer below uses the configured storage type
         # dropout sites: (rng words pointer, p, site id); None when off.  rng = int32[4] {seed_lo, seed_hi, step, -}
         rng_t = torch.zeros(4, dtype=torch.int32, device=self.dev)

@@ -21,7 +21,8 @@ import ctypes as C
 import math
 import os
 import weakref
-from typing import Dict, Optional
+from functools import partial
+from typing import Callable, Dict, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -1208,20 +1209,68 @@ def flatten_parameters(module: nn.Module) -> nn.Module:
 CAPTURE_MODE = "thread_local"
 
 
+class Bucket(NamedTuple):
+    """Backward segments whose gradients go to the all-reduce together (on a single GPU: one segment each)."""
+    segs: tuple                 # the backward segments, in execution order
+    rng: Optional[tuple]        # the flat gradient range complete after them (union of their adjacent ranges), None: none
+    rngs: tuple                 # ... per segment
+    layers: bool                # every segment is a layer segment: only then may the range's Adam slice run before the tail
+    gather: bool                # reducer.gather(plan.gather) must precede it ("bwd_embed_tables" reads every rank's rows)
+
+
+def gradient_buckets(bwd, bucket_after, group: int):
+    """THE bucket rule: consecutive layer segments share a bucket in groups of `group` -- their gradient
+    ranges are adjacent in the flat buffer: fewer graph boundaries, larger RCCL messages (measured on a 1-rank RCCL group:
+    11.21 ms/step with one graph per layer, 10.99 in pairs, 10.97 in threes).  The last two layers and everything that is not a
+    layer go on their own, so the all-reduce left exposed after the backward stays small; a left-over layer goes on its own."""
+    n_layers = sum(1 for sg in bwd if sg.name.startswith("bwd_layer_"))
+    groups, seen, open_ = [], 0, False
+    for sg in bwd:
+        layer = sg.name.startswith("bwd_layer_")
+        seen += layer
+        grouped = layer and seen <= n_layers - 2
+        if grouped and open_:
+            groups[-1].append(sg)
+        else:
+            groups.append([sg])
+        open_ = grouped and len(groups[-1]) < group
+    out = []
+    for segs in groups:
+        rngs = tuple(bucket_after[sg.name] for sg in segs if bucket_after.get(sg.name) is not None)
+        out.append(Bucket(tuple(segs), (min(r[0] for r in rngs), max(r[1] for r in rngs)) if rngs else None, rngs,
+                          all(sg.name.startswith("bwd_layer_") for sg in segs), segs[0].name == "bwd_embed_tables"))
+    return out
+
+
+DEVICE, HOST, REDUCE = "device", "host", "reduce"
+
+
+class Unit(NamedTuple):
+    """One entry of the step schedule: ``fn(step, stream)`` issues it."""
+    name: str
+    fn: Callable
+    kind: str       # DEVICE: launches (capturable on its own); HOST: a blocking exchange; REDUCE: the gradient all-reduce machinery
+
+
 class GraphedStep:
     """Whole fine-tune step (forward, loss, backward, clip, Adam) captured into hipGraphs and
     replayed per batch, so the ~600 kernel launches of a step cost a handful of host calls.
 
-    Single GPU: ONE graph.  Data parallel (``reducer`` given), ``ddp_mode``:
+    The schedule is a flat list of units (``self.units``), built once; ``mode`` only decides which of them are captured
+    together (``self.groups``).  ``"single"`` (no ``reducer``): ONE graph.  Data parallel (``reducer`` given), ``ddp_mode``:
 
-    * ``"segments"`` (default): one graph per backward segment (pairs of layers), the all-reduce issued between graph
-      launches.  Every graph boundary joins all streams; measured 10.55 ms against 9.91 for the single graph at one rank.
+    * ``"segments"`` (default): one graph per gradient bucket (pairs of layers, ``gradient_buckets``), the all-reduce issued
+      between graph launches.  Every graph boundary joins all streams; measured 10.55 ms against 9.91 for the single graph at
+      one rank.
     * ``"stream"``: the forward + loss is one graph; the backward is launched eagerly with exactly the single-GPU two-stream
       schedule (weight-gradient GEMMs on a side stream, no joins between layers), and as soon as a bucket's gradient slice
-      is complete -- its segment's main-stream work and its weight-gradient event -- the all-reduce of that slice is issued
+      is complete -- its segments' main-stream work and their weight-gradient events -- the all-reduce of that slice is issued
       behind a fence stream and, behind the all-reduce, that slice's Adam update.  The host issues a step in 5.1 ms, so it
       stays ahead of the GPU, but eagerly launched cross-stream edges resolve more slowly than a graph's (10-35 us gaps in
       the kernel trace): 10.82 ms at one rank.  Kept for multi-rank A/B.
+    * ``"graph"``: the "stream" schedule captured WHOLE, collectives included, into ONE hipGraph (RCCL's launches are
+      capturable; torch's process group records them as nodes on its own stream, forked from and joined to the capture stream
+      by events).
     """
 
     def __init__(self, model: MultimodalClassifier, optimizer: Adam, batch: int, seq_len: int, use_graph: bool = True,
@@ -1260,37 +1309,42 @@ class GraphedStep:
         ddp_mode = ddp_mode or os.environ.get("MEMEHIP_DDP_MODE", "segments")
         if ddp_mode not in ("stream", "segments", "graph"):
             raise ValueError(f"ddp_mode must be 'stream', 'segments' or 'graph', got {ddp_mode!r}")
-        # "graph": the "stream" schedule -- two-stream backward, every completed gradient slice all-reduced behind a fence stream, its
-        # Adam slice behind the all-reduce -- captured WHOLE, collectives included, into ONE hipGraph (RCCL's launches are capturable;
-        # torch's process group records them as nodes on its own stream, forked from and joined to the capture stream by events)
-        self.ddp_graph = reducer is not None and ddp_mode == "graph"
-        self.ddp_stream = reducer is not None and ddp_mode in ("stream", "graph")
-        # weight-gradient GEMMs run on a second stream beside the LayerNorm / attention / dgrad chain
-        # (a high-priority side stream was measured: 16.1 vs 9.79 ms for config 3, 92.0 vs 81.2 ms for config 5 -- as with the
-        #  high-priority main stream of round 1, any non-default stream priority inside the graph loses badly on this stack)
-        self.side = torch.cuda.Stream() if ((overlap_wgrad or overlap_optimizer) and (reducer is None or self.ddp_stream)) else None
-        self.ddp_fence = torch.cuda.Stream() if self.ddp_stream else None
-        self.wgrad_side = bool(overlap_wgrad)
-        # optimizer-in-backward: the (HBM-bound) Adam update of a layer pair's matrices follows their weight-gradient
+        self.mode = mode = "single" if reducer is None else ddp_mode
+        self.ddp_graph = mode == "graph"
+        self.ddp_stream = mode in ("stream", "graph")
+        early_ok = overlap_optimizer and optimizer.max_grad_norm is None and optimizer.skip_nonfinite != "strict"
+        # optimizer-in-backward: the (HBM-bound) Adam update of a layer's matrices follows their weight-gradient
         # GEMMs on the side stream, under the (MFMA-bound) backward chain of the layers below; only the tail
         # (embeddings, biases, head) is updated after the backward.  Needs no global clip and a single GPU.
         # (with skip_nonfinite=True the slices go through the GUARDED update kernels; clipping and "strict" need the global norm first)
-        self.opt_in_bwd = bool(overlap_optimizer and self.side is not None and reducer is None and optimizer.max_grad_norm is None
-                               and optimizer.skip_nonfinite != "strict")
-        # data parallel: the same idea behind the all-reduce -- as soon as a layer pair's gradient slice has been summed
+        self.opt_in_bwd = bool(early_ok and mode == "single")
+        # data parallel: the same idea behind the all-reduce -- as soon as a bucket's gradient slice has been summed
         # over the ranks, its Adam update runs on a side stream under the backward of the layers below
-        self.ddp_opt_in_bwd = bool(overlap_optimizer and reducer is not None and optimizer.max_grad_norm is None
-                                   and optimizer.skip_nonfinite != "strict")
-        self.ddp_side = torch.cuda.Stream() if self.ddp_opt_in_bwd else None
-        self.ddp_wside = torch.cuda.Stream() if (reducer is not None and overlap_wgrad and not self.ddp_stream) else None
+        self.ddp_opt_in_bwd = bool(early_ok and mode != "single")
+        # `side`: the stream the lane-1 work forks to.  The weight-gradient GEMMs run on it beside the LayerNorm / attention /
+        # dgrad chain ("segments": inside a bucket's graph only), and on a single GPU the early Adam slices behind them
+        # (a high-priority side stream was measured: 16.1 vs 9.79 ms for config 3, 92.0 vs 81.2 ms for config 5 -- as with the
+        #  high-priority main stream of round 1, any non-default stream priority inside the graph loses badly on this stack)
+        self.wgrad_side = bool(overlap_wgrad)
+        want_side = overlap_wgrad if mode == "segments" else (overlap_wgrad or overlap_optimizer)
+        self.side = torch.cuda.Stream() if want_side and mode != "segments" else None
+        self.ddp_fence = torch.cuda.Stream() if self.ddp_stream else None       # gathers what a bucket's all-reduce has to wait for
+        self.ddp_side = torch.cuda.Stream() if self.ddp_opt_in_bwd else None    # carries the Adam slices behind the all-reduces
+        if want_side and mode == "segments":        # (after `ddp_side`: the order in which torch's pool has always handed them out here)
+            self.side = torch.cuda.Stream()
+        # MEMEHIP_DDP_GROUP is read here and nowhere else; a single GPU has nothing to batch: one segment per bucket
+        group = max(1, int(os.environ.get("MEMEHIP_DDP_GROUP", "2"))) if reducer is not None else 1
+        self.buckets = gradient_buckets(self.plan.bwd, self.plan.bucket_after, group)
+        # the ranges whose Adam slice has run by the time the optimizer tail is launched (its ``skip=``)
+        self.early = [r for b in self.buckets if b.layers for r in b.rngs] if (self.opt_in_bwd or self.ddp_opt_in_bwd) else []
+        self.units, self.groups = self._schedule()
         self.closed = False
-        from . import ddp as _ddp
         _ddp._LIVE_STEPS.add(self)
 
     def close(self):
         """Explicit teardown, in dependency order: wait for the device, reset the hipGraphs (last captured first; the data-parallel
-        ones share ONE private memory pool, which is released with the last of them), drop the closures that keep this object in a
-        reference cycle, then the side / fence streams.  With a reducer this has to happen while the process group is alive
+        ones share ONE private memory pool, which is released with the last of them), drop the schedule, then the side / fence
+        streams.  With a reducer this has to happen while the process group is alive
         (``ddp.shutdown()`` closes steps, then reducers, then destroys the group).  Idempotent; ``step()`` raises afterwards."""
         if self.closed:
             return
@@ -1299,12 +1353,10 @@ class GraphedStep:
             self.reducer.wait()
         torch.cuda.synchronize()
         for g, _, _ in reversed(self.graphs or []):
-            if g is not None:
-                g.reset()
+            g.reset()
         self.graphs = None
-        self._tail = None
-        self._opt_done = None
-        self.side = self.ddp_fence = self.ddp_side = self.ddp_wside = None
+        self.units = self.groups = self.buckets = None
+        self.side = self.ddp_fence = self.ddp_side = None
         self.plan = None
 
     def __enter__(self):
@@ -1313,162 +1365,138 @@ class GraphedStep:
     def __exit__(self, *exc):
         self.close()
 
-    # ---- pieces ------------------------------------------------------------------------------------------
-    def _pieces(self):
-        p = self.plan
-        def fwd(stream):
-            if self.side is None:
-                p.fwd.run(stream)
-            else:
-                p.fwd.run2(torch.cuda.current_stream(), None, {})
-            p.loss.run(stream)
-        pieces = [("fwd", fwd, None)]
-        if self.side is None and not self.ddp_stream:
-            # data parallel: `ddp_group` consecutive layer segments share one hipGraph and one all-reduce bucket (their
-            # gradient ranges are adjacent in the flat buffer): fewer graph boundaries, larger RCCL messages
-            # (measured on a 1-rank RCCL group: 11.21 ms/step with one graph per layer, 10.99 in pairs, 10.97 in threes).
-            # The last two layers keep their own buckets, so the all-reduce left exposed after the backward stays small.
-            group = max(1, int(os.environ.get("MEMEHIP_DDP_GROUP", "2")))
-            n_layer_segs = sum(1 for sg in p.bwd if sg.name.startswith("bwd_layer_"))
-            seen = 0
-            pend = []
-
-            def flush():
-                if not pend:
-                    return
-                segs = list(pend)
-                pend.clear()
-                rngs = [p.bucket_after[sg.name] for sg in segs if p.bucket_after.get(sg.name) is not None]
-                rng = (min(r[0] for r in rngs), max(r[1] for r in rngs)) if rngs else None
-
-                def run(stream, segs=segs):
-                    if self.ddp_wside is None or len(segs) < 2:
-                        for sg in segs:
-                            sg.run(stream)
-                        return
-                    # inside a pair the first layer's weight-gradient GEMMs run on a side stream beside the second layer's
-                    # chain (the buffers they read belong to the other layer parity); everything is joined at the end of
-                    # the graph, before the pair's gradient slice goes to the all-reduce
-                    main, events = torch.cuda.current_stream(), {}
-                    for sg in segs:
-                        sg.run2(main, self.ddp_wside, events)
-                    for ev in events.values():
-                        main.wait_event(ev)
-                pieces.append((segs[0].name, run, rng))
-
-            for seg in p.bwd:
-                if seg.name.startswith("bwd_layer_"):
-                    seen += 1
-                if seg.name.startswith("bwd_layer_") and group > 1 and seen <= n_layer_segs - 2:
-                    pend.append(seg)
-                    if len(pend) == group:
-                        flush()
-                    continue
-                flush()
-                if seg.name == "bwd_embed_tables":      # needs every rank's token ids + embedding-gradient rows first
-                    pieces.append(("gather", None, None))
-                pieces.append((seg.name, seg.run, p.bucket_after.get(seg.name)))
-            flush()
+    # ---- schedule ----------------------------------------------------------------------------------------
+    def _schedule(self):
+        """(units, groups).  Units hold plain functions of (step, stream), never bound methods: the step must not sit in a reference
+        cycle, or the model and optimizer it holds would live until the next cyclic collection.  groups = which units are
+        captured together, as (graph name, units, captured?): everything ("single", "graph"), the forward only ("stream"), every
+        DEVICE unit on its own ("segments": the collectives stay between graph launches)."""
+        S = GraphedStep
+        units = [Unit("fwd", S._forward, DEVICE)]
+        if self.mode == "segments":
+            for b in self.buckets:
+                if b.gather:
+                    units.append(Unit("gather", S._gather, HOST))
+                units.append(Unit(b.segs[0].name, partial(S._run_bucket, bucket=b), DEVICE))
+                if b.rng is not None:
+                    units.append(Unit("reduce", partial(S._reduce, bucket=b), REDUCE))
         else:
-            def bwd(stream):
-                main = torch.cuda.current_stream()
-                events = {}
-                done = []
-                red = self.reducer if self.ddp_stream else None
-                group = max(1, int(os.environ.get("MEMEHIP_DDP_GROUP", "2")))
-                n_layer_segs = sum(1 for sg in p.bwd if sg.name.startswith("bwd_layer_"))
-                pend, pend_ev, seen = [], [], 0
-
-                def flush():
-                    """all-reduce the union of the pending (adjacent) gradient ranges once everything that writes them has
-                    been issued: the fence stream waits for the main stream's position and the segments' weight-gradient
-                    events, the collective is enqueued behind the fence, the slice's Adam update behind the collective."""
-                    if not pend:
-                        return
-                    rng = (min(r[0] for r in pend), max(r[1] for r in pend))
-                    layer_rngs = list(pend)
-                    self.ddp_fence.wait_stream(main)
-                    for ev in pend_ev:
-                        self.ddp_fence.wait_event(ev)
-                    with torch.cuda.stream(self.ddp_fence):
-                        works = red.reduce_range(rng)
-                    if self.ddp_opt_in_bwd and pend_layer[0]:
-                        with torch.cuda.stream(self.ddp_side):
-                            for w in works:
-                                w.wait()
-                            for r in layer_rngs:
-                                self.opt.launch(only=r, guarded=True)
-                        done.extend(layer_rngs)
-                    pend.clear(); pend_ev.clear(); pend_layer[0] = True
-
-                pend_layer = [True]       # every pending range belongs to a layer segment (its Adam slice may run early)
-                for seg in p.bwd:
-                    if red is not None and seg.name == "bwd_embed_tables":      # needs every rank's ids + gradient rows first
-                        red.gather(p.gather)
-                    seg.run2(main, self.side if self.wgrad_side else None, events)
-                    rng = p.bucket_after.get(seg.name)
-                    is_layer = seg.name.startswith("bwd_layer_")
-                    if red is not None:
-                        if rng is not None:
-                            if is_layer:
-                                seen += 1
-                            pend.append(rng)
-                            pend_layer[0] = pend_layer[0] and is_layer
-                            if seg.name in events:
-                                pend_ev.append(events[seg.name])
-                            # the last two layers (and everything that is not a layer) go out on their own, so the
-                            # all-reduce left exposed after the backward stays small
-                            if (not is_layer) or len(pend) >= group or seen > n_layer_segs - 2:
-                                flush()
-                        continue
-                    if self.opt_in_bwd and is_layer and rng is not None:
-                        if seg.name not in events:      # weight gradients ran on the main stream: fork behind them
-                            e = torch.cuda.Event()
-                            e.record(main)
-                            self.side.wait_event(e)
-                        with torch.cuda.stream(self.side):
-                            self.opt.launch(only=rng, guarded=True)
-                        ev = torch.cuda.Event()
-                        ev.record(self.side)
-                        events[seg.name] = ev
-                        done.append(rng)
-                if red is not None:
-                    flush()
-                for ev in events.values():      # join before the optimizer reads the remaining gradients
-                    main.wait_event(ev)
-                self._opt_done = done
-            pieces.append(("bwd", bwd, None))
-        if self.ddp_opt_in_bwd and not self.ddp_stream:
-            self._opt_done = [p.bucket_after[seg.name] for seg in p.bwd
-                              if seg.name.startswith("bwd_layer_") and p.bucket_after.get(seg.name) is not None]
-        pieces.append(("opt", lambda stream: self.opt.launch(skip=getattr(self, "_opt_done", None),
-                                                             guarded=self.opt_in_bwd or self.ddp_opt_in_bwd), None))
-        return pieces
-
-    def _after_segment(self, name, rng):
-        """Data parallel: start the all-reduce of the gradient slice a segment completed and, behind it on the side
-        stream, that slice's Adam update."""
-        works = self.reducer.reduce_range(rng)
-        if self.ddp_opt_in_bwd and rng is not None and name.startswith("bwd_layer_"):
-            self.ddp_side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self.ddp_side):
-                for w in works:
-                    w.wait()
-                self.opt.launch(only=rng, guarded=True)
-
-    def _run_eager(self):
-        stream = torch.cuda.current_stream().cuda_stream
-        for name, fn, rng in self._pieces():
-            if name == "gather":
-                self.reducer.gather(self.plan.gather)
-                continue
-            if name == "opt" and self.reducer is not None:
-                self.reducer.wait()
-            fn(stream)
-            if self.reducer is not None and not self.ddp_stream:
-                self._after_segment(name, rng)
+            units.append(Unit("bwd", S._backward, DEVICE))
+        if self.reducer is not None:
+            units.append(Unit("wait", S._wait, REDUCE))         # every all-reduce is ordered in front of the tail, which reads all gradients
+        units.append(Unit("opt", S._opt_tail, DEVICE))
         if self.ddp_side is not None:
-            torch.cuda.current_stream().wait_stream(self.ddp_side)
+            units.append(Unit("join", S._join, REDUCE))
+        if self.mode == "segments":
+            groups = [(u.name, [u], u.kind == DEVICE) for u in units]
+        elif self.mode == "stream":
+            groups = [("fwd", units[:1], True), ("bwd", units[1:], False)]
+        else:
+            groups = [("step", units, True)]
+        return units, groups
+
+    def _issue(self, units):
+        """THE driver: the eager step, the warm-up, every capture and whatever a replay does not find in a graph go through here."""
+        stream = torch.cuda.current_stream().cuda_stream
+        for unit in units:
+            unit.fn(self, stream)
+
+    def _forward(self, stream):
+        self.plan.fwd.run(stream)
+        self.plan.loss.run(stream)
+
+    def _gather(self, stream):
+        self.reducer.gather(self.plan.gather)
+
+    def _wait(self, stream):
+        self.reducer.wait()
+
+    def _join(self, stream):
+        torch.cuda.current_stream().wait_stream(self.ddp_side)
+
+    def _opt_tail(self, stream):
+        self.opt.launch(skip=self.early, guarded=self.opt_in_bwd or self.ddp_opt_in_bwd)
+
+    def _run_bucket(self, stream, bucket):
+        """"segments": the launches of one bucket, i.e. of one hipGraph."""
+        if self.side is None or len(bucket.segs) < 2:
+            for sg in bucket.segs:
+                sg.run(stream)
+            return
+        # inside a pair the first layer's weight-gradient GEMMs run on a side stream beside the second layer's
+        # chain (the buffers they read belong to the other layer parity); everything is joined at the end of
+        # the graph, before the pair's gradient slice goes to the all-reduce
+        main, events = torch.cuda.current_stream(), {}
+        for sg in bucket.segs:
+            sg.run2(main, self.side, events)
+        for ev in events.values():
+            main.wait_event(ev)
+
+    def _backward(self, stream):
+        """"single", "stream", "graph": the whole backward as one two-stream schedule over the buckets."""
+        main, events = torch.cuda.current_stream(), {}
+        wside = self.side if self.wgrad_side else None
+        for b in self.buckets:
+            if b.gather:
+                self.reducer.gather(self.plan.gather)
+            wgrads = []         # the weight-gradient events of this bucket, taken before a later segment's wait() pops them
+            for sg in b.segs:
+                sg.run2(main, wside, events)
+                if sg.name in events:
+                    wgrads.append(events[sg.name])
+            if b.rng is not None:
+                self._bucket_complete(b, main, events, wgrads)
+        for ev in events.values():      # join before the optimizer reads the remaining gradients
+            main.wait_event(ev)
+
+    def _bucket_complete(self, b, main, events, wgrads):
+        """Everything that writes the gradient range of bucket `b` has been issued.  Three outcomes:
+        data parallel -- the fence stream waits for the main stream's position and the bucket's weight-gradient events, and the
+        all-reduce (with the Adam slices behind it, `_reduce`) is enqueued behind the fence;
+        single GPU with the optimizer overlap -- the Adam slice of a layer follows its weight gradients on the side stream;
+        otherwise (overlap off, clipping, "strict") -- nothing: the tail updates everything."""
+        if self.mode != "single":
+            self.ddp_fence.wait_stream(main)
+            for ev in wgrads:
+                self.ddp_fence.wait_event(ev)
+            self._reduce(None, b)
+        elif self.opt_in_bwd and b.layers:
+            name = b.segs[-1].name
+            if name not in events:      # weight gradients ran on the main stream: fork behind them
+                e = torch.cuda.Event()
+                e.record(main)
+                self.side.wait_event(e)
+            with torch.cuda.stream(self.side):
+                self.opt.launch(only=b.rng, guarded=True)
+            ev = torch.cuda.Event()
+            ev.record(self.side)
+            events[name] = ev           # replaces the weight-gradient event on purpose: wait("bwd_layer_{l+2}") then waits for the update too
+
+    def _reduce(self, stream, bucket):
+        """Data parallel: start the all-reduce of the gradient range `bucket` completed and, behind it on `ddp_side`, that
+        range's Adam update.  "segments" calls it between two graph launches, "stream" / "graph" from `_bucket_complete`."""
+        segments = self.mode == "segments"
+        if segments:
+            works = self.reducer.reduce_range(bucket.rng)
+        else:
+            with torch.cuda.stream(self.ddp_fence):
+                works = self.reducer.reduce_range(bucket.rng)
+        if not (self.ddp_opt_in_bwd and bucket.layers):
+            return
+        if segments:
+            # the graph boundary has joined every stream into the current one, so this one edge orders `ddp_side` behind all
+            # writers of the range.  "stream" / "graph" have no such point (the writers are the main stream AND the side
+            # stream's weight gradients, gathered by the fence): there the work handles alone carry the order, and one more
+            # edge would be one more node dependency in the captured graph.
+            self.ddp_side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.ddp_side):
+            for w in works:
+                w.wait()
+            # "segments" updates the bucket's range in ONE guarded launch, "stream" / "graph" in one per layer: every guarded
+            # launch takes an ordinal (Adam._next_ordinal) that is part of the result on an overflowing step, and the launches
+            # are nodes of the captured graph -- each mode keeps the sequence it has been tested bit for bit with
+            for r in ((bucket.rng,) if segments else bucket.rngs):
+                self.opt.launch(only=r, guarded=True)
 
     def load_batch(self, text, image, mask, labels):
         b = self.plan.buf
@@ -1492,109 +1520,61 @@ class GraphedStep:
         self.model._advance_rng(self.plan)
         self.model._get_engine().before_backward(self.plan)
         if not self.use_graph:
-            self._run_eager()
+            self._issue(self.units)
         else:
             if self.graphs is None:
                 self._capture()
-            if self.ddp_graph:        # everything, the collectives included, is one graph
-                self.graphs[0][0].replay()
-                self.reducer.reduced_elems += self._per_replay[0]
-                self.reducer.wire_bytes += self._per_replay[1]
-                return self.plan.buf["loss"], self.plan.buf["ncorrect"]
-            if self.ddp_stream:       # forward graph, then the backward + optimizer as stream-ordered eager launches
-                self.graphs[0][0].replay()
-                stream = torch.cuda.current_stream().cuda_stream
-                for name, fn, rng in self._tail:
-                    if name == "opt":
-                        self.reducer.wait()
-                    fn(stream)
-                if self.ddp_side is not None:
-                    torch.cuda.current_stream().wait_stream(self.ddp_side)
-                return self.plan.buf["loss"], self.plan.buf["ncorrect"]
-            for g, name, rng in self.graphs:
-                if name == "gather":
-                    self.reducer.gather(self.plan.gather)
+            graphs = iter(self.graphs)
+            for _, units, captured in self.groups:
+                if not captured:
+                    self._issue(units)
                     continue
-                if name == "opt" and self.reducer is not None:
-                    self.reducer.wait()
+                g, _, counted = next(graphs)
                 g.replay()
-                if self.reducer is not None:
-                    self._after_segment(name, rng)
-            if self.ddp_side is not None:
-                torch.cuda.current_stream().wait_stream(self.ddp_side)
+                if counted is not None:       # the host-side counters of the collectives inside the graph ("graph" mode)
+                    self.reducer.reduced_elems += counted[0]
+                    self.reducer.wire_bytes += counted[1]
         return self.plan.buf["loss"], self.plan.buf["ncorrect"]
 
     def _capture(self):
         # one warm-up run on a side stream (lazy module loads, workspace allocation), undone afterwards so
         # it does not count as a training step; then capture the same launches
         f = self.opt._flat
+        red = self.reducer
         snap = (f["P"].clone(), f["M"].clone(), f["V"].clone())
         acct = [f["skip_state"], f["overflow"]] + list(f["hyper"])        # the warm-up's accounting launch must not count as a step
         if self.opt._scaler is not None and self.opt._scaler._scale is not None:
             acct += [self.opt._scaler._scale, self.opt._scaler._growth]
         acct_snap = [t.clone() for t in acct]
-        counters = (self.reducer.reduced_elems, self.reducer.wire_bytes) if self.reducer is not None else None
+        counters = (red.reduced_elems, red.wire_bytes) if red is not None else None
+        # "segments" rehearses what it captures (and the gather that feeds it); its all-reduces and the Adam slices behind them
+        # are ordinary launches between the graphs and start with the first real step
+        warm = [u for u in self.units if u.kind != REDUCE] if self.mode == "segments" else self.units
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            stream = s.cuda_stream
-            for name, fn, rng in self._pieces():
-                if name == "gather":
-                    self.reducer.gather(self.plan.gather)
-                else:
-                    if name == "opt" and self.ddp_stream:
-                        self.reducer.wait()
-                    fn(stream)
-            if self.ddp_side is not None and self.ddp_stream:
-                s.wait_stream(self.ddp_side)
+            self._issue(warm)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         f["P"].copy_(snap[0]); f["M"].copy_(snap[1]); f["V"].copy_(snap[2])
         for t, c in zip(acct, acct_snap):
             t.copy_(c)
         if counters is not None:      # (the stream schedule's warm-up ran the collectives for real)
-            self.reducer.reduced_elems, self.reducer.wire_bytes = counters
+            red.reduced_elems, red.wire_bytes = counters
         self.model.refresh_shadow()
         # (the warm-up left prev_ids == ids, so the first real step re-zeroes exactly the embedding-gradient
         #  rows the warm-up wrote)
-        pieces = self._pieces()
-        graphs = []
-        if self.ddp_graph:
-            e0, w0 = self.reducer.reduced_elems, self.reducer.wire_bytes
+        graphs, pool = [], None
+        for name, units, captured in self.groups:
+            if not captured:
+                continue
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-                stream = torch.cuda.current_stream().cuda_stream
-                for name, fn, rng in pieces:
-                    if name == "opt":
-                        self.reducer.wait()
-                    fn(stream)
-                if self.ddp_side is not None:
-                    torch.cuda.current_stream().wait_stream(self.ddp_side)
-            graphs.append((g, "step", None))
-            self._per_replay = (self.reducer.reduced_elems - e0, self.reducer.wire_bytes - w0)      # the host-side counters of one step
-            self.reducer.reduced_elems, self.reducer.wire_bytes = e0, w0
-        elif self.ddp_stream:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-                pieces[0][1](torch.cuda.current_stream().cuda_stream)
-            graphs.append((g, "fwd", None))
-            self._tail = pieces[1:]
-        elif self.reducer is None:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-                stream = torch.cuda.current_stream().cuda_stream
-                for name, fn, rng in pieces:
-                    fn(stream)
-            graphs.append((g, "step", None))
-        else:
-            pool = None
-            for name, fn, rng in pieces:
-                if name == "gather":
-                    graphs.append((None, "gather", None))
-                    continue
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool, capture_error_mode=CAPTURE_MODE):
-                    fn(torch.cuda.current_stream().cuda_stream)
-                pool = g.pool()
-                graphs.append((g, name, rng))
+            with torch.cuda.graph(g, pool=pool, capture_error_mode=CAPTURE_MODE):
+                self._issue(units)
+            pool = g.pool()         # the graphs of one step share ONE private memory pool
+            counted = None
+            if red is not None:     # collectives issued under capture counted on the host once; every replay counts them again
+                counted = (red.reduced_elems - counters[0], red.wire_bytes - counters[1])
+                red.reduced_elems, red.wire_bytes = counters
+            graphs.append((g, name, counted))
         self.graphs = graphs

@@ -331,3 +331,36 @@ def test_hue_and_rotation_restatements_are_bit_exact_against_pil():
         for ang in (3.7, -14.99, 11.25, 0.31, -7.0, 15.0, -15.0, 45.0, 123.4):
             assert np.array_equal(rotate(a, pil_rotate_fixed_coeffs(ang, w, h)), np.asarray(E.rotate_pil(im, ang))), (h, w, ang)
     assert pil_rotate_fixed_coeffs(0.0, 10, 10) is None and pil_rotate_fixed_coeffs(360.0, 10, 10) is None
+
+
+def test_gradient_bucket_rule():
+    """The one bucket rule of the data-parallel schedules: layer segments in groups, the last two layers and
+    every segment that is not a layer on their own, a left-over layer on its own; ranges are unions of adjacent segment ranges."""
+    from types import SimpleNamespace
+    from multimodal_propaganda_meme_classification_amd.model import gradient_buckets
+
+    def plan(n_layers):
+        names = ["bwd_head"] + [f"bwd_layer_{l}" for l in range(n_layers - 1, -1, -1)] + ["bwd_embed", "bwd_embed_tables"]
+        after = {f"bwd_layer_{l}": (100 * l, 100 * l + 100) for l in range(n_layers)}
+        after["bwd_embed"] = (100 * n_layers, 100 * n_layers + 7)
+        return [SimpleNamespace(name=n) for n in names], after
+
+    def names(buckets):
+        return [[sg.name.replace("bwd_layer_", "L") for sg in b.segs] for b in buckets]
+
+    bwd, after = plan(5)
+    b5 = gradient_buckets(bwd, after, 2)
+    assert names(b5) == [["bwd_head"], ["L4", "L3"], ["L2"], ["L1"], ["L0"], ["bwd_embed"], ["bwd_embed_tables"]]
+    assert [b.rng for b in b5] == [None, (300, 500), (200, 300), (100, 200), (0, 100), (500, 507), None]
+    assert b5[1].rngs == ((400, 500), (300, 400))
+    assert [b.layers for b in b5] == [False, True, True, True, True, False, False]
+    assert [b.gather for b in b5] == [False] * 6 + [True]
+    bwd, after = plan(4)
+    assert names(gradient_buckets(bwd, after, 2))[1:5] == [["L3", "L2"], ["L1"], ["L0"], ["bwd_embed"]]
+    assert names(gradient_buckets(bwd, after, 3))[1:4] == [["L3", "L2"], ["L1"], ["L0"]]
+    assert all(len(b.segs) == 1 for b in gradient_buckets(bwd, after, 1))            # what a single GPU uses
+    bwd, after = plan(12)
+    assert [len(b.segs) for b in gradient_buckets(bwd, after, 2)] == [1, 2, 2, 2, 2, 2, 1, 1, 1, 1]
+    assert [len(b.segs) for b in gradient_buckets(bwd, after, 3)] == [1, 3, 3, 3, 1, 1, 1, 1, 1]
+    bwd, after = plan(1)
+    assert names(gradient_buckets(bwd, after, 2)) == [["bwd_head"], ["L0"], ["bwd_embed"], ["bwd_embed_tables"]]
