@@ -549,12 +549,6 @@ int geom_check(const MhConvGeom* g, int& Ho, int& Wo) {
 extern "C" int mh_conv_splitk(const MhConvGeom* g, int dgrad) {
     int Ho, Wo;
     if (geom_check(g, Ho, Wo) != MH_OK) return 1;
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("MEMEHIP_CONV_SPLITK");
-        on = (e && atoi(e) == 0) ? 0 : 1;
-    }
-    if (!on) return 1;
     if (dgrad && g->stride != 1) return 1;      // (the parity-class problems of a strided input gradient are launched together: never split)
     const int M = dgrad ? g->B * g->H * g->W : g->B * Ho * Wo, N = dgrad ? g->C : g->Cout;
     const int K = dgrad ? g->KH * g->KW * g->Cout : g->ldk;

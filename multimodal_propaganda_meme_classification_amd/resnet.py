@@ -11,8 +11,9 @@ submodules only HOLD the parameters and running statistics; the arithmetic runs 
 * train-mode BatchNorm2d with per-replica batch statistics (the reference uses plain BN): the statistics come from
   the convolution epilogue's per-tile column sums (``mh_bn2d_fwd_parts``: no pass over the activation), the normalisation is
   fused with the residual add and the ReLU; max pool, global average pool, the 2048 -> 1000 classifier in exact f32;
-* the backward is one opaque autograd node (``mh_conv_wgrad``, ``mh_conv_dgrad`` -- the six strided convolutions keep the
-  dgrad GEMM + ``mh_col2im_nhwc`` --, BatchNorm backward);
+* the backward is one opaque autograd node over a typed tape (``Tape``): ``mh_conv_wgrad``, the input gradient by the route
+  ``dgrad_route`` names (``mh_conv_dgrad``; the strided 1x1 downsamples keep the dgrad GEMM + ``mh_col2im_nhwc``), BatchNorm
+  backward; ``ResNet50.options`` (``TowerOptions``) holds its A/B switches;
 * the 16-bit gradient stream carries ``grad_stream_scale`` (8192 for fp16), removed where parameter gradients are produced.
 
 ``ResNetClassifier`` is the Subtask-2B surface (ResNet_example_task2B.py:206-221): ``model(pixel_values=..., labels=...)``
@@ -20,7 +21,7 @@ returns ``(loss, logits)`` for HF Trainer.
 """
 from __future__ import annotations
 
-import os
+from dataclasses import dataclass
 from typing import List, Optional
 
 import torch
@@ -31,6 +32,36 @@ from ._lib import check
 from .model import CrossEntropyLoss
 
 F32 = torch.float32
+WGRAD_TILES = 256      # split-K tile target of an ungrouped weight gradient (512 / 384 / 256 / 192: 7.78 / 7.74 / 7.74 / 7.72 ms per step; 256 halves the slabs)
+GEMM, IMPLICIT, COL2IM = "gemm", "implicit", "gemm + col2im"      # the input-gradient routes
+
+
+@dataclass(frozen=True)
+class TowerOptions:
+    """A/B switches of the tower's backward (``ResNet50.options``); every default is the measured winner."""
+    bn_bwd_fuse: bool = True         # a BatchNorm backward's ReLU mask + statistics in the epilogue of the dgrad that produces its dy
+    block_out_fuse: bool = True      # ... and, for a block's bn3, the residual merge too, in the conv1 epilogue of the block above (needs bn_bwd_fuse)
+    strided_dgrad: bool = True       # 3x3 / 2 input gradient as four parity classes of mh_conv_dgrad (off: GEMM + col2im)
+    # weight gradients launched together (1: one launch each), clamped to MH_CONV_MAX_GROUP.  6 since the conv kernels deal every problem's
+    wgrad_group: int = 6             # tiles to all eight XCDs (round 4, second session: 6.29 -> 6.24 ms; with one run over the concatenated tile list 4 was the best)
+
+
+def dgrad_route(cv, H, W, opts: TowerOptions) -> str:
+    """The input-gradient route of `cv` (a _Conv: geometry only) on an H x W input.  GEMM: a 1x1 / stride 1 is the plain GEMM.
+    IMPLICIT: mh_conv_dgrad -- stride 1, or k x k (k > 1) / stride 2 on an even image as four parity-class problems in one launch
+    (3 layers of ResNet-50; round 4).  COL2IM: dgrad GEMM into a per-tap panel + mh_col2im_nhwc (the 3 strided 1x1 downsamples)."""
+    if cv.direct and cv.cout % 64:
+        return GEMM
+    parity = cv.stride == 2 and cv.kh > 1 and H % 2 == 0 and W % 2 == 0 and opts.strided_dgrad
+    if (cv.stride == 1 or parity) and cv.kh == cv.kw and cv.cout % 64 == 0:
+        return IMPLICIT
+    return COL2IM
+
+
+def epilogue_takes_bn(cv, H, W, opts: TowerOptions, block_out: bool = False) -> bool:
+    """Whether cv's dgrad epilogue does the backward masking + statistics of the BatchNorm (+ReLU) that produced cv's input (only
+    the implicit route has that epilogue); `block_out`: cv is a block's conv1, the BatchNorm the bn3 + residual of the block below."""
+    return opts.bn_bwd_fuse and (opts.block_out_fuse or not block_out) and dgrad_route(cv, H, W, opts) == IMPLICIT
 
 
 def _stream():
@@ -41,12 +72,21 @@ def _grad_target(p: nn.Parameter, grads: dict):
     """Where a parameter's gradient is written: straight into an existing f32 .grad (accumulated by the kernel; autograd gets
     None for it -- no add launch per parameter), or a fresh tensor handed to autograd."""
     g = p.grad
-    if g is not None and g.dtype == F32 and g.is_contiguous() and g.device == p.device:
-        grads[id(p)] = None
-        return g, True
-    g = torch.empty_like(p)
-    grads[id(p)] = g
-    return g, False
+    acc = g is not None and g.dtype == F32 and g.is_contiguous() and g.device == p.device
+    g = g if acc else torch.empty_like(p)
+    grads[id(p)] = None if acc else g
+    return g, acc
+
+
+def _bn_epilogue(below, part, addend=None, y_mask=None):
+    """The MhConvBnBwd of a dgrad whose dx is the dy of the BatchNorm (+ReLU) of tape record `below`: mask it, leave its two backward sums per tile
+    in `part`.  `addend`: a gradient added before the mask; `y_mask`: the stored output whose sign is the mask (else recomputed from z)."""
+    f, m = _lib.MhConvBnBwd(), below.bn.mod
+    f.z, f.mean, f.rstd = below.z.data_ptr(), below.mean.data_ptr(), below.rstd.data_ptr()
+    f.gamma, f.beta, f.part, f.relu = m.weight.data_ptr(), m.bias.data_ptr(), part.data_ptr(), int(below.relu)
+    f.addend = None if addend is None else addend.data_ptr()
+    f.y_mask = None if y_mask is None else y_mask.data_ptr()
+    return f
 
 
 class _Conv:
@@ -90,69 +130,43 @@ class _Conv:
         want = max(1, min(64, -(-target // tiles), M // 256))
         return max(1, lib.mh_gemm_ksplit_for(int(M), int(want)))
 
-    def _wgrad(self, lib, dy, x, B, H, W, Ho, Wo, gscale):
-        M = B * Ho * Wo
-        sp = self._wgrad_split(lib, M, int(os.environ.get("MEMEHIP_WGRAD_TILES", 256)))      # (512 / 384 / 256 / 192: 7.78 / 7.74 / 7.74 / 7.72 ms per step; 256 halves the slabs)
-        slabs = torch.empty((sp, self.cout, self.ldk), dtype=F32, device=dy.device)
-        check(lib.mh_conv_wgrad(dy.data_ptr(), x.data_ptr(), slabs.data_ptr(), sp, 1.0 / gscale, self.geom(B, H, W), _stream()),
-              "mh_conv_wgrad")
-        return slabs, sp
-
-    def backward(self, lib, dy, x, wk, B, H, W, Ho, Wo, gscale, wjobs, need_dx=True, side=None, wq=None, bnb=None):
-        """dy [M, cout] 16-bit -> dx [B*H*W, cp] 16-bit (or None); the weight gradient's split-K slabs are queued in `wjobs`
-        (summed, un-packed and added to .grad for all convolutions at once at the end of the backward).  With `side`, the
-        weight-gradient kernel -- which nothing later in the backward chain reads -- runs on that stream beside the input-gradient
-        chain of the layers below (the operands are kept alive in `wjobs` until the streams join).
-        Weight gradient: implicit GEMM over x (mh_conv_wgrad).  Input gradient: stride 1 -> mh_conv_dgrad (1x1: the plain GEMM,
-        which is the same thing); 3x3 / stride 2 -> mh_conv_dgrad as four parity-class problems in one launch (3 layers of ResNet-50);
-        1x1 / stride 2 (the 3 downsampling convolutions) -> dgrad GEMM into a per-tap panel + mh_col2im_nhwc."""
-        M = B * Ho * Wo
-        dev = dy.device
-        if side is not None:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                slabs, sp = self._wgrad(lib, dy, x, B, H, W, Ho, Wo, gscale)
-        elif wq is not None:      # deferred: consecutive layers' weight gradients go out together (flush_wgrads)
+    def backward(self, lib, dy, x, wk, B, H, W, Ho, Wo, gscale, wjobs, opts, need_dx=True, wq=None, below=None, addend=None):
+        """dy [M, cout] 16-bit -> (dx [B*H*W, cp] 16-bit or None, the statistics partials of `below` or None).  The weight gradient
+        (implicit GEMM over x, mh_conv_wgrad) is deferred into `wq` (flush_wgrads) or launched here; its split-K slabs are queued in
+        `wjobs` (summed, un-packed and added to .grad for all convolutions at once at the end of the backward).  The input gradient
+        goes by dgrad_route.  `below` (implicit route only: epilogue_takes_bn): the tape record whose BatchNorm (+ReLU) produced x
+        -- the epilogue masks dx for it and sums its statistics, after adding `addend` and by the sign of below.y if that is given."""
+        M, dev = B * Ho * Wo, dy.device
+        if wq is not None:
             wq.append((self, dy, x, B, H, W, Ho, Wo))
-            slabs = None
         else:
-            slabs, sp = self._wgrad(lib, dy, x, B, H, W, Ho, Wo, gscale)
-        if slabs is not None:
+            sp = self._wgrad_split(lib, M, WGRAD_TILES)
+            slabs = torch.empty((sp, self.cout, self.ldk), dtype=F32, device=dev)
+            check(lib.mh_conv_wgrad(dy.data_ptr(), x.data_ptr(), slabs.data_ptr(), sp, 1.0 / gscale, self.geom(B, H, W), _stream()), "mh_conv_wgrad")
             wjobs.append((self, slabs, sp, dy, x))
         if not need_dx:
             return None, None
-        if self.direct and self.cout % 64:
-            dx = torch.empty((M, self.cp), dtype=dy.dtype, device=dev)
-            ops.gemm_grouped([ops.Gemm(dy, wk, dx, M, self.ldk, self.cout, self.cout, self.ldk, self.ldk)], False, True)
-            return dx, None
+        route = dgrad_route(self, H, W, opts)
+        if below is not None and route != IMPLICIT:
+            raise _lib.MemehipError(f"the {route} input gradient has no BatchNorm epilogue")
         dx = torch.empty((B * H * W, self.cp), dtype=dy.dtype, device=dev)
-        # stride 2, k x k (k > 1) on an even image: the four parity classes of input pixels as one grouped implicit launch (round 4)
-        strided_implicit = (self.stride == 2 and self.kh > 1 and H % 2 == 0 and W % 2 == 0 and
-                            os.environ.get("MEMEHIP_STRIDED_DGRAD", "1") != "0")
-        if (self.stride == 1 or strided_implicit) and self.kh == self.kw and self.cout % 64 == 0:
+        if route == IMPLICIT:
             geom = self.geom(B, H, W)
             sp = int(lib.mh_conv_splitk(geom, 1))
             ws = torch.empty((sp, B * H * W, self.cp), dtype=F32, device=dev) if sp > 1 else None
             fuse, part = None, None
-            if bnb is not None:      # dx is the dy of the BatchNorm (+ReLU) that produced x: mask it and sum its statistics right here
-                z_prev, bn_mod, sm_prev, sr_prev, relu_prev = bnb[:5]
-                addend, y_mask = (bnb[5], bnb[6]) if len(bnb) > 5 else (None, None)
+            if below is not None:
                 nblk = (B * H * W + 127) // 128 if self.stride == 1 else 4 * ((B * (H // 2) * (W // 2) + 127) // 128)
                 part = torch.empty((2, self.cp, nblk), dtype=F32, device=dev)
-                fuse = _lib.MhConvBnBwd()
-                fuse.z, fuse.mean, fuse.rstd = z_prev.data_ptr(), sm_prev.data_ptr(), sr_prev.data_ptr()
-                fuse.gamma, fuse.beta, fuse.part, fuse.relu = bn_mod.weight.data_ptr(), bn_mod.bias.data_ptr(), part.data_ptr(), int(relu_prev)
-                fuse.addend = None if addend is None else addend.data_ptr()
-                fuse.y_mask = None if y_mask is None else y_mask.data_ptr()
+                fuse = _bn_epilogue(below, part, addend=addend, y_mask=None if addend is None else below.y)
             check(lib.mh_conv_dgrad(dy.data_ptr(), wk.data_ptr(), dx.data_ptr(), None if ws is None else ws.data_ptr(), geom, fuse, _stream()),
                   "mh_conv_dgrad")
             return dx, part
-        dA = torch.empty((M, self.ldk), dtype=dy.dtype, device=dev)
+        dA = dx if route == GEMM else torch.empty((M, self.ldk), dtype=dy.dtype, device=dev)      # (GEMM: ldk == cp, the panel IS dx)
         ops.gemm_grouped([ops.Gemm(dy, wk, dA, M, self.ldk, self.cout, self.cout, self.ldk, self.ldk)], False, True)
-        check(lib.mh_col2im_nhwc(dA.data_ptr(), dx.data_ptr(), B, H, W, self.cp, self.kh, self.kw, self.stride, self.pad, self.ldk,
-                                 _stream()), "mh_col2im_nhwc")
+        if route == COL2IM:
+            check(lib.mh_col2im_nhwc(dA.data_ptr(), dx.data_ptr(), B, H, W, self.cp, self.kh, self.kw, self.stride, self.pad, self.ldk,
+                                     _stream()), "mh_col2im_nhwc")
         return dx, None
 
 
@@ -188,52 +202,98 @@ class _BN:
         m = self.mod
         y = torch.empty_like(x)
         sm, sr = torch.empty(self.C, dtype=F32, device=x.device), torch.empty(self.C, dtype=F32, device=x.device)
+        res, momentum = None if residual is None else residual.data_ptr(), float(m.momentum if m.momentum is not None else 0.1)
         if training and part is not None:      # batch statistics from the convolution epilogue's per-tile sums: no pass over x
             check(lib.mh_bn2d_fwd_parts(x.data_ptr(), part.data_ptr(), part.shape[2], m.weight.data_ptr(), m.bias.data_ptr(),
-                                        m.running_mean.data_ptr(), m.running_var.data_ptr(), None if residual is None else residual.data_ptr(),
-                                        y.data_ptr(), sm.data_ptr(), sr.data_ptr(), M, self.C, float(m.eps),
-                                        float(m.momentum if m.momentum is not None else 0.1), int(relu), _stream()), "mh_bn2d_fwd_parts")
+                                        m.running_mean.data_ptr(), m.running_var.data_ptr(), res, y.data_ptr(), sm.data_ptr(), sr.data_ptr(),
+                                        M, self.C, float(m.eps), momentum, int(relu), _stream()), "mh_bn2d_fwd_parts")
             return y, sm, sr
         ws = self._ws(M, x.device)
         check(lib.mh_bn2d_fwd(x.data_ptr(), m.weight.data_ptr(), m.bias.data_ptr(), m.running_mean.data_ptr(), m.running_var.data_ptr(),
-                              None if residual is None else residual.data_ptr(), y.data_ptr(), sm.data_ptr(), sr.data_ptr(),
-                              ws.data_ptr(), M, self.C, float(m.eps), float(m.momentum if m.momentum is not None else 0.1),
+                              res, y.data_ptr(), sm.data_ptr(), sr.data_ptr(), ws.data_ptr(), M, self.C, float(m.eps), momentum,
                               int(training), int(relu), _stream()), "mh_bn2d_fwd")
         return y, sm, sr
 
-    def backward(self, lib, dy, x, y, sm, sr, M, relu, want_dres, gscale, grads):
+    def _param_grad_targets(self, grads):
+        """(dgamma, dbeta, accumulate): where the two parameter gradients go (_grad_target), as one in-place / fresh decision"""
         m = self.mod
-        dx = torch.empty_like(x)
-        dres = torch.empty_like(x) if want_dres else None
         dg, acc_g = _grad_target(m.weight, grads)
         db, acc_b = _grad_target(m.bias, grads)
         if acc_g != acc_b:      # (one of the two has a usable .grad and the other does not: take the slow path for both)
             dg, db = torch.empty_like(m.weight), torch.empty_like(m.bias)
             grads[id(m.weight)], grads[id(m.bias)] = dg, db
             acc_g = False
+        return dg, db, acc_g
+
+    def backward(self, lib, dy, x, y, sm, sr, M, relu, want_dres, gscale, grads):
+        m = self.mod
+        dx = torch.empty_like(x)
+        dres = torch.empty_like(x) if want_dres else None
+        dg, db, acc = self._param_grad_targets(grads)
         ws = self._ws(M, x.device)
-        flags = (_lib.MH_BN_RELU if relu else 0) | (_lib.MH_BN_ACCUM_PARAM_GRADS if acc_g else 0)
+        flags = (_lib.MH_BN_RELU if relu else 0) | (_lib.MH_BN_ACCUM_PARAM_GRADS if acc else 0)
         check(lib.mh_bn2d_bwd(dy.data_ptr(), x.data_ptr(), None if y is None else y.data_ptr(), m.weight.data_ptr(), m.bias.data_ptr(), sm.data_ptr(),
                               sr.data_ptr(), dx.data_ptr(), None if dres is None else dres.data_ptr(), dg.data_ptr(), db.data_ptr(),
                               ws.data_ptr(), M, self.C, flags, 1.0 / gscale, _stream()), "mh_bn2d_bwd")
         return dx, dres
 
+    def backward_parts(self, lib, dy_masked, x, sm, sr, part, M, gscale, grads):
+        """BatchNorm2d backward when the producing dgrad epilogue already masked dy and summed its statistics (mh_conv_dgrad with `below`)."""
+        dx = torch.empty_like(x)
+        dg, db, acc = self._param_grad_targets(grads)
+        sums = torch.empty((2, self.C), dtype=F32, device=x.device)
+        check(lib.mh_bn2d_bwd_parts(dy_masked.data_ptr(), x.data_ptr(), part.data_ptr(), part.shape[2], self.mod.weight.data_ptr(), sm.data_ptr(),
+                                    sr.data_ptr(), dx.data_ptr(), dg.data_ptr(), db.data_ptr(), sums.data_ptr(), M, self.C,
+                                    _lib.MH_BN_ACCUM_PARAM_GRADS if acc else 0, 1.0 / gscale, _stream()), "mh_bn2d_bwd_parts")
+        return dx
 
-def _bn_backward_parts(bn, lib, dy_masked, x, sm, sr, part, M, gscale, grads):
-    """BatchNorm2d backward when the producing dgrad epilogue already masked dy and summed its statistics (mh_conv_dgrad with `bn`)."""
-    m = bn.mod
-    dx = torch.empty_like(x)
-    dg, acc_g = _grad_target(m.weight, grads)
-    db, acc_b = _grad_target(m.bias, grads)
-    if acc_g != acc_b:
-        dg, db = torch.empty_like(m.weight), torch.empty_like(m.bias)
-        grads[id(m.weight)], grads[id(m.bias)] = dg, db
-        acc_g = False
-    sums = torch.empty((2, bn.C), dtype=F32, device=x.device)
-    check(lib.mh_bn2d_bwd_parts(dy_masked.data_ptr(), x.data_ptr(), part.data_ptr(), part.shape[2], m.weight.data_ptr(), sm.data_ptr(),
-                                sr.data_ptr(), dx.data_ptr(), dg.data_ptr(), db.data_ptr(), sums.data_ptr(), M, bn.C,
-                                _lib.MH_BN_ACCUM_PARAM_GRADS if acc_g else 0, 1.0 / gscale, _stream()), "mh_bn2d_bwd_parts")
-    return dx
+
+@dataclass
+class ConvBnRec:
+    """One conv + BatchNorm (+ residual) (+ ReLU), y = act(bn(z = conv(x)) [+ residual]).  `conv` and `bn` alone: the layer's launch objects, built
+    once per model (ResNet50._units), shared by the forward, the weight pack and the backward; every field: what one forward left on the tape."""
+    conv: _Conv
+    bn: _BN
+    x: torch.Tensor = None         # [B*H*W, cp] 16-bit input
+    wk: torch.Tensor = None        # packed weight [cout, ldk]
+    z: torch.Tensor = None         # conv output = BatchNorm input [B*Ho*Wo, cout]
+    y: torch.Tensor = None
+    mean: torch.Tensor = None      # the statistics the forward normalised with
+    rstd: torch.Tensor = None
+    H: int = 0                     # input and output size
+    W: int = 0
+    Ho: int = 0
+    Wo: int = 0
+    relu: bool = True
+    has_res: bool = False          # a residual was added before the ReLU
+
+
+@dataclass
+class BlockRec:
+    """One bottleneck's four layers: ResNet50._block_units, and on the tape their records of one forward."""
+    conv1: ConvBnRec
+    conv2: ConvBnRec
+    conv3: ConvBnRec
+    downsample: Optional[ConvBnRec] = None
+
+
+@dataclass
+class PoolRec:
+    arg: torch.Tensor        # uint8 index of the maximum in its window
+    H: int
+    W: int
+    C: int
+
+
+@dataclass
+class Tape:
+    B: int
+    stem: ConvBnRec
+    pool: PoolRec
+    blocks: List[BlockRec]
+    pooled: torch.Tensor
+    last_hw: tuple
+    dtype: torch.dtype
 
 
 class Bottleneck(nn.Module):
@@ -248,9 +308,7 @@ class Bottleneck(nn.Module):
         self.bn2 = nn.BatchNorm2d(planes)
         self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * 4)
-        self.downsample = None
-        if downsample:
-            self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes * 4, 1, stride=stride, bias=False), nn.BatchNorm2d(planes * 4))
+        self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes * 4, 1, stride=stride, bias=False), nn.BatchNorm2d(planes * 4)) if downsample else None
         self.stride = stride
 
 
@@ -261,7 +319,7 @@ class _TowerFn(torch.autograd.Function):
     def forward(ctx, image, net, *params):
         ctx.net = net
         ctx.tape = net._forward_tape(image, training=net.training)
-        return ctx.tape["pooled"].clone()
+        return ctx.tape.pooled.clone()
 
     @staticmethod
     def backward(ctx, d_pooled):
@@ -272,15 +330,16 @@ class _TowerFn(torch.autograd.Function):
 
 class ResNet50(nn.Module):
     """torchvision ``resnet50`` topology and state_dict on the HIP kernels.  ``forward(image f32 [B,3,H,W]) -> logits [B,1000]``
-    (``num_classes`` outputs); ``features(image)`` returns the pooled 2048-d features."""
+    (``num_classes`` outputs); ``features(image)`` returns the pooled 2048-d features; ``options``: the backward's TowerOptions."""
 
     def __init__(self, num_classes: int = 1000, compute_dtype: str = "fp16", layers=(3, 4, 6, 3), width: int = 64,
-                 grad_stream_scale: float = 0.0, seed: int = 0):
+                 grad_stream_scale: float = 0.0, seed: int = 0, options: TowerOptions = TowerOptions()):
         super().__init__()
         if compute_dtype not in ("bf16", "fp16"):
             raise ValueError(f"compute_dtype must be 'bf16' or 'fp16', got {compute_dtype!r}")
         torch.manual_seed(seed)
         self.compute_dtype = compute_dtype
+        self.options = options
         self.gscale = float(grad_stream_scale) if grad_stream_scale else (8192.0 if compute_dtype == "fp16" else 1.0)
         self.conv1 = nn.Conv2d(3, width, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(width)
@@ -299,78 +358,61 @@ class ResNet50(nn.Module):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
         self._tower_params: List[nn.Parameter] = [p for n, p in self.named_parameters() if not n.startswith("fc.")]
 
+        def unit(conv, bn, cin_pad=None):
+            return ConvBnRec(_Conv(conv, cin_pad), _BN(bn))
+        self._stem_unit = unit(self.conv1, self.bn1, 8)
+        self._block_units = [BlockRec(unit(b.conv1, b.bn1), unit(b.conv2, b.bn2), unit(b.conv3, b.bn3),
+                                      None if b.downsample is None else unit(b.downsample[0], b.downsample[1]))
+                             for li in range(1, 5) for b in getattr(self, f"layer{li}")]
+        self._units = [self._stem_unit] + [u for b in self._block_units for u in (b.conv1, b.conv2, b.conv3, b.downsample) if u is not None]
+
     # ---- launches ----------------------------------------------------------------------------------------------
-    def _lib(self):
-        return _lib.load(self.compute_dtype)
-
-    def _blocks(self):
-        for li in range(1, 5):
-            for blk in getattr(self, f"layer{li}"):
-                yield blk
-
-    def _forward_tape(self, image: torch.Tensor, training: bool):
+    def _forward_tape(self, image: torch.Tensor, training: bool) -> Tape:
         if not image.is_cuda:
             raise _lib.MemehipError("ResNet50 runs on the HIP device only (no CPU fallback): move the batch with .to(device)")
-        lib = self._lib()
+        lib = _lib.load(self.compute_dtype)
         T16 = torch.float16 if self.compute_dtype == "fp16" else torch.bfloat16
         B, Cc, H, W = image.shape
         if Cc != 3:
             raise ValueError("ResNet50 expects 3-channel images")
-        tape = {"B": B, "ops": []}
         x = torch.empty((B * H * W, 8), dtype=T16, device=image.device)
         img32 = image.to(F32).contiguous()      # named: a temporary would be freed (and its block re-used) before the launch
         check(lib.mh_nchw_to_nhwc(img32.data_ptr(), x.data_ptr(), B, 3, H, W, 8, _stream()), "mh_nchw_to_nhwc")
-
         packed = self._pack_all_weights(lib, T16)
+        def conv_bn(u, xin, h, w, residual=None, relu=True) -> ConvBnRec:
+            wk = packed[id(u.conv.mod)]
+            z, part, ho, wo = u.conv.forward(lib, xin, B, h, w, T16, wk, want_stats=training)
+            y, sm, sr = u.bn.forward(lib, z, B * ho * wo, residual, relu, training, part)
+            return ConvBnRec(u.conv, u.bn, xin, wk, z, y, sm, sr, h, w, ho, wo, relu, residual is not None)
 
-        def conv_bn(conv_mod, bn_mod, xin, h, w, residual=None, relu=True, cin_pad=None):
-            cv, bn = _Conv(conv_mod, cin_pad), _BN(bn_mod)
-            wk = packed[id(conv_mod)]
-            z, part, ho, wo = cv.forward(lib, xin, B, h, w, T16, wk, want_stats=training)
-            M = B * ho * wo
-            y, sm, sr = bn.forward(lib, z, M, residual, relu, training, part)
-            tape["ops"].append(("conv_bn", cv, bn, xin, wk, z, y, sm, sr, h, w, ho, wo, relu, residual is not None))
-            return y, ho, wo
-
-        y, h, w = conv_bn(self.conv1, self.bn1, x, H, W, cin_pad=8)
+        stem = conv_bn(self._stem_unit, x, H, W)
         C1 = self.conv1.out_channels
-        ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-        p = torch.empty((B * ho * wo, C1), dtype=T16, device=image.device)
-        arg = torch.empty((B * ho * wo, C1), dtype=torch.uint8, device=image.device)
-        check(lib.mh_maxpool_fwd(y.data_ptr(), p.data_ptr(), arg.data_ptr(), B, h, w, C1, 3, 2, 1, _stream()), "mh_maxpool_fwd")
-        tape["ops"].append(("maxpool", arg, h, w, C1))
-        x, h, w = p, ho, wo
-        for blk in self._blocks():
-            tape["ops"].append(("block_begin",))
-            identity, ih, iw = x, h, w
-            o, h1, w1 = conv_bn(blk.conv1, blk.bn1, x, h, w)
-            o, h2, w2 = conv_bn(blk.conv2, blk.bn2, o, h1, w1)
-            if blk.downsample is not None:
-                identity, _, _ = conv_bn(blk.downsample[0], blk.downsample[1], x, ih, iw, relu=False)
-                tape["ops"].append(("branch_end",))
-            x, h, w = conv_bn(blk.conv3, blk.bn3, o, h2, w2, residual=identity, relu=True)
-            tape["ops"].append(("block_end", blk.downsample is not None))
-        Cf = self.feature_dim
-        pooled = torch.empty((B, Cf), dtype=F32, device=image.device)
-        check(lib.mh_avgpool_fwd(x.data_ptr(), pooled.data_ptr(), B, h * w, Cf, _stream()), "mh_avgpool_fwd")
-        tape.update(pooled=pooled, last_hw=(h, w), T16=T16)
+        h, w = (stem.Ho + 2 - 3) // 2 + 1, (stem.Wo + 2 - 3) // 2 + 1
+        x = torch.empty((B * h * w, C1), dtype=T16, device=image.device)
+        arg = torch.empty((B * h * w, C1), dtype=torch.uint8, device=image.device)
+        check(lib.mh_maxpool_fwd(stem.y.data_ptr(), x.data_ptr(), arg.data_ptr(), B, stem.Ho, stem.Wo, C1, 3, 2, 1, _stream()), "mh_maxpool_fwd")
+        blocks = []
+        for u in self._block_units:
+            c1 = conv_bn(u.conv1, x, h, w)
+            c2 = conv_bn(u.conv2, c1.y, c1.Ho, c1.Wo)
+            ds = None if u.downsample is None else conv_bn(u.downsample, x, h, w, relu=False)
+            c3 = conv_bn(u.conv3, c2.y, c2.Ho, c2.Wo, residual=x if ds is None else ds.y, relu=True)
+            blocks.append(BlockRec(c1, c2, c3, ds))
+            x, h, w = c3.y, c3.Ho, c3.Wo
+        pooled = torch.empty((B, self.feature_dim), dtype=F32, device=image.device)
+        check(lib.mh_avgpool_fwd(x.data_ptr(), pooled.data_ptr(), B, h * w, self.feature_dim, _stream()), "mh_avgpool_fwd")
         if training:      # nn.BatchNorm2d's step counter, all 53 of them in one multi-tensor launch
-            torch._foreach_add_([m.num_batches_tracked for m in self.modules() if isinstance(m, nn.BatchNorm2d)], 1)
-        return tape
+            torch._foreach_add_([u.bn.mod.num_batches_tracked for u in self._units], 1)
+        return Tape(B, stem, PoolRec(arg, stem.Ho, stem.Wo, C1), blocks, pooled, (h, w), T16)
 
     def _convs(self):
         """(conv module, input channels of its NHWC activation) in a fixed order"""
-        out = [(self.conv1, 8)]
-        for blk in self._blocks():
-            out += [(blk.conv1, None), (blk.conv2, None), (blk.conv3, None)]
-            if blk.downsample is not None:
-                out.append((blk.downsample[0], None))
-        return out
+        return [(u.conv.mod, u.conv.cp) for u in self._units]
 
     def _pack_all_weights(self, lib, T16):
         """f32 [Cout][Cin][kh][kw] -> 16-bit [Cout][(kh,kw,c)] for every convolution: one buffer, mh_conv_weight_pack_batched
         launches of <= 64 jobs."""
-        convs = [_Conv(m, cp) for m, cp in self._convs()]
+        convs = [u.conv for u in self._units]
         total = sum(c.cout * c.ldk for c in convs)
         buf = torch.empty(total, dtype=T16, device=self.conv1.weight.device)
         packed, off = {}, 0
@@ -386,103 +428,61 @@ class ResNet50(nn.Module):
             check(lib.mh_conv_weight_pack_batched(jobs, len(chunk), _stream()), "mh_conv_weight_pack_batched")
         return packed
 
-    def _backward_tape(self, tape, d_pooled: torch.Tensor):
-        lib = self._lib()
-        B, T16 = tape["B"], tape["T16"]
-        h, w = tape["last_hw"]
-        Cf = self.feature_dim
-        dev = d_pooled.device
+    def _backward_tape(self, tape: Tape, d_pooled: torch.Tensor):
+        lib, opts = _lib.load(self.compute_dtype), self.options
+        B, T16, (h, w), Cf, dev = tape.B, tape.dtype, tape.last_hw, self.feature_dim, d_pooled.device
         dx = torch.empty((B * h * w, Cf), dtype=T16, device=dev)
         dp32 = d_pooled.to(F32).contiguous()
         check(lib.mh_avgpool_bwd(dp32.data_ptr(), dx.data_ptr(), B, h * w, Cf, self.gscale, _stream()), "mh_avgpool_bwd")
-        ops_ = tape["ops"]
-        i = len(ops_) - 1
         grads = {}      # id(parameter) -> gradient tensor for autograd, or None when it was accumulated into .grad in place
         wjobs = []      # (conv, split-K slabs of its weight gradient, nsplit, operands kept alive): finished in one launch at the end
-        side = None      # (weight-gradient GEMMs on a second stream: measured SLOWER, 9.39 vs 8.76 ms/step -- 53 cross-stream edges of ~10 us for 26-us GEMMs)
+        group = max(1, min(opts.wgrad_group, _lib.MH_CONV_MAX_GROUP))
+        wq = [] if group > 1 else None
 
-        # weight gradients launched together (1: one launch each).  6 since the conv kernels deal every problem's tiles to all eight XCDs
-        # (round 4, second session: 6.29 -> 6.24 ms; with one run over the concatenated tile list 4 was the best)
-        group = int(os.environ.get("MEMEHIP_WGRAD_GROUP", "6"))
-        group = max(1, min(group, _lib.MH_CONV_MAX_GROUP))
-        wq = [] if (group > 1 and side is None) else None
-
-        fuse_on = os.environ.get("MEMEHIP_BN_BWD_FUSE", "1") != "0"
-
-        def conv_bn_bwd(op, dy, want_dres, need_dx=True, fuse_prev=None, pre_part=None, block_out=None):
-            """Backward of one conv + BatchNorm (+ReLU).  `pre_part`: dy arrives MASKED with its column sums already taken by the
-            dgrad epilogue that produced it; `fuse_prev`: the conv + BatchNorm whose output is this convolution's input -- when its
-            BatchNorm has a ReLU and no residual, this dgrad's epilogue does that BatchNorm's masking and statistics.
-            `block_out` = (op of the PREVIOUS block's conv3 + bn3, d_ident): this convolution is a block's conv1, its input the previous
-            block's output y = relu(bn3(z) + residual): the epilogue adds the gradient arriving through the other branch (d_ident),
-            masks by y > 0 and takes bn3's statistics -- no mh_add_h16 pass, no statistics pass for that bn3 (round 4)."""
-            _, cv, bn, A, wk, z, y, sm, sr, hh, ww, ho, wo, relu, has_res = op
-            M = B * ho * wo
+        def conv_bn_bwd(rec, dy, want_dres=False, need_dx=True, pre_part=None, below=None, addend=None):
+            """Backward of one conv + BatchNorm (+ReLU) -> (dx, the residual branch's gradient, statistics partials of `below`).
+            `pre_part`: dy arrives MASKED with its column sums already taken by the dgrad epilogue that produced it.  `below`: the
+            record whose output is this convolution's input -- when its BatchNorm has a ReLU and no residual, this dgrad's epilogue
+            does that BatchNorm's masking and statistics (epilogue_takes_bn).  `addend`: the block_out form, see the block loop."""
+            M = B * rec.Ho * rec.Wo
             if pre_part is not None:
-                dz = _bn_backward_parts(bn, lib, dy, z, sm, sr, pre_part, M, self.gscale, grads)
+                dz = rec.bn.backward_parts(lib, dy, rec.z, rec.mean, rec.rstd, pre_part, M, self.gscale, grads)
                 dres = dy if want_dres else None          # the masked gradient IS the gradient of the residual branch
             else:
                 # the ReLU mask: from y where a residual was added before the ReLU, recomputed from z otherwise (one tensor less to read)
-                dz, dres = bn.backward(lib, dy, z, y if (relu and has_res) else None, sm, sr, M, relu, want_dres, self.gscale, grads)
-            bnb = None
-            if fuse_on and fuse_prev is not None and fuse_prev[13] and not fuse_prev[14]:
-                bnb = (fuse_prev[5], fuse_prev[2].mod, fuse_prev[7], fuse_prev[8], True)
-            if block_out is not None:
-                pv, d_ident_in = block_out
-                bnb = (pv[5], pv[2].mod, pv[7], pv[8], True, d_ident_in, pv[6])
-            dxin, part = cv.backward(lib, dz, A, wk, B, hh, ww, ho, wo, self.gscale, wjobs, need_dx, side=side, wq=wq, bnb=bnb)
+                dz, dres = rec.bn.backward(lib, dy, rec.z, rec.y if (rec.relu and rec.has_res) else None, rec.mean, rec.rstd, M, rec.relu,
+                                           want_dres, self.gscale, grads)
+            if addend is None and not (below is not None and below.relu and not below.has_res
+                                       and epilogue_takes_bn(rec.conv, rec.H, rec.W, opts)):
+                below = None
+            dxin, part = rec.conv.backward(lib, dz, rec.x, rec.wk, B, rec.H, rec.W, rec.Ho, rec.Wo, self.gscale, wjobs, opts, need_dx,
+                                           wq=wq, below=below, addend=addend)
             if wq is not None and len(wq) >= group:
                 flush_wgrads(lib, wq, wjobs, self.gscale)
             return dxin, dres, part
 
-        fuse_out = fuse_on and os.environ.get("MEMEHIP_BN_BWD_FUSE_OUT", "1") != "0"
         dx_part = None       # statistics partials of the gradient in `dx` when a block's conv1 epilogue already masked it for the bn3 below
-        while i >= 0:
-            op = ops_[i]
-            kind = op[0]
-            if kind == "block_end":
-                has_ds = op[1]
-                # conv3 + bn3 (+ residual + relu): dres is the gradient of the identity branch; its dgrad epilogue already does
-                # bn2's masking + statistics, conv2's does bn1's
-                jc2 = i - 4 if has_ds else i - 2
-                d_o, dres, part2 = conv_bn_bwd(ops_[i - 1], dx, want_dres=True, fuse_prev=ops_[jc2], pre_part=dx_part)
-                dx_part = None
-                j = i - 2
-                d_ident = dres
-                if has_ds:
-                    assert ops_[j][0] == "branch_end"
-                    d_branch_in, _, _ = conv_bn_bwd(ops_[j - 1], dres, want_dres=False)      # downsample conv + bn (no relu)
-                    d_ident = d_branch_in
-                    j -= 2
-                d_o, _, part1 = conv_bn_bwd(ops_[j], d_o, want_dres=False, fuse_prev=ops_[j - 1], pre_part=part2)        # conv2
-                assert ops_[j - 2][0] == "block_begin"
-                below = ops_[j - 3] if j - 3 >= 0 else None
-                cv1 = ops_[j - 1][1]
-                if fuse_out and below is not None and below[0] == "block_end" and cv1.stride == 1 and cv1.kh == 1 and cv1.cout % 64 == 0:
-                    # conv1's dgrad epilogue = + d_ident, the ReLU mask of the block below (its stored output is conv1's input), bn3's statistics
-                    dx, _, dx_part = conv_bn_bwd(ops_[j - 1], d_o, want_dres=False, pre_part=part1, block_out=(ops_[j - 4], d_ident))
-                    assert dx_part is not None
-                else:
-                    d_o, _, _ = conv_bn_bwd(ops_[j - 1], d_o, want_dres=False, pre_part=part1)    # conv1
-                    merged = torch.empty_like(d_o)
-                    check(lib.mh_add_h16(d_o.data_ptr(), d_ident.data_ptr(), merged.data_ptr(), d_o.numel(), _stream()), "mh_add_h16")
-                    dx = merged
-                i = j - 3
-                continue
-            if kind == "maxpool":
-                _, arg, hh, ww, C1 = op
-                dxp = torch.empty((B * hh * ww, C1), dtype=T16, device=dev)
-                check(lib.mh_maxpool_bwd(dx.data_ptr(), arg.data_ptr(), dxp.data_ptr(), B, hh, ww, C1, 3, 2, 1, _stream()), "mh_maxpool_bwd")
-                dx = dxp
-                i -= 1
-                continue
-            if kind == "conv_bn":      # the stem
-                conv_bn_bwd(op, dx, want_dres=False, need_dx=False)      # the stem
-                i -= 1
-                continue
-            raise AssertionError(kind)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
+        for k in reversed(range(len(tape.blocks))):
+            blk, below = tape.blocks[k], (tape.blocks[k - 1] if k else None)
+            # conv3 + bn3 (+ residual + relu): d_ident is the gradient of the identity branch; its dgrad epilogue already does
+            # bn2's masking + statistics, conv2's does bn1's
+            d_o, d_ident, part2 = conv_bn_bwd(blk.conv3, dx, want_dres=True, below=blk.conv2, pre_part=dx_part)
+            if blk.downsample is not None:
+                d_ident, _, _ = conv_bn_bwd(blk.downsample, d_ident)      # downsample conv + bn (no relu)
+            d_o, _, part1 = conv_bn_bwd(blk.conv2, d_o, below=blk.conv1, pre_part=part2)
+            c1 = blk.conv1
+            if below is not None and epilogue_takes_bn(c1.conv, c1.H, c1.W, opts, block_out=True):
+                # conv1's input is the output y = relu(bn3(z) + residual) of the block below: its dgrad epilogue adds the gradient arriving
+                # through the other branch (d_ident), masks by y > 0 and takes bn3's statistics -- no mh_add_h16 pass, no statistics pass (round 4)
+                dx, _, dx_part = conv_bn_bwd(c1, d_o, pre_part=part1, below=below.conv3, addend=d_ident)
+            else:
+                d_o, _, _ = conv_bn_bwd(c1, d_o, pre_part=part1)
+                dx, dx_part = torch.empty_like(d_o), None
+                check(lib.mh_add_h16(d_o.data_ptr(), d_ident.data_ptr(), dx.data_ptr(), d_o.numel(), _stream()), "mh_add_h16")
+        pool = tape.pool
+        dxp = torch.empty((B * pool.H * pool.W, pool.C), dtype=T16, device=dev)
+        check(lib.mh_maxpool_bwd(dx.data_ptr(), pool.arg.data_ptr(), dxp.data_ptr(), B, pool.H, pool.W, pool.C, 3, 2, 1, _stream()), "mh_maxpool_bwd")
+        conv_bn_bwd(tape.stem, dxp, need_dx=False)
         if wq:
             flush_wgrads(lib, wq, wjobs, self.gscale)
         for i0 in range(0, len(wjobs), _lib.MH_CONV_MAX_JOBS):
@@ -500,7 +500,7 @@ class ResNet50(nn.Module):
     def features(self, image: torch.Tensor) -> torch.Tensor:
         if torch.is_grad_enabled() and self.training:
             return _TowerFn.apply(image, self, *self._tower_params)
-        return self._forward_tape(image, training=self.training)["pooled"]
+        return self._forward_tape(image, training=self.training).pooled
 
     def forward(self, image: torch.Tensor) -> torch.Tensor:
         return fused.linear(self.features(image), self.fc.weight, self.fc.bias)

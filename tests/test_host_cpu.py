@@ -364,3 +364,59 @@ def test_gradient_bucket_rule():
     assert [len(b.segs) for b in gradient_buckets(bwd, after, 3)] == [1, 3, 3, 3, 1, 1, 1, 1, 1]
     bwd, after = plan(1)
     assert names(gradient_buckets(bwd, after, 2)) == [["bwd_head"], ["L0"], ["bwd_embed"], ["bwd_embed_tables"]]
+
+
+def test_resnet_dgrad_routes_and_batchnorm_fusions():
+    """resnet.dgrad_route / resnet.epilogue_takes_bn (pure functions: what _Conv.backward and the backward walk ask) for ResNet-50
+    at 224 x 224 with the default options, and the routes off the common path."""
+    import torch.nn as nn
+    from collections import Counter
+    from multimodal_propaganda_meme_classification_amd import resnet as R
+    GEMM, IMPLICIT, COL2IM = "gemm", "implicit", "gemm + col2im"
+    assert (R.GEMM, R.IMPLICIT, R.COL2IM) == (GEMM, IMPLICIT, COL2IM)
+
+    def walk(net, H, W, opts):
+        """(routes of the convolutions that need an input gradient, who does each BatchNorm's backward masking + statistics)"""
+        routes, bns = [], Counter(plain=1)                       # the stem's BatchNorm: nothing above it but the max pool
+        h, w = net._stem_unit.conv.out_hw(H, W)
+        h, w = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
+        n = len(net._block_units)
+        for k, b in enumerate(net._block_units):
+            h2, w2 = b.conv2.conv.out_hw(h, w)
+            routes += [(b.conv1.conv, R.dgrad_route(b.conv1.conv, h, w, opts)), (b.conv2.conv, R.dgrad_route(b.conv2.conv, h, w, opts)),
+                       (b.conv3.conv, R.dgrad_route(b.conv3.conv, h2, w2, opts))]
+            bns["next_dgrad" if R.epilogue_takes_bn(b.conv2.conv, h, w, opts) else "plain"] += 1          # bn1, by conv2's dgrad
+            bns["next_dgrad" if R.epilogue_takes_bn(b.conv3.conv, h2, w2, opts) else "plain"] += 1        # bn2, by conv3's
+            if k > 0:        # this conv1's input is the output of the block below: its bn3
+                bns["conv1_above" if R.epilogue_takes_bn(b.conv1.conv, h, w, opts, block_out=True) else "plain"] += 1
+            if b.downsample is not None:
+                routes.append((b.downsample.conv, R.dgrad_route(b.downsample.conv, h, w, opts)))
+                bns["plain"] += 1
+            h, w = h2, w2
+        bns["plain"] += 1                                        # the top block's bn3
+        return routes, bns
+
+    net = pkg.ResNet50()
+    assert net.options == R.TowerOptions(bn_bwd_fuse=True, block_out_fuse=True, strided_dgrad=True, wgrad_group=6)
+    routes, bns = walk(net, 224, 224, net.options)
+    assert len(routes) == 52 and Counter(r for _, r in routes) == {IMPLICIT: 49, COL2IM: 3}
+    assert [(c.kh, c.stride) for c, r in routes if r == IMPLICIT and c.stride == 2] == [(3, 2)] * 3          # as parity classes
+    assert [(c.kh, c.stride) for c, r in routes if r == COL2IM] == [(1, 2)] * 3                               # the downsamples
+    assert bns == {"next_dgrad": 32, "conv1_above": 15, "plain": 6}
+    off = R.TowerOptions(strided_dgrad=False)
+    routes_off, _ = walk(net, 224, 224, off)
+    assert [(c.kh, c.stride) for c, r in routes_off if r == COL2IM].count((3, 2)) == 3 and Counter(r for _, r in routes_off) == {IMPLICIT: 46, COL2IM: 6}
+    _, bns_off = walk(net, 224, 224, R.TowerOptions(bn_bwd_fuse=False))
+    assert bns_off == {"plain": 53}
+    _, bns_out = walk(net, 224, 224, R.TowerOptions(block_out_fuse=False))
+    assert bns_out == {"next_dgrad": 32, "plain": 21}
+    # off the common path
+    opts = R.TowerOptions()
+    s2 = R._Conv(nn.Conv2d(64, 128, 3, stride=2, padding=1, bias=False))
+    assert R.dgrad_route(s2, 18, 18, opts) == IMPLICIT and R.dgrad_route(s2, 18, 18, off) == COL2IM
+    assert R.dgrad_route(s2, 9, 18, opts) == R.dgrad_route(s2, 18, 9, opts) == R.dgrad_route(s2, 9, 9, opts) == COL2IM
+    assert R.dgrad_route(R._Conv(nn.Conv2d(128, 32, 1, bias=False)), 18, 18, opts) == GEMM          # Cout % 64 != 0, ldk == Cp
+    assert R.dgrad_route(R._Conv(nn.Conv2d(32, 32, 1, bias=False)), 18, 18, opts) == COL2IM         # ... ldk 64 != Cp 32
+    assert R.dgrad_route(R._Conv(nn.Conv2d(32, 32, 3, padding=1, bias=False)), 18, 18, opts) == COL2IM
+    assert R.dgrad_route(R._Conv(nn.Conv2d(32, 64, 1, bias=False)), 18, 18, opts) == IMPLICIT
+    assert not R.epilogue_takes_bn(R._Conv(nn.Conv2d(128, 32, 1, bias=False)), 18, 18, opts)

@@ -28,8 +28,8 @@ Which path each case reaches (csrc/convgemm.hip, csrc/conv.hip, resnet.py):
       (bn2d_bwd_finish_kernel + bn2d_bwd_apply_kernel) with and without accumulate and scale
   wgrad                                   mh_conv_wgrad at several ksplit + mh_conv_wgrad_finish_batched (accumulate 0 / 1);
                                             mh_conv_wgrad_grouped (5 mixed problems) == the single calls bit for bit
-  model switches                          ResNet50(layers=(2, 1, 1, 1)) _backward_tape under MEMEHIP_BN_BWD_FUSE,
-                                            MEMEHIP_BN_BWD_FUSE_OUT, MEMEHIP_STRIDED_DGRAD, MEMEHIP_WGRAD_GROUP: fuse_prev,
+  model switches                          ResNet50(layers=(2, 1, 1, 1)) _backward_tape under ResNet50.options (TowerOptions:
+                                            bn_bwd_fuse, block_out_fuse, strided_dgrad, wgrad_group): fuse_prev,
                                             pre_part and block_out are asserted to fire, and every gradient must agree
 
 Tolerances, in units of the storage type's epsilon EPS (2^-10 fp16, 2^-7 bf16):
@@ -735,14 +735,13 @@ def test_conv_wgrad_grouped_equals_single_calls(pkg, n, T16):
 # 5. model-level switch consistency
 # ---------------------------------------------------------------------------------------------------------------------
 
-SWITCHES = ("MEMEHIP_BN_BWD_FUSE", "MEMEHIP_BN_BWD_FUSE_OUT", "MEMEHIP_STRIDED_DGRAD", "MEMEHIP_WGRAD_GROUP")
-SETTINGS = {
+SETTINGS = {          # fields of resnet.TowerOptions that leave their default
     "fused": {},
-    "bn_bwd_fuse=0": {"MEMEHIP_BN_BWD_FUSE": "0"},
-    "bn_bwd_fuse_out=0": {"MEMEHIP_BN_BWD_FUSE_OUT": "0"},
-    "strided_dgrad=0": {"MEMEHIP_STRIDED_DGRAD": "0"},
-    "wgrad_group=1": {"MEMEHIP_WGRAD_GROUP": "1"},
-    "all_off": {"MEMEHIP_BN_BWD_FUSE": "0", "MEMEHIP_BN_BWD_FUSE_OUT": "0", "MEMEHIP_STRIDED_DGRAD": "0", "MEMEHIP_WGRAD_GROUP": "1"},
+    "bn_bwd_fuse=0": {"bn_bwd_fuse": False},
+    "bn_bwd_fuse_out=0": {"block_out_fuse": False},
+    "strided_dgrad=0": {"strided_dgrad": False},
+    "wgrad_group=1": {"wgrad_group": 1},
+    "all_off": {"bn_bwd_fuse": False, "block_out_fuse": False, "strided_dgrad": False, "wgrad_group": 1},
 }
 ACT_ULPS = 4           # activation gradients: max |a - b| in ulps (EPS) of the tensor's largest element
 PARAM_REL_EPS = 10     # parameter gradients: ||a - b|| / ||b|| <= 10 EPS (fp16 9.8e-3, bf16 7.8e-2).  A BatchNorm bias gradient is a
@@ -811,12 +810,8 @@ def test_model_switches_agree(pkg, monkeypatch, T16):
     rec = {}
     _instrument(monkeypatch, pkg, lib, T16, rec)
     results = {}
-    for name, env in SETTINGS.items():
-        for k in SWITCHES:
-            if k in env:
-                monkeypatch.setenv(k, env[k])
-            else:
-                monkeypatch.delenv(k, raising=False)
+    for name, fields in SETTINGS.items():
+        net.options = pkg.resnet.TowerOptions(**fields)
         rec.clear()
         rec.update({k: 0 for k in ("dgrad_plain", "block_out", "fuse_prev", "other", "strided_dgrad", "pre_part", "wgrad_single",
                                    "wgrad_grouped")})
