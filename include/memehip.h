@@ -226,6 +226,29 @@ int mh_unpack_rows(const void* src /*bf16 packed [.][D]*/, const int32_t* inv_ma
                    int max_rows, int D, mh_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Row jobs of the last encoder layer.  The classifier reads ONE row per sample from each tower (the pooled text
+ * position, the ViT class token), and behind the last attention every block is row-wise: with these two calls the
+ * blocks run on a compact [n][D] panel instead of every token row.
+ *   compact row b  <->  full row  idx[b]  (device int32 [n], strictly ASCENDING)  or  b*stride + offset  (idx NULL)
+ * mh_rows_gather:       dst[b] = src[row(b)]            src = full [rows][D], dst = compact [n][D]; a row index is
+ *                       clamped into [0, rows) before it is used
+ * mh_rows_scatter_zero: dst[row(b)] = src[b], every other row of dst[0 .. rows) = 0
+ *                       src = compact [n][D], dst = full; rows = min(rows, *rows_dev) when rows_dev is given, rows
+ *                       past it are not touched; an index outside [0, rows) writes nothing
+ * 16-bit elements, D % 8 == 0, 16-byte aligned buffers.  Up to MH_ROWS_MAX_JOBS jobs (of any D) share one launch.
+ * ------------------------------------------------------------------------------------------ */
+#define MH_ROWS_MAX_JOBS 8
+typedef struct {
+    const void* src;
+    void* dst;
+    const int32_t* idx;        /* device, or NULL */
+    const int32_t* rows_dev;   /* device, or NULL (scatter only) */
+    int32_t n, rows, D, stride, offset; int32_t reserved_;
+} MhRowsJob;
+int mh_rows_gather(const MhRowsJob* jobs /*host*/, int n_jobs, mh_stream_t stream);
+int mh_rows_scatter_zero(const MhRowsJob* jobs /*host*/, int n_jobs, mh_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * BERT embeddings: x = LN(word[ids] + pos[s] + type[0]) (BertEmbeddings; ids are the Dataset's
  * int64 `text`, Multimodal_example_task2C.txt:63).  type may be NULL (DistilBERT).
  * fwd saves the pre-LN sum (bf16) + mean/rstd for the backward.

@@ -98,6 +98,14 @@ class MhAttnProblem(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+MH_ROWS_MAX_JOBS = 8
+
+
+class MhRowsJob(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("src", "dst", "idx", "rows_dev")] + \
+               [(n, C.c_int32) for n in ("n", "rows", "D", "stride", "offset", "reserved_")]
+
+
 class MhGemmF32(C.Structure):
     _fields_ = [("A", c_void_p), ("B", c_void_p), ("C", c_void_p), ("bias", c_void_p)] + \
                [(n, C.c_int32) for n in ("M", "N", "K", "lda", "ldb", "ldc", "flags")] + \
@@ -137,6 +145,8 @@ _PROTOS = {
     "mh_pack_plan": [c_void_p, c_int, c_int, c_int] + [c_void_p] * 6 + [c_void_p],
     "mh_pack_rows": [c_void_p] * 4 + [c_int, c_int, c_void_p],
     "mh_unpack_rows": [c_void_p] * 3 + [c_int, c_int, c_void_p],
+    "mh_rows_gather": [C.POINTER(MhRowsJob), c_int, c_void_p],
+    "mh_rows_scatter_zero": [C.POINTER(MhRowsJob), c_int, c_void_p],
     "mh_bert_embed_fwd": [c_void_p] * 10 + [c_int, c_int, c_int, c_int, c_float, c_void_p, c_float, C.c_uint32, c_void_p],
     "mh_image_normalize_u8": [c_void_p, c_void_p, c_int, c_int, c_int, C.POINTER(c_float), C.POINTER(c_float), c_void_p],
     "mh_image_resample_u8": [c_void_p] * 5 + [c_int] + [c_void_p] * 2 + [c_int] + [c_void_p] * 4 + [c_int] * 5 + [c_void_p],

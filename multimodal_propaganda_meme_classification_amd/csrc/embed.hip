@@ -686,6 +686,116 @@ extern "C" int mh_unpack_rows(const void* src, const int32_t* inv_map, void* dst
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Row jobs of the last encoder layer (see include/memehip.h: MhRowsJob): the head reads one row per sample, so the
+// row-wise blocks behind the last attention run on a compact [n][D] panel.  mh_rows_gather builds the panels,
+// mh_rows_scatter_zero puts a compact gradient back into the full buffer and zero-fills every other row.
+// Several jobs (both towers, several operands) share a launch; a wave moves whole rows in 16-B chunks.
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+struct RowsGroup {
+    int n;
+    int start[MH_ROWS_MAX_JOBS + 1];      // first workgroup (x) of each job
+    MhRowsJob job[MH_ROWS_MAX_JOBS];
+};
+
+MH_DEV int rows_job_of(const RowsGroup& grp) {
+    int j = 0;
+    while (j + 1 < grp.n && (int)blockIdx.x >= grp.start[j + 1]) ++j;
+    return j;
+}
+// full row of compact row b (wave-uniform b)
+MH_DEV int rows_index(const MhRowsJob& jb, int b) { return jb.idx ? jb.idx[b] : b * jb.stride + jb.offset; }
+
+// one row of D 16-bit elements, 2048 per trip: the four loads of a trip are issued before the first store (the
+// buffer resources end at the row's end: loads past it return 0 and stores past it are dropped, so none is predicated).
+// s and d are wave-uniform.
+MH_DEV void rows_copy_row(const h16* __restrict__ s, h16* __restrict__ d, int D, int lane) {
+    const __amdgpu_buffer_rsrc_t rs = mh_rsrc(s, (uint32_t)D * 2u), rd = mh_rsrc(d, (uint32_t)D * 2u);
+    for (int c0 = 0; c0 < D; c0 += 2048) {
+        i32x4 v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = mh_buf_load16(rs, (uint32_t)(c0 + (lane + 64 * i) * 8) * 2u);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) mh_buf_store16(rd, (uint32_t)(c0 + (lane + 64 * i) * 8) * 2u, v[i]);
+    }
+}
+
+// wave per compact row, 4 rows per workgroup
+__global__ __launch_bounds__(256) void rows_gather_kernel(const RowsGroup grp) {
+    const int j = rows_job_of(grp);
+    const MhRowsJob& jb = grp.job[j];
+    const int lane = threadIdx.x & 63;
+    const int b = ((int)blockIdx.x - grp.start[j]) * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (b >= jb.n) return;
+    const int r = __builtin_amdgcn_readfirstlane(min(max(rows_index(jb, b), 0), jb.rows - 1));     // never outside the source
+    rows_copy_row((const h16*)jb.src + (size_t)r * jb.D, (h16*)jb.dst + (size_t)b * jb.D, jb.D, lane);
+}
+
+// The indices ascend, so the destination falls into n + 1 segments: segment s holds the zero rows behind indexed row s-1 and
+// then indexed row s itself (segment n: the zero rows behind the last one).  blockIdx.x = segment, blockIdx.y = one of
+// gridDim.y workgroups that share its rows (wave w of them takes rows lo + w, lo + w + 4 gridDim.y, ...).  A segment's bounds
+// are two wave-uniform index reads and its data row is compact row s: no load depends on another.
+__global__ __launch_bounds__(256) void rows_scatter_zero_kernel(const RowsGroup grp) {
+    const int j = rows_job_of(grp);
+    const MhRowsJob& jb = grp.job[j];
+    const int lane = threadIdx.x & 63;
+    const int seg = (int)blockIdx.x - grp.start[j];
+    const int n = jb.n, D = jb.D;
+    if (seg > n) return;
+    const int rows = jb.rows_dev ? min(jb.rows, *jb.rows_dev) : jb.rows;
+    const int at_prev = rows_index(jb, max(seg - 1, 0)), at_this = rows_index(jb, min(seg, n - 1));
+    const int lo = seg == 0 ? 0 : min(max(at_prev + 1, 0), rows);
+    const int hi = seg < n ? min(max(at_this, 0), rows) : rows;      // the indexed row, or the end of the buffer
+    const int nw = 4 * (int)gridDim.y;
+    const int w = __builtin_amdgcn_readfirstlane((int)blockIdx.y * 4 + (int)(threadIdx.x >> 6));
+    h16* __restrict__ dst = (h16*)jb.dst;
+    const i32x4 zero = {0, 0, 0, 0};
+    for (int row = lo + w; row < hi; row += nw)
+        for (int c = lane * 8; c < D; c += 512) *(i32x4*)(dst + (size_t)row * D + c) = zero;
+    // the data row: only when the index is a row of the (clamped) buffer and the indices did ascend
+    if (seg < n && at_this == hi && hi < rows && hi >= lo && w == (hi - lo) % nw)
+        rows_copy_row((const h16*)jb.src + (size_t)seg * D, dst + (size_t)__builtin_amdgcn_readfirstlane(hi) * D, D, lane);
+}
+
+int rows_group(const MhRowsJob* jobs, int n_jobs, bool scatter, RowsGroup& g) {
+    if (!jobs || n_jobs < 1 || n_jobs > MH_ROWS_MAX_JOBS) return MH_EINVAL;
+    g.n = n_jobs;
+    int blocks = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        const MhRowsJob& jb = jobs[i];
+        if (!jb.src || !jb.dst) return MH_EINVAL;
+        if (((uintptr_t)jb.src | (uintptr_t)jb.dst) & 15) return MH_EINVAL;
+        if (jb.n < 1 || jb.rows < 1 || jb.D < 8 || (jb.D % 8)) return MH_ESHAPE;
+        // arithmetic rows: every index inside the full buffer, and ascending
+        if (!jb.idx && (jb.stride < 1 || jb.offset < 0 || (int64_t)(jb.n - 1) * jb.stride + jb.offset >= jb.rows)) return MH_ESHAPE;
+        g.job[i] = jb;
+        g.start[i] = blocks;
+        blocks += scatter ? jb.n + 1 : (jb.n + 3) / 4;
+    }
+    for (int i = n_jobs; i <= MH_ROWS_MAX_JOBS; ++i) g.start[i] = blocks;
+    return MH_OK;
+}
+
+}  // namespace
+
+extern "C" int mh_rows_gather(const MhRowsJob* jobs, int n_jobs, mh_stream_t stream) {
+    RowsGroup g;
+    const int rc = rows_group(jobs, n_jobs, false, g);
+    if (rc != MH_OK) return rc;
+    hipLaunchKernelGGL(rows_gather_kernel, dim3(g.start[MH_ROWS_MAX_JOBS]), dim3(256), 0, (hipStream_t)stream, g);
+    return mh_launch_status();
+}
+
+extern "C" int mh_rows_scatter_zero(const MhRowsJob* jobs, int n_jobs, mh_stream_t stream) {
+    RowsGroup g;
+    const int rc = rows_group(jobs, n_jobs, true, g);
+    if (rc != MH_OK) return rc;
+    hipLaunchKernelGGL(rows_scatter_zero_kernel, dim3(g.start[MH_ROWS_MAX_JOBS], 4), dim3(256), 0, (hipStream_t)stream, g);
+    return mh_launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Input pipeline on the device: ToTensor + Normalize of the reference's transform
 // (Multimodal_example_task2C.txt:37-41: x/255 then (x - mean)/std per channel) from the decoded, resized and cropped
 // uint8 image.  The host ships 1 byte per sample instead of 4 and no longer spends a core on the arithmetic.

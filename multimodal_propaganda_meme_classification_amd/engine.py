@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from ._lib import (MH_GEMM_ACCUM, MH_GEMM_DERIV_AUX, MH_GEMM_GELU, MH_GEMM_OUT_F32, MH_GEMM_QUICK_GELU, MhAttnProblem, MhColsumJob, MhGemmProblem, MhHeadGrads,
-                   MhHeadParams, MhLnBwdJob, MhLnFwdJob)
+                   MhHeadParams, MhLnBwdJob, MhLnFwdJob, MhRowsJob)
 from .config import Layout, ModelConfig
 
 BF16, F32, I64 = torch.bfloat16, torch.float32, torch.int64
@@ -153,6 +153,7 @@ class Plan:
         self.packed = False
         self.dropout_on = False               # some dropout probability is non-zero in this plan
         self.features = False                 # False | True | "sequence": where the plan stops (Engine.plan)
+        self.last_rows = "all"                # "pooled": the blocks behind the last attention run on the B pooled rows only
         self.gather = None                    # data parallel: (local, gathered) tensor pairs exchanged before "bwd_embed_tables"
         self._ln_jobs: Dict[int, list] = {}   # width -> (partials, dgamma, dbeta) of every LayerNorm backward, summed in "bwd_embed"
 
@@ -327,6 +328,21 @@ class Engine:
         plan.keep.append(arr)
         seg.c("mh_attn_bwd_grouped" if backward else "mh_attn_fwd_grouped", arr, len(probs))
 
+    def _rows(self, plan: Plan, seg: Segment, jobs: List[dict], scatter: bool):
+        """Row jobs of the last layer as ONE launch: gather (full -> compact [n, D]) or scatter with zero fill (compact -> full).
+        A job names its rows by a device index array `idx` (ascending) or as b * stride + offset."""
+        assert 1 <= len(jobs) <= _lib.MH_ROWS_MAX_JOBS
+        arr = (MhRowsJob * len(jobs))()
+        for e, j in zip(arr, jobs):
+            src, dst, idx, n, rows, D = j["src"], j["dst"], j.get("idx"), j["n"], j["rows"], j["D"]
+            full, compact = (dst, src) if scatter else (src, dst)
+            assert src.dtype == self.T16 and dst.dtype == self.T16 and full.numel() >= rows * D and compact.numel() >= n * D
+            assert idx is None or (idx.dtype == torch.int32 and idx.numel() >= n)
+            e.src, e.dst, e.idx, e.rows_dev = _ptr(src), _ptr(dst), _ptr(idx), _ptr(j.get("rows_dev") if scatter else None)
+            e.n, e.rows, e.D, e.stride, e.offset = n, rows, D, j.get("stride", 0), j.get("offset", 0)
+        plan.keep.append(arr)
+        seg.c("mh_rows_scatter_zero" if scatter else "mh_rows_gather", arr, len(jobs))
+
     def before_backward(self, plan: Plan):
         """Each plan re-zeroes the word-embedding gradient rows IT touched last time (the table gradient is dense,
         only touched rows are ever non-zero).  When the previous backward ran under a different plan (another
@@ -344,7 +360,8 @@ class Engine:
         self._last_bwd_plan = plan
 
     # ---- plan ----------------------------------------------------------------------------------------------
-    def plan(self, B: int, S: int, training: bool = True, gather_world: int = 0, features=False) -> Plan:
+    def plan(self, B: int, S: int, training: bool = True, gather_world: int = 0, features=False,
+             last_rows: str = "pooled") -> Plan:
         """Plans differ between train and eval only when some dropout probability is non-zero.
         features = True: the plan stops at the pooled tower features (text pooled row | ViT class token, f32) and its
         backward starts from their gradient: the late-fusion head is then whatever the caller builds on top.
@@ -352,18 +369,23 @@ class Engine:
         boundary -- for poolings that read every position (max / mean / attention / conv1d); the reference pools over the
         padded positions too, so this plan computes them (no row packing).
         gather_world = W > 0 (data parallel): the embedding-table gradients are built from the all-gathered token ids
-        and embedding-gradient rows of all W ranks (6 MB per rank) instead of all-reducing the dense 196-MB table."""
+        and embedding-gradient rows of all W ranks (6 MB per rank) instead of all-reducing the dense 196-MB table.
+        last_rows = "pooled" (default): behind the attention of each tower's last layer, only the rows the pooling reads are
+        computed (see _build); "all" computes every row.  Plans whose full last hidden states are read, or that carry
+        dropout, are built as "all" whatever is asked for: ``plan.last_rows`` tells which form a plan has."""
+        if last_rows not in ("pooled", "all"):
+            raise ValueError(f"last_rows must be 'pooled' or 'all', got {last_rows!r}")
         cfg = self.cfg
         has_drop = (cfg.text.hidden_dropout > 0 or cfg.text.attention_dropout > 0 or cfg.head_dropout > 0)
         features = features if features == "sequence" else bool(features)
         pack = self.pack_text and features != "sequence"
-        key = (B, S, bool(training and has_drop), int(gather_world), pack, features)
+        key = (B, S, bool(training and has_drop), int(gather_world), pack, features) + (() if last_rows == "pooled" else (last_rows,))
         if key not in self.plans:
-            self.plans[key] = self._build(B, S, key[2], key[3], key[4], key[5])
+            self.plans[key] = self._build(B, S, key[2], key[3], key[4], key[5], last_rows=last_rows)
         return self.plans[key]
 
     def _build(self, B: int, S: int, dropout_on: bool = False, gather_world: int = 0, pack: bool = False,
-               features=False) -> Plan:
+               features=False, last_rows: str = "pooled") -> Plan:
         cfg, t, v = self.cfg, self.cfg.text, self.cfg.image
         if S > t.max_position:
             raise ValueError(f"sequence length {S} > max_position {t.max_position}")
@@ -391,6 +413,14 @@ class Engine:
         Kp = v.channels * v.patch * v.patch
         Tt, Ti = B * S, B * Nt
         P_, Cn = cfg.proj, cfg.num_classes
+        # The head reads ONE row per sample from each tower (the pooled text position, the ViT class token), and behind the
+        # attention core every block of a layer is row-wise.  cmp: the last layer of each tower gathers those B rows behind its
+        # attention and runs out-proj, LayerNorms and FFN on [B, D] panels (forward and backward); the out-proj input
+        # gradient is scattered back, with zeros everywhere else, in front of the attention backward.  Not when somebody
+        # reads the full last hidden states ("sequence"), and not with dropout (its masks are indexed by the full row).
+        cmp = last_rows == "pooled" and features != "sequence" and not dropout_on and Lt >= 1 and Li >= 1
+        pl.last_rows = "pooled" if cmp else "all"
+        Rt, Ri = (B, B) if cmp else (Tt, Ti)      # rows of a tower's last hidden state
 
         def alloc(name, shape, dtype=BF16, zero=False):
             tns = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=dev)
@@ -471,26 +501,41 @@ class Engine:
                 _ptr(self.p(IMG + "embeddings.position_embeddings")), _ptr(xi[0]), B, Np, Di)
         quick = dict(quick=True) if v.act == "quick_gelu" else {}
 
-        xt_last32 = alloc("t.xlast32", (Tt, Dt), F32)   # unrounded tower outputs for the fp32 head
-        xf32 = alloc("i.xf32", (Ti, Di), F32)
+        xt_last32 = alloc("t.xlast32", (Rt, Dt), F32)   # unrounded tower outputs for the fp32 head
+        xf32 = alloc("i.xf32", (Ri, Di), F32)
         tl: List[dict] = []   # per-layer saved activations, text
         il: List[dict] = []
+        # "rows" of a layer = the rows of everything behind its attention core ("pctx" / "x": the operands of the first such block,
+        # the attention output and the layer input, at those rows: gathered copies in a compact last layer)
         for l in range(Lt):
+            R = B if (cmp and l == Lt - 1) else Tt
             tl.append(dict(qkv=alloc(f"t{l}.qkv", (Tt, 3 * Dt)), ctx=alloc(f"t{l}.ctx", (Tt, Dt)),
-                           lse=alloc(f"t{l}.lse", (B, Ht, S), F32), a=alloc(f"t{l}.a", (Tt, Dt)),
-                           y=alloc(f"t{l}.y", (Tt, Dt)), m1=alloc(f"t{l}.m1", (Tt,), F32), r1=alloc(f"t{l}.r1", (Tt,), F32),
-                           h=alloc(f"t{l}.h", (Tt, It)), g=alloc(f"t{l}.g", (Tt, It)), f=alloc(f"t{l}.f", (Tt, Dt)),
-                           m2=alloc(f"t{l}.m2", (Tt,), F32), r2=alloc(f"t{l}.r2", (Tt,), F32)))
-            xt.append(alloc(f"t.x{l + 1}", (Tt, Dt)))
+                           lse=alloc(f"t{l}.lse", (B, Ht, S), F32), a=alloc(f"t{l}.a", (R, Dt)),
+                           y=alloc(f"t{l}.y", (R, Dt)), m1=alloc(f"t{l}.m1", (R,), F32), r1=alloc(f"t{l}.r1", (R,), F32),
+                           h=alloc(f"t{l}.h", (R, It)), g=alloc(f"t{l}.g", (R, It)), f=alloc(f"t{l}.f", (R, Dt)),
+                           m2=alloc(f"t{l}.m2", (R,), F32), r2=alloc(f"t{l}.r2", (R,), F32), rows=R))
+            if R != Tt:     # (a [B, D] panel is never clamped by the live-row count)
+                tl[l].update(pctx=alloc(f"t{l}.pctx", (B, Dt)), x=alloc(f"t{l}.xrows", (B, Dt)), tp={}, tpd={})
+            else:
+                tl[l].update(pctx=tl[l]["ctx"], x=xt[l], tp=tp, tpd=tpd)
+            xt.append(alloc(f"t.x{l + 1}", (R, Dt)))
         for l in range(Li):
+            R = B if (cmp and l == Li - 1) else Ti
             il.append(dict(u=alloc(f"i{l}.u", (Ti, Di)), m1=alloc(f"i{l}.m1", (Ti,), F32), r1=alloc(f"i{l}.r1", (Ti,), F32),
                            qkv=alloc(f"i{l}.qkv", (Ti, 3 * Di)), ctx=alloc(f"i{l}.ctx", (Ti, Di)),
-                           lse=alloc(f"i{l}.lse", (B, Hi, Nt), F32), xp=alloc(f"i{l}.xp", (Ti, Di)),
-                           w=alloc(f"i{l}.w", (Ti, Di)), m2=alloc(f"i{l}.m2", (Ti,), F32), r2=alloc(f"i{l}.r2", (Ti,), F32),
-                           h=alloc(f"i{l}.h", (Ti, Ii)), g=alloc(f"i{l}.g", (Ti, Ii))))
-            xi.append(alloc(f"i.x{l + 1}", (Ti, Di)))
-        xf = alloc("i.xf", (Ti, Di))
-        mf, rf = alloc("i.mf", (Ti,), F32), alloc("i.rf", (Ti,), F32)
+                           lse=alloc(f"i{l}.lse", (B, Hi, Nt), F32), xp=alloc(f"i{l}.xp", (R, Di)),
+                           w=alloc(f"i{l}.w", (R, Di)), m2=alloc(f"i{l}.m2", (R,), F32), r2=alloc(f"i{l}.r2", (R,), F32),
+                           h=alloc(f"i{l}.h", (R, Ii)), g=alloc(f"i{l}.g", (R, Ii)), rows=R))
+            if R != Ti:
+                il[l].update(pctx=alloc(f"i{l}.pctx", (B, Di)), x=alloc(f"i{l}.xrows", (B, Di)))
+            else:
+                il[l].update(pctx=il[l]["ctx"], x=xi[l])
+            xi.append(alloc(f"i.x{l + 1}", (R, Di)))
+        xf = alloc("i.xf", (Ri, Di))
+        mf, rf = alloc("i.mf", (Ri,), F32), alloc("i.rf", (Ri,), F32)
+        # the pooled rows of each tower's row buffers: by the packing plan's pool_rows, or by arithmetic
+        t_rows = dict(idx=pool_rows, n=B, rows=Tt, D=Dt) if pack else dict(stride=S, offset=pool_index, n=B, rows=Tt, D=Dt)
+        i_rows = dict(stride=Nt, offset=0, n=B, rows=Ti, D=Di)
 
         def img_ln1(l):
             """The ViT block's pre-attention LayerNorm of layer l; past the last layer, the final ViT LayerNorm.
@@ -500,7 +545,7 @@ class Engine:
                 return self._ln_fwd_job(xi[l], LI + "layernorm_before.weight", LI + "layernorm_before.bias", il[l]["u"],
                                         il[l]["m1"], il[l]["r1"], Ti, Di, v.ln_eps)
             if l == Li:
-                return self._ln_fwd_job(xi[Li], IMG + "layernorm.weight", IMG + "layernorm.bias", xf, mf, rf, Ti, Di,
+                return self._ln_fwd_job(xi[Li], IMG + "layernorm.weight", IMG + "layernorm.bias", xf, mf, rf, Ri, Di,
                                         v.ln_eps, y32=xf32)
             return None
 
@@ -522,45 +567,55 @@ class Engine:
             self._attn(pl, f, [
                 dict(qkv=b_["qkv"], out=b_["ctx"], lse=b_["lse"], B=B, S=Nt, H=Hi) if has_i else None,
                 text_attn(a, 16 * (l + 1) + 1) if has_t else None], backward=False)
+            # a compact last layer: from here on, only the pooled rows (of the attention output and of the layer input)
+            jobs = []
+            if has_t and a["rows"] != Tt:
+                jobs += [dict(t_rows, src=a["ctx"], dst=a["pctx"]), dict(t_rows, src=xt[l], dst=a["x"])]
+            if has_i and b_["rows"] != Ti:
+                jobs += [dict(i_rows, src=b_["ctx"], dst=b_["pctx"]), dict(i_rows, src=xi[l], dst=b_["x"])]
+            if jobs:
+                self._rows(pl, f, jobs, scatter=False)
+            Mt, Mi = (a["rows"] if has_t else 0), (b_["rows"] if has_i else 0)
+            tp_l, tpd_l = (a["tp"], a["tpd"]) if has_t else ({}, {})
             # attention output projection + residual
             pr = []
             if has_t:
-                pr.append(self._fwd_prob(a["ctx"], self.w(LT + "attention.output.dense.weight"), a["a"], Tt, Dt, Dt,
-                                         bias=self.p(LT + "attention.output.dense.bias"), residual=xt[l],
-                                         drop=site(p_h, 16 * (l + 1) + 2), **tpd))
+                pr.append(self._fwd_prob(a["pctx"], self.w(LT + "attention.output.dense.weight"), a["a"], Mt, Dt, Dt,
+                                         bias=self.p(LT + "attention.output.dense.bias"), residual=a["x"],
+                                         drop=site(p_h, 16 * (l + 1) + 2), **tpd_l))
             if has_i:
-                pr.append(self._fwd_prob(b_["ctx"], self.w(LI + "attention.output.dense.weight"), b_["xp"], Ti, Di, Di,
-                                         bias=self.p(LI + "attention.output.dense.bias"), residual=xi[l]))
+                pr.append(self._fwd_prob(b_["pctx"], self.w(LI + "attention.output.dense.weight"), b_["xp"], Mi, Di, Di,
+                                         bias=self.p(LI + "attention.output.dense.bias"), residual=b_["x"]))
             self._gemm(pl, f, pr, False, False)
             self._ln_fwd(pl, f, [
                 self._ln_fwd_job(a["a"], LT + "attention.output.LayerNorm.weight", LT + "attention.output.LayerNorm.bias",
-                                 a["y"], a["m1"], a["r1"], Tt, Dt, t.ln_eps, **tp) if has_t else None,
+                                 a["y"], a["m1"], a["r1"], Mt, Dt, t.ln_eps, **tp_l) if has_t else None,
                 self._ln_fwd_job(b_["xp"], LI + "layernorm_after.weight", LI + "layernorm_after.bias", b_["w"], b_["m2"],
-                                 b_["r2"], Ti, Di, v.ln_eps) if has_i else None])
+                                 b_["r2"], Mi, Di, v.ln_eps) if has_i else None])
             # FFN up + GELU; "h" keeps gelu'(pre-activation) for the backward (computed here from the activation's own exponential:
             # MH_GEMM_DERIV_AUX; MEMEHIP_GEMM_DERIV_AUX=0 keeps the pre-activation and evaluates gelu' in the backward epilogue)
             pr = []
             if has_t:
-                pr.append(self._fwd_prob(a["y"], self.w(LT + "intermediate.dense.weight"), a["g"], Tt, It, Dt,
-                                         bias=self.p(LT + "intermediate.dense.bias"), aux=a["h"], gelu=True, deriv_aux=DERIV_AUX, **tp))
+                pr.append(self._fwd_prob(a["y"], self.w(LT + "intermediate.dense.weight"), a["g"], Mt, It, Dt,
+                                         bias=self.p(LT + "intermediate.dense.bias"), aux=a["h"], gelu=True, deriv_aux=DERIV_AUX, **tp_l))
             if has_i:
-                pr.append(self._fwd_prob(b_["w"], self.w(LI + "intermediate.dense.weight"), b_["g"], Ti, Ii, Di,
+                pr.append(self._fwd_prob(b_["w"], self.w(LI + "intermediate.dense.weight"), b_["g"], Mi, Ii, Di,
                                          bias=self.p(LI + "intermediate.dense.bias"), aux=b_["h"], gelu=True, deriv_aux=DERIV_AUX, **quick))
             self._gemm(pl, f, pr, False, False)
             # FFN down + residual
             pr = []
             if has_t:
-                pr.append(self._fwd_prob(a["g"], self.w(LT + "output.dense.weight"), a["f"], Tt, Dt, It,
+                pr.append(self._fwd_prob(a["g"], self.w(LT + "output.dense.weight"), a["f"], Mt, Dt, It,
                                          bias=self.p(LT + "output.dense.bias"), residual=a["y"],
-                                         drop=site(p_h, 16 * (l + 1) + 3), **tpd))
+                                         drop=site(p_h, 16 * (l + 1) + 3), **tpd_l))
             if has_i:
-                pr.append(self._fwd_prob(b_["g"], self.w(LI + "output.dense.weight"), xi[l + 1], Ti, Di, Ii,
+                pr.append(self._fwd_prob(b_["g"], self.w(LI + "output.dense.weight"), xi[l + 1], Mi, Di, Ii,
                                          bias=self.p(LI + "output.dense.bias"), residual=b_["xp"]))
             self._gemm(pl, f, pr, False, False)
             # the text LayerNorm closing this layer + the image LayerNorm opening the next (or the final ViT one)
             self._ln_fwd(pl, f, [
                 self._ln_fwd_job(a["f"], LT + "output.LayerNorm.weight", LT + "output.LayerNorm.bias", xt[l + 1], a["m2"],
-                                 a["r2"], Tt, Dt, t.ln_eps, y32=xt_last32 if l == Lt - 1 else None, **tp) if has_t else None,
+                                 a["r2"], Mt, Dt, t.ln_eps, y32=xt_last32 if l == Lt - 1 else None, **tp_l) if has_t else None,
                 img_ln1(l + 1) if has_i else None])
 
         # head
@@ -575,15 +630,17 @@ class Engine:
         feat, fused = alloc("h.feat", (B, 2 * P_), F32), alloc("h.fused", (B, P_), F32)
         logits = alloc("logits", (B, Cn), F32)
         pl.features = features
+        # where the head finds its rows: compact towers hand it [B, D] (one "token" per sample)
+        S_h, Nt_h, pool_h, rows_h = (1, 1, 0, None) if cmp else (S, Nt, pool_index, pool_rows)
         if features == "sequence":
             assert not pack
             d_seq_t, d_seq_i = alloc("h.d_seq_t", (Tt, Dt), F32, zero=True), alloc("h.d_seq_i", (Ti, Di), F32, zero=True)
         elif features:
             d_pooled = alloc("h.d_pooled", (B, Dt + Di), F32, zero=True)
-            f.c("mh_pool_fwd", _ptr(xt_last32), _ptr(xf32), pool_index, _ptr(pooled), B, S, Nt, Dt, Di, _ptr(pool_rows))
+            f.c("mh_pool_fwd", _ptr(xt_last32), _ptr(xf32), pool_h, _ptr(pooled), B, S_h, Nt_h, Dt, Di, _ptr(rows_h))
         else:
-            f.c("mh_head_fwd", C.byref(hp), _ptr(xt_last32), _ptr(xf32), pool_index, _ptr(pooled), _ptr(feat), _ptr(fused),
-                _ptr(logits), B, S, Nt, Dt, Di, P_, Cn, *site_args(p_head, 7), _ptr(pool_rows))
+            f.c("mh_head_fwd", C.byref(hp), _ptr(xt_last32), _ptr(xf32), pool_h, _ptr(pooled), _ptr(feat), _ptr(fused),
+                _ptr(logits), B, S_h, Nt_h, Dt, Di, P_, Cn, *site_args(p_head, 7), _ptr(rows_h))
 
         # loss
         loss = alloc("loss", (1,), F32, zero=True)
@@ -605,10 +662,16 @@ class Engine:
         # and layer l-2 waits for them before it overwrites those buffers
         dXt = [alloc(f"t.dX{i}", (Tt, Dt)) for i in range(3)]
         dXi = [alloc(f"i.dX{i}", (Ti, Di)) for i in range(3)]
-        dXf = alloc("i.dXf", (Ti, Di))
+        dXf = alloc("i.dXf", (Ri, Di))
         dfeat, dfused = alloc("h.dfeat", (B, 2 * P_), F32), alloc("h.dfused", (B, P_), F32)
-        s.py(dXt[0].zero_)
-        s.py(dXf.zero_)
+        # the gradient that enters each tower's last layer: non-zero at the pooled rows only.  Full rows: zero-filled, the head
+        # writes the pooled rows.  Compact: [B, D], every row written by the head.
+        if cmp:
+            t_in, i_in = alloc("t.dXrows", (B, Dt)), alloc("i.dXrows", (B, Di))
+        else:
+            t_in, i_in = dXt[0], dXi[0]
+            s.py(t_in.zero_)
+            s.py(dXf.zero_)
         if features:
             # the built-in head is not part of this graph: its gradient slots must not keep stale values
             h0 = self.layout.spec["bert_fc.weight"].offset
@@ -616,15 +679,15 @@ class Engine:
             head_grads = self.G[h0:h1]
             s.py(head_grads.zero_)
             if features == "sequence":      # the caller's gradient w.r.t. every hidden state (already times the stream scale)
-                s.c("mh_cast_f32_bf16", _ptr(d_seq_t), _ptr(dXt[0]), Tt * Dt)
+                s.c("mh_cast_f32_bf16", _ptr(d_seq_t), _ptr(t_in), Tt * Dt)
                 s.c("mh_cast_f32_bf16", _ptr(d_seq_i), _ptr(dXf), Ti * Di)
             else:
-                s.c("mh_pool_bwd", _ptr(d_pooled), _ptr(dXt[0]), _ptr(dXf), pool_index, B, S, Nt, Dt, Di, float(self.gscale),
-                    _ptr(pool_rows))
+                s.c("mh_pool_bwd", _ptr(d_pooled), _ptr(t_in), _ptr(dXf), pool_h, B, S_h, Nt_h, Dt, Di, float(self.gscale),
+                    _ptr(rows_h))
         else:
             s.c("mh_head_bwd", C.byref(hp), C.byref(hg), _ptr(dlogits), _ptr(pooled), _ptr(feat), _ptr(fused), _ptr(dfeat),
-                _ptr(dfused), _ptr(dXt[0]), _ptr(dXf), pool_index, B, S, Nt, Dt, Di, P_, Cn, float(self.gscale),
-                *site_args(p_head, 7), _ptr(pool_rows))
+                _ptr(dfused), _ptr(t_in), _ptr(dXf), pool_h, B, S_h, Nt_h, Dt, Di, P_, Cn, float(self.gscale),
+                *site_args(p_head, 7), _ptr(rows_h))
         # backward temporaries, one set per layer parity
         T_ = [dict(dh=alloc(f"t.dh{i}", (Tt, It)), da=alloc(f"t.da{i}", (Tt, Dt)),
                    dqkv=alloc(f"t.dqkv{i}", (Tt, 3 * Dt)),
@@ -640,20 +703,28 @@ class Engine:
         t_delta = alloc("t.delta", (B, Ht, S), F32)
         i_dw, i_dctx, i_du = alloc("i.dw", (Ti, Di)), alloc("i.dctx", (Ti, Di)), alloc("i.du", (Ti, Di))
         i_delta = alloc("i.delta", (B, Hi, Nt), F32)
+        if cmp:
+            # the compact last layers' own gradient panels.  The two that reach past the attention output projection are
+            # scattered into the full buffers of that layer parity, which the full-size kernels then read as before.
+            tc = dict(df=alloc("t.dfrows", (B, Dt)), dh=alloc("t.dhrows", (B, It)), dy=alloc("t.dyrows", (B, Dt)),
+                      da=alloc("t.darows", (B, Dt)), dctx=alloc("t.dctxrows", (B, Dt)))
+            ic = dict(dh=alloc("i.dhrows", (B, Ii)), dw=alloc("i.dwrows", (B, Di)), dxp=alloc("i.dxprows", (B, Di)),
+                      dctx=alloc("i.dctxrows", (B, Di)))
 
         def text_ln2_bwd(l, ct_):
-            """Backward of the LayerNorm that closes text layer l (incoming gradient dXt[ct_]).  Issued at the END of
-            the segment above, grouped with the image tower's LayerNorm there."""
+            """Backward of the LayerNorm that closes text layer l (incoming gradient dXt[ct_]; the last layer's: t_in).
+            Issued at the END of the segment above, grouped with the image tower's LayerNorm there."""
             if not (0 <= l < Lt):
                 return None
             LT_ = f"{TXT}encoder.layer.{l}."
-            return self._ln_bwd_job(pl, dXt[ct_], tl[l]["f"], LT_ + "output.LayerNorm.weight", LT_ + "output.LayerNorm.bias",
-                                    tl[l]["m2"], tl[l]["r2"], DF_[l % 3]["df"], Tt, Dt,
-                                    dx_drop=DF_[l % 3]["dfm"] if p_h > 0 else None, drop=site(p_h, 16 * (l + 1) + 3), **tpd)
+            dy, dx = (t_in, tc["df"] if cmp else DF_[l % 3]["df"]) if l == Lt - 1 else (dXt[ct_], DF_[l % 3]["df"])
+            return self._ln_bwd_job(pl, dy, tl[l]["f"], LT_ + "output.LayerNorm.weight", LT_ + "output.LayerNorm.bias",
+                                    tl[l]["m2"], tl[l]["r2"], dx, tl[l]["rows"], Dt,
+                                    dx_drop=DF_[l % 3]["dfm"] if p_h > 0 else None, drop=site(p_h, 16 * (l + 1) + 3), **tl[l]["tpd"])
 
         nl = max(Lt, Li)
         self._ln_bwd(pl, s, [
-            self._ln_bwd_job(pl, dXf, xi[Li], IMG + "layernorm.weight", IMG + "layernorm.bias", mf, rf, dXi[0], Ti, Di),
+            self._ln_bwd_job(pl, dXf, xi[Li], IMG + "layernorm.weight", IMG + "layernorm.bias", mf, rf, i_in, Ri, Di),
             text_ln2_bwd(nl - 1, 0) if Lt == nl else None])
 
         t_dpre = alloc("t.dpre", (Tt, Dt))
@@ -670,34 +741,57 @@ class Engine:
             t_dfm = DF_[l % 3]["dfm"] if p_h > 0 else t_df     # gradient w.r.t. the (dropped) FFN output dense
             t_dam = T_[l & 1]["dam"] if p_h > 0 else t_da      # gradient w.r.t. the (dropped) attention output dense
             i_dh, i_dxp, i_dqkv = (I_[l & 1][k] for k in ("dh", "dxp", "dqkv"))
+            i_dx = i_in if l == Li - 1 else dXi[ci]            # gradient at this image layer's output
+            # r*: the same gradients as the blocks behind the attention core see them -- the buffers above, or in a compact
+            # last layer its [B, D] panels
+            Mt, Mi = (a["rows"] if has_t else 0), (b_["rows"] if has_i else 0)
+            tp_l, tpd_l = (a["tp"], a["tpd"]) if has_t else ({}, {})
+            rt_df = rt_dfm = rt_dh = rt_dy = rt_da = rt_dam = rt_dctx = ri_dh = ri_dw = ri_dxp = ri_dctx = None
+            if has_t:
+                rt_df, rt_dfm, rt_dh, rt_dy, rt_da, rt_dam, rt_dctx = (t_df, t_dfm, t_dh, t_dy, t_da, t_dam, t_dctx) if Mt == Tt else \
+                    (tc["df"], tc["df"], tc["dh"], tc["dy"], tc["da"], tc["da"], tc["dctx"])
+            if has_i:
+                ri_dh, ri_dw, ri_dxp, ri_dctx = (i_dh, i_dw, i_dxp, i_dctx) if Mi == Ti else (ic["dh"], ic["dw"], ic["dxp"], ic["dctx"])
             # d gelu_in = (d_out @ W2) * gelu'(h)
             pr = []
             if has_t:
-                pr.append(self._dgrad_prob(t_dfm, self.w(LT + "output.dense.weight"), t_dh, Tt, Dt, It, mul=a["h"], deriv_aux=DERIV_AUX, **tp))
+                pr.append(self._dgrad_prob(rt_dfm, self.w(LT + "output.dense.weight"), rt_dh, Mt, Dt, It, mul=a["h"], deriv_aux=DERIV_AUX, **tp_l))
             if has_i:
-                pr.append(self._dgrad_prob(dXi[ci], self.w(LI + "output.dense.weight"), i_dh, Ti, Di, Ii, mul=b_["h"], deriv_aux=DERIV_AUX,
+                pr.append(self._dgrad_prob(i_dx, self.w(LI + "output.dense.weight"), ri_dh, Mi, Di, Ii, mul=b_["h"], deriv_aux=DERIV_AUX,
                                            **quick))
             self._gemm(pl, s, pr, False, True)
             # through W1 (text adds the residual branch df)
             pr = []
             if has_t:
-                pr.append(self._dgrad_prob(t_dh, self.w(LT + "intermediate.dense.weight"), t_dy, Tt, It, Dt, residual=t_df, **tp))
+                pr.append(self._dgrad_prob(rt_dh, self.w(LT + "intermediate.dense.weight"), rt_dy, Mt, It, Dt, residual=rt_df, **tp_l))
             if has_i:
-                pr.append(self._dgrad_prob(i_dh, self.w(LI + "intermediate.dense.weight"), i_dw, Ti, Ii, Di))
+                pr.append(self._dgrad_prob(ri_dh, self.w(LI + "intermediate.dense.weight"), ri_dw, Mi, Ii, Di))
             self._gemm(pl, s, pr, False, True)
             self._ln_bwd(pl, s, [
-                self._ln_bwd_job(pl, t_dy, a["a"], LT + "attention.output.LayerNorm.weight",
-                                 LT + "attention.output.LayerNorm.bias", a["m1"], a["r1"], t_da, Tt, Dt,
-                                 dx_drop=t_dam if p_h > 0 else None, drop=site(p_h, 16 * (l + 1) + 2), **tpd) if has_t else None,
-                self._ln_bwd_job(pl, i_dw, b_["xp"], LI + "layernorm_after.weight", LI + "layernorm_after.bias", b_["m2"],
-                                 b_["r2"], i_dxp, Ti, Di, dx_add=dXi[ci]) if has_i else None])
+                self._ln_bwd_job(pl, rt_dy, a["a"], LT + "attention.output.LayerNorm.weight",
+                                 LT + "attention.output.LayerNorm.bias", a["m1"], a["r1"], rt_da, Mt, Dt,
+                                 dx_drop=rt_dam if p_h > 0 else None, drop=site(p_h, 16 * (l + 1) + 2), **tpd_l) if has_t else None,
+                self._ln_bwd_job(pl, ri_dw, b_["xp"], LI + "layernorm_after.weight", LI + "layernorm_after.bias", b_["m2"],
+                                 b_["r2"], ri_dxp, Mi, Di, dx_add=i_dx) if has_i else None])
             # through the attention output projection
             pr = []
             if has_t:
-                pr.append(self._dgrad_prob(t_dam, self.w(LT + "attention.output.dense.weight"), t_dctx, Tt, Dt, Dt, **tp))
+                pr.append(self._dgrad_prob(rt_dam, self.w(LT + "attention.output.dense.weight"), rt_dctx, Mt, Dt, Dt, **tp_l))
             if has_i:
-                pr.append(self._dgrad_prob(i_dxp, self.w(LI + "attention.output.dense.weight"), i_dctx, Ti, Di, Di))
+                pr.append(self._dgrad_prob(ri_dxp, self.w(LI + "attention.output.dense.weight"), ri_dctx, Mi, Di, Di))
             self._gemm(pl, s, pr, False, True)
+            # a compact last layer ends here: its gradient w.r.t. the attention output goes back to the pooled rows of the full
+            # buffer, zeros everywhere else (no row attends for the loss but the pooled one), and the attention backward runs
+            # as ever.  The same for the residual branch around the attention (text: da, the `residual` of the QKV dgrad; image:
+            # dxp, the `dx_add` of the LayerNorm backward that opens the layer): those kernels add a full buffer, so they get one
+            # that is zero off the pooled rows -- adding the panel behind them instead would round twice.
+            jobs = []
+            if has_t and Mt != Tt:
+                jobs += [dict(t_rows, src=rt_dctx, dst=t_dctx, rows_dev=n_rows), dict(t_rows, src=rt_da, dst=t_da, rows_dev=n_rows)]
+            if has_i and Mi != Ti:
+                jobs += [dict(i_rows, src=ri_dctx, dst=i_dctx), dict(i_rows, src=ri_dxp, dst=i_dxp)]
+            if jobs:
+                self._rows(pl, s, jobs, scatter=True)
             self._attn(pl, s, [
                 dict(qkv=b_["qkv"], out=b_["ctx"], lse=b_["lse"], dout=i_dctx, delta=i_delta, dqkv=i_dqkv, B=B, S=Nt,
                      H=Hi) if has_i else None,
@@ -733,14 +827,14 @@ class Engine:
             # (round 3, with or without a tile order giving every XCD its share of every problem, tools/lab/RESULTS.md (r3k)): the side stream must not hold every workgroup
             # slot -- two 432-tile launches leave 80 of the 512 slots to the main chain.
             wg_t = [
-                    self._wgrad_prob(t_dfm, a["g"], self.g(LT + "output.dense.weight"), self.g(LT + "output.dense.bias"), Tt, Dt, It, **tp),
-                    self._wgrad_prob(t_dh, a["y"], self.g(LT + "intermediate.dense.weight"), self.g(LT + "intermediate.dense.bias"), Tt, It, Dt, **tp),
-                    self._wgrad_prob(t_dam, a["ctx"], self.g(LT + "attention.output.dense.weight"), self.g(LT + "attention.output.dense.bias"), Tt, Dt, Dt, **tp),
+                    self._wgrad_prob(rt_dfm, a["g"], self.g(LT + "output.dense.weight"), self.g(LT + "output.dense.bias"), Mt, Dt, It, **tp_l),
+                    self._wgrad_prob(rt_dh, a["y"], self.g(LT + "intermediate.dense.weight"), self.g(LT + "intermediate.dense.bias"), Mt, It, Dt, **tp_l),
+                    self._wgrad_prob(rt_dam, a["pctx"], self.g(LT + "attention.output.dense.weight"), self.g(LT + "attention.output.dense.bias"), Mt, Dt, Dt, **tp_l),
                     self._wgrad_prob(t_dqkv, xt[l], self.g(LT + "attention.self.query.weight", 3), self.g(LT + "attention.self.query.bias", 3), Tt, 3 * Dt, Dt, **tp)] if has_t else []
             wg_i = [
-                    self._wgrad_prob(dXi[ci], b_["g"], self.g(LI + "output.dense.weight"), self.g(LI + "output.dense.bias"), Ti, Di, Ii),
-                    self._wgrad_prob(i_dh, b_["w"], self.g(LI + "intermediate.dense.weight"), self.g(LI + "intermediate.dense.bias"), Ti, Ii, Di),
-                    self._wgrad_prob(i_dxp, b_["ctx"], self.g(LI + "attention.output.dense.weight"), self.g(LI + "attention.output.dense.bias"), Ti, Di, Di),
+                    self._wgrad_prob(i_dx, b_["g"], self.g(LI + "output.dense.weight"), self.g(LI + "output.dense.bias"), Mi, Di, Ii),
+                    self._wgrad_prob(ri_dh, b_["w"], self.g(LI + "intermediate.dense.weight"), self.g(LI + "intermediate.dense.bias"), Mi, Ii, Di),
+                    self._wgrad_prob(ri_dxp, b_["pctx"], self.g(LI + "attention.output.dense.weight"), self.g(LI + "attention.output.dense.bias"), Mi, Di, Di),
                     self._wgrad_prob(i_dqkv, b_["u"], self.g(LI + "attention.attention.query.weight", 3), self.g(LI + "attention.attention.query.bias", 3), Ti, 3 * Di, Di)] if has_i else []
             self._gemm(pl, s, wg_t, True, True, lane=1)
             self._gemm(pl, s, wg_i, True, True, lane=1)

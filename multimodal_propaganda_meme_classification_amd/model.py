@@ -1275,7 +1275,9 @@ class GraphedStep:
 
     def __init__(self, model: MultimodalClassifier, optimizer: Adam, batch: int, seq_len: int, use_graph: bool = True,
                  reducer=None, overlap_wgrad: bool = True, overlap_optimizer: bool = True, ddp_mode: Optional[str] = None,
-                 scaler: Optional["GradScaler"] = None):
+                 scaler: Optional["GradScaler"] = None, last_rows: str = "pooled"):
+        # last_rows: "pooled" computes, behind the last attention of each tower, only the rows the pooling reads (Engine.plan);
+        # "all" every row.  self.plan.last_rows tells which form the step runs.
         self.model, self.opt = model, optimizer
         optimizer._model = model
         optimizer._resolve_skip(model)
@@ -1288,7 +1290,7 @@ class GraphedStep:
             optimizer._attach_scaler(scaler)
         self.scaler = scaler
         eng = model._get_engine()
-        self.plan = eng.plan(batch, seq_len, True, gather_world=(reducer.world if reducer is not None else 0))
+        self.plan = eng.plan(batch, seq_len, True, gather_world=(reducer.world if reducer is not None else 0), last_rows=last_rows)
         if model.weights_changed():
             model.refresh_shadow()
         from . import ddp as _ddp

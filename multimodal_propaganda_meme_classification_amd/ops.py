@@ -327,6 +327,36 @@ def unpack_rows(src, plan, D):
     return dst
 
 
+def _rows_jobs(jobs, scatter: bool):
+    """jobs: dicts of src, dst and the rows' names -- idx (int32 device tensor, ascending) or stride / offset -- plus, for a
+    scatter, an optional rows_dev (int32[1]).  The full side is [rows, D], the compact side [n, D]."""
+    assert 1 <= len(jobs) <= _lib.MH_ROWS_MAX_JOBS
+    arr = (_lib.MhRowsJob * len(jobs))()
+    for e, j in zip(arr, jobs):
+        src, dst, idx = _chk(j["src"], BF16, "src"), _chk(j["dst"], BF16, "dst"), j.get("idx")
+        assert src.dim() == 2 and dst.dim() == 2 and src.dtype == dst.dtype and src.shape[1] == dst.shape[1]
+        full, compact = (dst, src) if scatter else (src, dst)
+        n, D = compact.shape
+        if idx is not None:
+            _chk(idx, torch.int32, "idx")
+            assert idx.numel() == n
+        e.src, e.dst, e.idx, e.rows_dev = _p(src), _p(dst), _p(idx), _p(j.get("rows_dev") if scatter else None)
+        e.n, e.rows, e.D, e.stride, e.offset = n, full.shape[0], D, int(j.get("stride", 0)), int(j.get("offset", 0))
+    return arr
+
+
+def rows_gather(jobs):
+    """dst[b] = src[row(b)] for every job, one launch (mh_rows_gather)."""
+    arr = _rows_jobs(jobs, False)
+    check(_L(jobs[0]["src"]).mh_rows_gather(arr, len(jobs), _stream()), "mh_rows_gather")
+
+
+def rows_scatter_zero(jobs):
+    """dst[row(b)] = src[b], every other row of dst (up to rows_dev) zero, for every job, one launch (mh_rows_scatter_zero)."""
+    arr = _rows_jobs(jobs, True)
+    check(_L(jobs[0]["src"]).mh_rows_scatter_zero(arr, len(jobs), _stream()), "mh_rows_scatter_zero")
+
+
 def attn_fwd_packed(qkv, plan, B, S, H, drop=None):
     """qkv: packed rows [B*S (max), 3*H*64]; sequences delimited by plan['cu']."""
     _chk(qkv, BF16, "qkv")
