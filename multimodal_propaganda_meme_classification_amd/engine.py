@@ -18,19 +18,18 @@ example_scripts/Multimodal_example_task2C.txt:175,183 and the step at :200-223.
 from __future__ import annotations
 
 import ctypes as C
-import os
+from collections import namedtuple
 from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
 from . import _lib
-from ._lib import (MH_GEMM_ACCUM, MH_GEMM_DERIV_AUX, MH_GEMM_GELU, MH_GEMM_OUT_F32, MH_GEMM_QUICK_GELU, MhAttnProblem, MhColsumJob, MhGemmProblem, MhHeadGrads,
+from ._lib import (MH_GEMM_DERIV_AUX, MH_GEMM_GELU, MH_GEMM_OUT_F32, MH_GEMM_QUICK_GELU, MhAttnProblem, MhColsumJob, MhGemmProblem, MhHeadGrads,
                    MhHeadParams, MhLnBwdJob, MhLnFwdJob, MhRowsJob)
 from .config import Layout, ModelConfig
 
 BF16, F32, I64 = torch.bfloat16, torch.float32, torch.int64
-LN_PARTS = int(os.environ.get("MEMEHIP_LN_PARTS", "512"))     # workgroups (= sets of dgamma/dbeta partials) per LayerNorm backward
-DERIV_AUX = os.environ.get("MEMEHIP_GEMM_DERIV_AUX", "1") != "0"     # FFN-up epilogue stores gelu'(x) for the backward (A/B: 0 = store x)
+LN_PARTS = 512     # workgroups (= sets of dgamma/dbeta partials) per LayerNorm backward
 
 LAUNCH, PY, WAIT = "launch", "py", "wait"
 
@@ -169,8 +168,7 @@ class Engine:
         assert SH.dtype == self.T16
         self.lib = _lib.load(self.kind)
         self.gscale = cfg.stream_scale          # scale carried by the 16-bit gradient streams
-        # padding-free text tower (rows with attention_mask == 0 are never computed); MEMEHIP_PACK_TEXT=0 for A/B runs
-        self.pack_text = bool(getattr(cfg, "pack_text", True)) and os.environ.get("MEMEHIP_PACK_TEXT", "1") != "0"
+        self.pack_text = cfg.pack_text          # padding-free text tower (rows with attention_mask == 0 are never computed)
         self.plans: Dict[Tuple[int, int], Plan] = {}
         # one byte per word-embedding row: has it ever received a gradient?  (rows that have not keep g = m = v = 0,
         # for which Adam is the identity: model.Adam skips them, mh_adam_step_rows)
@@ -196,152 +194,6 @@ class Engine:
         s = self.layout.spec[name]
         assert s.offset + s.numel * count <= self.layout.n_shadow, name
         return self.SH[s.offset:s.offset + s.numel * count]
-
-    # ---- call builders ---------------------------------------------------------------------------------
-    def _gemm(self, plan: Plan, seg: Segment, probs: List[dict], a_k: bool, b_k: bool, lane: int = 0):
-        if not probs:
-            return
-        n = len(probs)
-        assert n <= _lib.MH_GEMM_MAX_GROUP
-        arr = (MhGemmProblem * n)()
-        for i, d in enumerate(probs):
-            A, Bm, Cm = d["A"], d["B"], d["C"]
-            M, N, K = d["M"], d["N"], d["K"]
-            lda, ldb, ldc = d["lda"], d["ldb"], d["ldc"]
-            assert A.dtype == self.T16 and Bm.dtype == self.T16 and Cm.dtype in (self.T16, F32)
-            a_need = (K - 1) * lda + M if a_k else (M - 1) * lda + K
-            b_need = (K - 1) * ldb + N if b_k else (N - 1) * ldb + K
-            assert A.numel() >= a_need and Bm.numel() >= b_need and Cm.numel() >= (M - 1) * ldc + N, (M, N, K)
-            for key, dt, need in (("bias", F32, N), ("residual", self.T16, (M - 1) * ldc + N), ("aux", self.T16, (M - 1) * ldc + N),
-                                  ("mul", self.T16, (M - 1) * ldc + N), ("rowsum", F32, M)):
-                t = d.get(key)
-                assert t is None or (t.dtype == dt and t.numel() >= need), key
-            e = arr[i]
-            e.A, e.B, e.C = _ptr(A), _ptr(Bm), _ptr(Cm)
-            e.bias, e.residual, e.aux = _ptr(d.get("bias")), _ptr(d.get("residual")), _ptr(d.get("aux"))
-            e.mul, e.rowsum = _ptr(d.get("mul")), _ptr(d.get("rowsum"))
-            e.M, e.N, e.K, e.lda, e.ldb, e.ldc = M, N, K, lda, ldb, ldc
-            e.flags = (MH_GEMM_GELU if d.get("gelu") else 0) | (MH_GEMM_OUT_F32 if Cm.dtype == F32 else 0) | \
-                      (MH_GEMM_ACCUM if d.get("accum") else 0) | (MH_GEMM_QUICK_GELU if d.get("quick") else 0) | \
-                      (MH_GEMM_DERIV_AUX if d.get("deriv_aux") else 0)
-            e.alpha = float(d.get("alpha", 1.0))
-            if d.get("drop") is not None:
-                e.drop_rng, e.drop_p, e.drop_stream = d["drop"]
-                e.drop_rows = _ptr(d.get("drop_rows"))
-            e.rows_dev = _ptr(d.get("rows_dev"))
-        plan.keep.append(arr)
-        fl = [2.0 * d["M"] * d["N"] * d["K"] for d in probs]
-        dyn = float(sum(x for x, d in zip(fl, probs) if d.get("rows_dev") is not None))    # scales with the live rows
-        fixed = float(sum(fl)) - dyn
-        plan.gemm_flops += fixed + dyn
-        plan.gemm_flops_dyn += dyn
-        seg.c("mh_gemm_bf16_grouped", arr, n, int(a_k), int(b_k), tag=f"gemm<{int(a_k)},{int(b_k)}>", work=(fixed, dyn),
-              lane=lane)
-
-    @staticmethod
-    def _fwd_prob(x, w, out, T, N, K, **kw):
-        return dict(A=x, B=w, C=out, M=T, N=N, K=K, lda=K, ldb=K, ldc=N, **kw)
-
-    @staticmethod
-    def _dgrad_prob(dy, w, out, T, N_out, K_in, **kw):
-        # out[T, K_in] = dy[T, N_out] @ w[N_out, K_in]
-        return dict(A=dy, B=w, C=out, M=T, N=K_in, K=N_out, lda=N_out, ldb=K_in, ldc=K_in, **kw)
-
-    def _wgrad_prob(self, dy, x, dw, db, T, N_out, K_in, **kw):
-        # dw[N_out, K_in] = dy[T, N_out]^T @ x[T, K_in]   (dy carries the gradient-stream scale: alpha removes it)
-        return dict(A=dy, B=x, C=dw, M=N_out, N=K_in, K=T, lda=N_out, ldb=K_in, ldc=K_in, rowsum=db,
-                    alpha=1.0 / self.gscale, **kw)
-
-    @staticmethod
-    def _ln_groups(by_d):
-        if os.environ.get("MEMEHIP_LN_GROUP", "1") == "0":      # A/B switch: one launch per LayerNorm
-            return [(D, [j]) for D, js in by_d.items() for j in js]
-        return list(by_d.items())
-
-    def _ln_fwd_job(self, x, gname, bname, y, mean, rstd, rows, D, eps, y32=None, rows_dev=None):
-        return dict(x=x, gamma=self.p(gname), beta=self.p(bname), y=y, y32=y32, mean=mean, rstd=rstd, rows=rows, D=D,
-                    eps=float(eps), rows_dev=rows_dev)
-
-    def _ln_fwd(self, plan: Plan, seg: Segment, jobs: List[Optional[dict]]):
-        """LayerNorms that sit at the same point of the lockstep schedule go out as ONE grouped launch per width."""
-        by_d: Dict[int, List[dict]] = {}
-        for j in jobs:
-            if j is not None:
-                by_d.setdefault(j["D"], []).append(j)
-        for D, js in self._ln_groups(by_d):
-            assert len(js) <= _lib.MH_LN_MAX_JOBS
-            arr = (MhLnFwdJob * len(js))()
-            for e, j in zip(arr, js):
-                assert j["x"].numel() >= j["rows"] * D and j["y"].numel() >= j["rows"] * D
-                e.x, e.gamma, e.beta, e.y, e.y_f32 = _ptr(j["x"]), _ptr(j["gamma"]), _ptr(j["beta"]), _ptr(j["y"]), _ptr(j["y32"])
-                e.mean, e.rstd, e.rows, e.eps = _ptr(j["mean"]), _ptr(j["rstd"]), j["rows"], j["eps"]
-                e.rows_dev = _ptr(j["rows_dev"])
-            plan.keep.append(arr)
-            seg.c("mh_layernorm_fwd_grouped", arr, len(js), D)
-
-    def _ln_bwd_job(self, plan, dy, x, gname, bname, mean, rstd, dx, rows, D, dx_add=None, dx_drop=None, drop=None,
-                    rows_dev=None, drop_rows=None):
-        part = torch.empty((2, LN_PARTS, D), dtype=F32, device=self.dev)
-        plan.buf[f"lnpart.{gname}"] = part
-        plan._ln_jobs.setdefault(D, []).append((part, self.g(gname), self.g(bname)))
-        rng, p_, sid = drop if (drop is not None and dx_drop is not None) else (None, 0.0, 0)
-        return dict(dy=dy, x=x, gamma=self.p(gname), mean=mean, rstd=rstd, dx_add=dx_add, dx=dx, part=part,
-                    dx_drop=dx_drop if rng is not None else None, rng=rng, p=float(p_), sid=int(sid), rows=rows, D=D,
-                    rows_dev=rows_dev, drop_rows=drop_rows if rng is not None else None)
-
-    def _ln_bwd(self, plan: Plan, seg: Segment, jobs: List[Optional[dict]]):
-        by_d: Dict[int, List[dict]] = {}
-        for j in jobs:
-            if j is not None:
-                by_d.setdefault(j["D"], []).append(j)
-        for D, js in self._ln_groups(by_d):
-            assert len(js) <= _lib.MH_LN_MAX_JOBS
-            arr = (MhLnBwdJob * len(js))()
-            for e, j in zip(arr, js):
-                n = j["rows"] * D
-                assert j["dy"].numel() >= n and j["x"].numel() >= n and j["dx"].numel() >= n
-                assert j["dx_add"] is None or j["dx_add"].numel() >= n
-                e.dy, e.x, e.gamma, e.mean, e.rstd = _ptr(j["dy"]), _ptr(j["x"]), _ptr(j["gamma"]), _ptr(j["mean"]), _ptr(j["rstd"])
-                e.dx_add, e.dx, e.part, e.dx_drop, e.rng = _ptr(j["dx_add"]), _ptr(j["dx"]), _ptr(j["part"]), _ptr(j["dx_drop"]), j["rng"]
-                e.n_part, e.rows, e.drop_p, e.drop_stream = LN_PARTS, j["rows"], j["p"], j["sid"]
-                e.rows_dev, e.drop_rows = _ptr(j["rows_dev"]), _ptr(j["drop_rows"])
-            plan.keep.append(arr)
-            seg.c("mh_layernorm_bwd_grouped", arr, len(js), D)
-
-    def _attn(self, plan: Plan, seg: Segment, probs: List[Optional[dict]], backward: bool):
-        """Both towers' attention of a layer pair as one grouped call (one launch per kernel when the pair fits the
-        dual kernels, see include/memehip.h: mh_attn_fwd_grouped)."""
-        probs = [d for d in probs if d is not None]
-        if not probs:
-            return
-        arr = (MhAttnProblem * len(probs))()
-        for e, d in zip(arr, probs):
-            for k in ("qkv", "key_mask", "out", "lse", "dout", "delta", "dqkv", "cu", "row_map"):
-                setattr(e, k, _ptr(d.get(k)))
-            rng, p_, sid = d.get("drop") or (None, 0.0, 0)
-            e.rng, e.drop_p, e.drop_stream = rng, float(p_), int(sid)
-            e.B, e.S, e.H = d["B"], d["S"], d["H"]
-            n = d["B"] * d["S"] * d["H"] * 64
-            assert d["qkv"].numel() >= 3 * n and d["out"].numel() >= n and d["lse"].numel() >= d["B"] * d["H"] * d["S"]
-            if backward:
-                assert d["dout"].numel() >= n and d["dqkv"].numel() >= 3 * n and d["delta"].numel() >= d["B"] * d["H"] * d["S"]
-        plan.keep.append(arr)
-        seg.c("mh_attn_bwd_grouped" if backward else "mh_attn_fwd_grouped", arr, len(probs))
-
-    def _rows(self, plan: Plan, seg: Segment, jobs: List[dict], scatter: bool):
-        """Row jobs of the last layer as ONE launch: gather (full -> compact [n, D]) or scatter with zero fill (compact -> full).
-        A job names its rows by a device index array `idx` (ascending) or as b * stride + offset."""
-        assert 1 <= len(jobs) <= _lib.MH_ROWS_MAX_JOBS
-        arr = (MhRowsJob * len(jobs))()
-        for e, j in zip(arr, jobs):
-            src, dst, idx, n, rows, D = j["src"], j["dst"], j.get("idx"), j["n"], j["rows"], j["D"]
-            full, compact = (dst, src) if scatter else (src, dst)
-            assert src.dtype == self.T16 and dst.dtype == self.T16 and full.numel() >= rows * D and compact.numel() >= n * D
-            assert idx is None or (idx.dtype == torch.int32 and idx.numel() >= n)
-            e.src, e.dst, e.idx, e.rows_dev = _ptr(src), _ptr(dst), _ptr(idx), _ptr(j.get("rows_dev") if scatter else None)
-            e.n, e.rows, e.D, e.stride, e.offset = n, rows, D, j.get("stride", 0), j.get("offset", 0)
-        plan.keep.append(arr)
-        seg.c("mh_rows_scatter_zero" if scatter else "mh_rows_gather", arr, len(jobs))
 
     def before_backward(self, plan: Plan):
         """Each plan re-zeroes the word-embedding gradient rows IT touched last time (the table gradient is dense,
@@ -371,7 +223,7 @@ class Engine:
         gather_world = W > 0 (data parallel): the embedding-table gradients are built from the all-gathered token ids
         and embedding-gradient rows of all W ranks (6 MB per rank) instead of all-reducing the dense 196-MB table.
         last_rows = "pooled" (default): behind the attention of each tower's last layer, only the rows the pooling reads are
-        computed (see _build); "all" computes every row.  Plans whose full last hidden states are read, or that carry
+        computed (see _PlanBuilder.last_layer_form); "all" computes every row.  Plans whose full last hidden states are read, or that carry
         dropout, are built as "all" whatever is asked for: ``plan.last_rows`` tells which form a plan has."""
         if last_rows not in ("pooled", "all"):
             raise ValueError(f"last_rows must be 'pooled' or 'all', got {last_rows!r}")
@@ -386,496 +238,674 @@ class Engine:
 
     def _build(self, B: int, S: int, dropout_on: bool = False, gather_world: int = 0, pack: bool = False,
                features=False, last_rows: str = "pooled") -> Plan:
-        cfg, t, v = self.cfg, self.cfg.text, self.cfg.image
+        b = _PlanBuilder(self, B, S, dropout_on, gather_world, pack, features, last_rows)
+        nl = max(b.text.L, b.image.L)
+        b.text_embed()
+        b.image_embed()
+        b.last_layer_form()
+        b.layer_buffers()
+        for l in range(nl):
+            b.fwd_layer(l)
+        b.head_and_loss()
+        b.bwd_head()
+        for l in range(nl - 1, -1, -1):
+            b.bwd_layer(l)
+        b.bwd_embed()
+        pl = b.pl
+        pl.n_launches = sum(1 for sg in [pl.fwd, pl.loss] + pl.bwd for c in sg.calls if c[0] is not None)
+        return pl
+
+
+# ---- what a plan is built from: typed jobs, per-layer activations and gradients, one record per tower ------------------
+
+# A dropout site: rng = pointer to int32[4] {seed_lo, seed_hi, step, -} (None = off), probability, site id.
+Site = namedtuple("Site", "rng p sid", defaults=(None, 0.0, 0))
+NO_DROP = Site()
+
+# One problem of a grouped GEMM launch (MhGemmProblem); `drop` = the dropout site of the epilogue.
+Gemm = namedtuple("Gemm", "A B C M N K lda ldb ldc bias residual aux mul rowsum gelu quick deriv_aux alpha drop rows_dev drop_rows",
+                  defaults=(None, None, None, None, None, False, False, False, 1.0, NO_DROP, None, None))
+LnFwd = namedtuple("LnFwd", "x gamma beta y mean rstd rows D eps y32 rows_dev", defaults=(None, None))
+LnBwd = namedtuple("LnBwd", "dy x gamma mean rstd dx part rows D dx_add dx_drop drop rows_dev drop_rows",
+                   defaults=(None, None, NO_DROP, None, None))
+Attn = namedtuple("Attn", "qkv out lse B S H key_mask cu row_map drop dout delta dqkv", defaults=(None, None, None, NO_DROP, None, None, None))
+# n rows of a [rows, D] buffer, named by a device index array `idx` (ascending) or as b * stride + offset
+RowsJob = namedtuple("RowsJob", "n rows D idx stride offset src dst rows_dev", defaults=(None, 0, 0, None, None, None))
+
+# Saved activations of one layer.  "rows" = the rows of everything behind its attention core ("pctx" / "x": the operands of the
+# first such block, the attention output and the layer input, at those rows: gathered copies in a compact last layer).
+TextActs = namedtuple("TextActs", "qkv ctx lse a y m1 r1 h g f m2 r2 pctx x rows")
+ImageActs = namedtuple("ImageActs", "u m1 r1 qkv ctx lse xp w m2 r2 h g pctx x rows")
+
+# The operands of a layer's four Linears by what they are to the GEMM (the role table of a tower, Tower.roles):
+#   attn_in    input of the QKV projection                          text x_l     image u
+#   proj_out   output of the attention output projection                 a            xp
+#   ffn_in     input of FFN up                                           y            w
+#   ffn_res    residual added to FFN down (post-LN | pre-LN)             y            xp
+#   ffn_out    output of FFN down                                        f            x_{l+1}
+Roles = namedtuple("Roles", "attn_in proj_out ffn_in ffn_res ffn_out")
+
+# The gradient buffers of one layer of one tower as the blocks behind the attention core see them: the parity / rotation set of
+# the layer, or in a compact last layer its [B, D] panels (res_full / dctx_full / dqkv / d_in are full size either way).
+#   d_out    at the FFN-down output         text: dfm = df times its dropout mask (df itself without dropout)   image: the layer's incoming gradient
+#   dh       at the GELU input
+#   d_mid    at the FFN input               text: dy     image: dw
+#   d_proj   at the out-proj output         text: dam = da times its dropout mask (da itself without dropout)   image: dxp
+#   res      the residual branch around the attention      text: da     image: dxp
+#   dctx     at the attention output
+#   d_in     at the QKV input               text: the gradient at the output of the layer below                 image: du
+#   df       text only: at the FFN-down output in front of its dropout = the residual branch around the FFN
+Grads = namedtuple("Grads", "d_out dh d_mid d_proj res dctx res_full dctx_full dqkv d_in df", defaults=(None,))
+
+
+class Tower:
+    """What the lockstep schedule has to know about one encoder tower; built once per plan."""
+
+    def __init__(self, pre, c, T, S, attn, ln_mid, post_ln, quick=False, p_h=0.0, p_a=0.0):
+        self.pre, self.T, self.S = pre, T, S        # parameter-name prefix; rows of a full-size activation; sequence length
+        self.D, self.I, self.H, self.L, self.eps = c.hidden, c.intermediate, c.heads, c.layers, c.ln_eps
+        # the stems that differ: the fused q/k/v projection, the LayerNorm between the attention block and the FFN
+        self.attn, self.ln_mid = attn, ln_mid
+        self.post_ln, self.quick = post_ln, quick   # BERT: LayerNorm behind each residual sum, ViT: in front of each block; quick-GELU
+        self.p_h, self.p_a = p_h, p_a               # dropout behind the two residual Linears / on the attention probabilities (BERT only)
+        # padding-free text tower: live-row count and row map on the device, the packed key mask and sequence offsets
+        self.rows_dev = self.row_map = self.key_mask = self.cu = None
+        self.pool, self.compact = None, 0           # the rows the pooling reads (a RowsJob template); rows of the compact last layer, 0 = none
+        self.x, self.acts = [], []                  # layer inputs (x[L] = the tower's last hidden state); per-layer saved activations
+        self.dX, self.d_last = [], None             # gradient at a layer's output (rotation of three); the one that enters the last layer
+        self.grads, self.delta = [], None           # per-layer Grads; the attention backward's row sums
+
+    def rows(self, l: int) -> int:
+        """Rows of the blocks behind the attention core of layer l."""
+        return self.compact if (self.compact and l == self.L - 1) else self.T
+
+    @property
+    def out_rows(self) -> int:
+        """Rows of the tower's last hidden state."""
+        return self.compact or self.T
+
+    def live(self, M: int, drop: bool = False) -> dict:
+        """Clamp arguments of a GEMM problem / LayerNorm job over M rows (a [B, D] panel is never clamped by the live-row count)."""
+        if self.rows_dev is None or M != self.T:
+            return {}
+        return dict(rows_dev=self.rows_dev, drop_rows=self.row_map) if drop else dict(rows_dev=self.rows_dev)
+
+    def name(self, l: int, stem: str) -> str:
+        return f"{self.pre}encoder.layer.{l}.{stem}"
+
+    def roles(self, l: int) -> Roles:
+        a = self.acts[l]
+        return Roles(self.x[l], a.a, a.y, a.y, a.f) if self.post_ln else Roles(a.u, a.xp, a.w, a.xp, self.x[l + 1])
+
+    def d_x(self, l: int) -> torch.Tensor:
+        """Gradient at the output of layer l (l = -1: at the tower's input)."""
+        return self.d_last if l == self.L - 1 else self.dX[(self.L - 1 - l) % 3]
+
+
+def _fill_ln_fwd(e: MhLnFwdJob, j: LnFwd):
+    assert j.x.numel() >= j.rows * j.D and j.y.numel() >= j.rows * j.D
+    e.x, e.gamma, e.beta, e.y, e.y_f32 = _ptr(j.x), _ptr(j.gamma), _ptr(j.beta), _ptr(j.y), _ptr(j.y32)
+    e.mean, e.rstd, e.rows, e.eps = _ptr(j.mean), _ptr(j.rstd), j.rows, j.eps
+    e.rows_dev = _ptr(j.rows_dev)
+
+
+def _fill_ln_bwd(e: MhLnBwdJob, j: LnBwd):
+    n = j.rows * j.D
+    assert j.dy.numel() >= n and j.x.numel() >= n and j.dx.numel() >= n
+    assert j.dx_add is None or j.dx_add.numel() >= n
+    e.dy, e.x, e.gamma, e.mean, e.rstd = _ptr(j.dy), _ptr(j.x), _ptr(j.gamma), _ptr(j.mean), _ptr(j.rstd)
+    e.dx_add, e.dx, e.part, e.dx_drop, e.rng = _ptr(j.dx_add), _ptr(j.dx), _ptr(j.part), _ptr(j.dx_drop), j.drop.rng
+    e.n_part, e.rows, e.drop_p, e.drop_stream = LN_PARTS, j.rows, j.drop.p, j.drop.sid
+    e.rows_dev, e.drop_rows = _ptr(j.rows_dev), _ptr(j.drop_rows)
+
+
+TXT, IMG = "bert.", "image_model."
+
+
+class _PlanBuilder:
+    """Builds one Plan, step by step in execution order (Engine._build lists the steps).  What the steps share lives here:
+    the plan, the two Tower records, the dropout sites and `alloc`."""
+
+    def __init__(self, eng: Engine, B: int, S: int, dropout_on: bool, gather_world: int, pack: bool, features, last_rows: str):
+        cfg, t, v = eng.cfg, eng.cfg.text, eng.cfg.image
         if S > t.max_position:
             raise ValueError(f"sequence length {S} > max_position {t.max_position}")
         if B > 1024:
             raise ValueError("batch > 1024 not supported by the loss kernel")
-        pl = Plan(B, S, self.lib)
-        BF16 = self.T16          # every 16-bit buffer below uses the configured storage type
-        # dropout sites: (rng words pointer, p, site id); None when off.  rng = int32[4] {seed_lo, seed_hi, step, -}
-        rng_t = torch.zeros(4, dtype=torch.int32, device=self.dev)
-        pl.buf["rng"] = rng_t
-        pl.dropout_on = dropout_on
-        p_h = t.hidden_dropout if dropout_on else 0.0
-        p_a = t.attention_dropout if dropout_on else 0.0
-        p_head = cfg.head_dropout if dropout_on else 0.0
+        self.eng, self.cfg, self.B, self.S = eng, cfg, B, S
+        self.T16 = eng.T16          # every 16-bit buffer uses the configured storage type
+        self.pl = pl = Plan(B, S, eng.lib)
+        self.gather_world, self.last_rows = gather_world, last_rows
+        pl.dropout_on, pl.packed, pl.features = dropout_on, pack, features
+        self.rng = self.alloc("rng", (4,), torch.int32, zero=True)     # the words every dropout site reads
+        self.p_head = cfg.head_dropout if dropout_on else 0.0
+        self.pool_index = 0 if cfg.pool == "cls" else S - 1
+        self.text = Tower(TXT, t, B * S, S, "attention.self.", "attention.output.LayerNorm", post_ln=True,
+                          p_h=t.hidden_dropout if dropout_on else 0.0, p_a=t.attention_dropout if dropout_on else 0.0)
+        self.image = Tower(IMG, v, B * v.n_tokens, v.n_tokens, "attention.attention.", "layernorm_after", post_ln=False,
+                           quick=v.act == "quick_gelu")
+        self.towers = (self.text, self.image)
 
-        def site(p_, sid):
-            return (rng_t.data_ptr(), float(p_), int(sid)) if p_ > 0 else None
+    def alloc(self, name, shape, dtype=None, zero=False):
+        tns = (torch.zeros if zero else torch.empty)(shape, dtype=dtype or self.T16, device=self.eng.dev)
+        self.pl.buf[name] = tns
+        return tns
 
-        def site_args(p_, sid):
-            return (rng_t.data_ptr(), float(p_), int(sid)) if p_ > 0 else (None, 0.0, 0)
-        dev = self.dev
-        Dt, It, Ht, Lt = t.hidden, t.intermediate, t.heads, t.layers
-        Di, Ii, Hi, Li = v.hidden, v.intermediate, v.heads, v.layers
-        Np, Nt = v.n_patches, v.n_tokens
-        Kp = v.channels * v.patch * v.patch
-        Tt, Ti = B * S, B * Nt
-        P_, Cn = cfg.proj, cfg.num_classes
-        # The head reads ONE row per sample from each tower (the pooled text position, the ViT class token), and behind the
-        # attention core every block of a layer is row-wise.  cmp: the last layer of each tower gathers those B rows behind its
-        # attention and runs out-proj, LayerNorms and FFN on [B, D] panels (forward and backward); the out-proj input
-        # gradient is scattered back, with zeros everywhere else, in front of the attention backward.  Not when somebody
-        # reads the full last hidden states ("sequence"), and not with dropout (its masks are indexed by the full row).
-        cmp = last_rows == "pooled" and features != "sequence" and not dropout_on and Lt >= 1 and Li >= 1
-        pl.last_rows = "pooled" if cmp else "all"
-        Rt, Ri = (B, B) if cmp else (Tt, Ti)      # rows of a tower's last hidden state
+    def site(self, p_, sid) -> Site:
+        return Site(self.rng.data_ptr(), float(p_), int(sid)) if p_ > 0 else NO_DROP
 
-        def alloc(name, shape, dtype=BF16, zero=False):
-            tns = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=dev)
-            pl.buf[name] = tns
-            return tns
+    def seg(self, name) -> Segment:
+        s = Segment(name, self.eng.lib)
+        self.pl.bwd.append(s)
+        return s
 
-        # static inputs
-        ids = alloc("ids", (B, S), I64, zero=True)
-        mask = alloc("mask", (B, S), I64, zero=True)
-        image = alloc("image", (B, v.channels, v.image_size, v.image_size), F32, zero=True)
-        labels = alloc("labels", (B,), I64, zero=True)
-        prev_ids = alloc("prev_ids", (B, S), I64, zero=True)
+    # ---- packers: typed jobs -> one prepared grouped launch --------------------------------------------------
+    def _gemm(self, seg: Segment, probs: List[Gemm], a_k: bool, b_k: bool, lane: int = 0):
+        n, pl, T16 = len(probs), self.pl, self.T16
+        assert 1 <= n <= _lib.MH_GEMM_MAX_GROUP
+        arr = (MhGemmProblem * n)()
+        for e, d in zip(arr, probs):
+            A, Bm, Cm, M, N, K, lda, ldb, ldc = d[:9]
+            assert A.dtype == T16 and Bm.dtype == T16 and Cm.dtype in (T16, F32)
+            a_need = (K - 1) * lda + M if a_k else (M - 1) * lda + K
+            b_need = (K - 1) * ldb + N if b_k else (N - 1) * ldb + K
+            assert A.numel() >= a_need and Bm.numel() >= b_need and Cm.numel() >= (M - 1) * ldc + N, (M, N, K)
+            for key, t, dt, need in (("bias", d.bias, F32, N), ("residual", d.residual, T16, (M - 1) * ldc + N),
+                                     ("aux", d.aux, T16, (M - 1) * ldc + N), ("mul", d.mul, T16, (M - 1) * ldc + N),
+                                     ("rowsum", d.rowsum, F32, M)):
+                assert t is None or (t.dtype == dt and t.numel() >= need), key
+            e.A, e.B, e.C = _ptr(A), _ptr(Bm), _ptr(Cm)
+            e.bias, e.residual, e.aux = _ptr(d.bias), _ptr(d.residual), _ptr(d.aux)
+            e.mul, e.rowsum = _ptr(d.mul), _ptr(d.rowsum)
+            e.M, e.N, e.K, e.lda, e.ldb, e.ldc = M, N, K, lda, ldb, ldc
+            e.flags = (MH_GEMM_GELU if d.gelu else 0) | (MH_GEMM_OUT_F32 if Cm.dtype == F32 else 0) | \
+                      (MH_GEMM_QUICK_GELU if d.quick else 0) | (MH_GEMM_DERIV_AUX if d.deriv_aux else 0)
+            e.alpha = float(d.alpha)
+            if d.drop.rng is not None:
+                e.drop_rng, e.drop_p, e.drop_stream = d.drop
+                e.drop_rows = _ptr(d.drop_rows)
+            e.rows_dev = _ptr(d.rows_dev)
+        pl.keep.append(arr)
+        fl = [2.0 * d.M * d.N * d.K for d in probs]
+        dyn = float(sum(x for x, d in zip(fl, probs) if d.rows_dev is not None))    # scales with the live rows
+        fixed = float(sum(fl)) - dyn
+        pl.gemm_flops += fixed + dyn
+        pl.gemm_flops_dyn += dyn
+        seg.c("mh_gemm_bf16_grouped", arr, n, int(a_k), int(b_k), tag=f"gemm<{int(a_k)},{int(b_k)}>", work=(fixed, dyn),
+              lane=lane)
 
-        # ------------------------------------------------------------------ forward ------------------
-        f = pl.fwd
-        TXT, IMG = "bert.", "image_model."
-        # text embeddings (dense [B*S] rows: the tables are indexed by position)
-        pool_index = 0 if cfg.pool == "cls" else S - 1
-        pre0 = alloc("t.pre0", (Tt, Dt))
+    @staticmethod
+    def _fwd_prob(x, w, out, T, N, K, **kw) -> Gemm:
+        return Gemm(x, w, out, T, N, K, lda=K, ldb=K, ldc=N, **kw)
+
+    @staticmethod
+    def _dgrad_prob(dy, w, out, T, N_out, K_in, **kw) -> Gemm:
+        # out[T, K_in] = dy[T, N_out] @ w[N_out, K_in]
+        return Gemm(dy, w, out, T, K_in, N_out, lda=N_out, ldb=K_in, ldc=K_in, **kw)
+
+    def _wgrad_prob(self, dy, x, dw, db, T, N_out, K_in, **kw) -> Gemm:
+        # dw[N_out, K_in] = dy[T, N_out]^T @ x[T, K_in]   (dy carries the gradient-stream scale: alpha removes it)
+        return Gemm(dy, x, dw, N_out, K_in, T, lda=N_out, ldb=K_in, ldc=K_in, rowsum=db, alpha=1.0 / self.eng.gscale, **kw)
+
+    # the three GEMMs of one Linear of layer l of a tower (`stem`.weight / `stem`.bias; count = 3: the fused q/k/v)
+    def _linear(self, tw: Tower, l, stem, x, out, M, N, K, count=1, **kw) -> Gemm:
+        nm = tw.name(l, stem)
+        return self._fwd_prob(x, self.eng.w(nm + ".weight", count), out, M, N, K, bias=self.eng.p(nm + ".bias", count), **kw)
+
+    def _linear_dgrad(self, tw: Tower, l, stem, dy, out, M, N_out, K_in, count=1, **kw) -> Gemm:
+        return self._dgrad_prob(dy, self.eng.w(tw.name(l, stem) + ".weight", count), out, M, N_out, K_in, **kw)
+
+    def _linear_wgrad(self, tw: Tower, l, stem, dy, x, M, N_out, K_in, count=1, **kw) -> Gemm:
+        nm = tw.name(l, stem)
+        return self._wgrad_prob(dy, x, self.eng.g(nm + ".weight", count), self.eng.g(nm + ".bias", count), M, N_out, K_in, **kw)
+
+    def _ln_fwd_job(self, x, name, y, mean, rstd, rows, D, eps, y32=None, rows_dev=None) -> LnFwd:
+        return LnFwd(x, self.eng.p(name + ".weight"), self.eng.p(name + ".bias"), y, mean, rstd, rows, D, float(eps), y32, rows_dev)
+
+    def _ln_bwd_job(self, dy, x, name, mean, rstd, dx, rows, D, dx_add=None, dx_drop=None, drop=NO_DROP, rows_dev=None,
+                    drop_rows=None) -> LnBwd:
+        part = self.alloc(f"lnpart.{name}.weight", (2, LN_PARTS, D), F32)
+        self.pl._ln_jobs.setdefault(D, []).append((part, self.eng.g(name + ".weight"), self.eng.g(name + ".bias")))
+        on = drop.rng is not None and dx_drop is not None
+        return LnBwd(dy, x, self.eng.p(name + ".weight"), mean, rstd, dx, part, rows, D, dx_add, dx_drop if on else None,
+                     drop if on else NO_DROP, rows_dev, drop_rows if on else None)
+
+    def _ln(self, seg: Segment, jobs: list, fn_name: str, struct, fill):
+        """LayerNorms that sit at the same point of the lockstep schedule go out as ONE grouped launch per width."""
+        by_d: Dict[int, list] = {}
+        for j in jobs:
+            if j is not None:
+                by_d.setdefault(j.D, []).append(j)
+        for D, js in by_d.items():
+            assert len(js) <= _lib.MH_LN_MAX_JOBS
+            arr = (struct * len(js))()
+            for e, j in zip(arr, js):
+                fill(e, j)
+            self.pl.keep.append(arr)
+            seg.c(fn_name, arr, len(js), D)
+
+    def _ln_fwd(self, seg: Segment, jobs: List[Optional[LnFwd]]):
+        self._ln(seg, jobs, "mh_layernorm_fwd_grouped", MhLnFwdJob, _fill_ln_fwd)
+
+    def _ln_bwd(self, seg: Segment, jobs: List[Optional[LnBwd]]):
+        self._ln(seg, jobs, "mh_layernorm_bwd_grouped", MhLnBwdJob, _fill_ln_bwd)
+
+    def _attn(self, seg: Segment, probs: List[Attn], backward: bool):
+        """Both towers' attention of a layer pair as one grouped call (one launch per kernel when the pair fits the
+        dual kernels, see include/memehip.h: mh_attn_fwd_grouped)."""
+        arr = (MhAttnProblem * len(probs))()
+        for e, d in zip(arr, probs):
+            for k in ("qkv", "key_mask", "out", "lse", "dout", "delta", "dqkv", "cu", "row_map"):
+                setattr(e, k, _ptr(getattr(d, k)))
+            e.rng, e.drop_p, e.drop_stream = d.drop
+            e.B, e.S, e.H = d.B, d.S, d.H
+            n = d.B * d.S * d.H * 64
+            assert d.qkv.numel() >= 3 * n and d.out.numel() >= n and d.lse.numel() >= d.B * d.H * d.S
+            if backward:
+                assert d.dout.numel() >= n and d.dqkv.numel() >= 3 * n and d.delta.numel() >= d.B * d.H * d.S
+        self.pl.keep.append(arr)
+        seg.c("mh_attn_bwd_grouped" if backward else "mh_attn_fwd_grouped", arr, len(probs))
+
+    def _attn_prob(self, tw: Tower, l: int, **bw) -> Attn:
+        a = tw.acts[l]
+        return Attn(a.qkv, a.ctx, a.lse, self.B, tw.S, tw.H, tw.key_mask, tw.cu, tw.row_map,
+                    self.site(tw.p_a, 16 * (l + 1) + 1), **bw)
+
+    def _rows(self, seg: Segment, jobs: List[RowsJob], scatter: bool):
+        """Row jobs of the last layer as ONE launch: gather (full -> compact [n, D]) or scatter with zero fill (compact -> full)."""
+        if not jobs:
+            return
+        assert len(jobs) <= _lib.MH_ROWS_MAX_JOBS
+        arr = (MhRowsJob * len(jobs))()
+        for e, j in zip(arr, jobs):
+            full, compact = (j.dst, j.src) if scatter else (j.src, j.dst)
+            assert j.src.dtype == self.T16 and j.dst.dtype == self.T16 and full.numel() >= j.rows * j.D and compact.numel() >= j.n * j.D
+            assert j.idx is None or (j.idx.dtype == torch.int32 and j.idx.numel() >= j.n)
+            e.src, e.dst, e.idx, e.rows_dev = _ptr(j.src), _ptr(j.dst), _ptr(j.idx), _ptr(j.rows_dev if scatter else None)
+            e.n, e.rows, e.D, e.stride, e.offset = j.n, j.rows, j.D, j.stride, j.offset
+        self.pl.keep.append(arr)
+        seg.c("mh_rows_scatter_zero" if scatter else "mh_rows_gather", arr, len(jobs))
+
+    # ---- forward --------------------------------------------------------------------------------------------------
+    def text_embed(self):
+        """Text embeddings (dense [B*S] rows: the tables are indexed by position), then the row packing."""
+        eng, f, tw, t, B, S, alloc = self.eng, self.pl.fwd, self.text, self.cfg.text, self.B, self.S, self.alloc
+        Tt, Dt = tw.T, tw.D
+        self.ids, self.mask = alloc("ids", (B, S), I64, zero=True), alloc("mask", (B, S), I64, zero=True)      # static inputs
+        self.prev_ids = alloc("prev_ids", (B, S), I64, zero=True)
+        self.pre0 = alloc("t.pre0", (Tt, Dt))
         x0d = alloc("t.x0", (Tt, Dt))
-        m0, r0 = alloc("t.m0", (Tt,), F32), alloc("t.r0", (Tt,), F32)
-        type0 = self.p(TXT + "embeddings.token_type_embeddings.weight")[:Dt] if t.type_vocab > 0 else None
-        f.c("mh_bert_embed_fwd", _ptr(ids), _ptr(self.p(TXT + "embeddings.word_embeddings.weight")),
-            _ptr(self.p(TXT + "embeddings.position_embeddings.weight")), _ptr(type0),
-            _ptr(self.p(TXT + "embeddings.LayerNorm.weight")), _ptr(self.p(TXT + "embeddings.LayerNorm.bias")),
-            _ptr(pre0), _ptr(x0d), _ptr(m0), _ptr(r0), B, S, Dt, t.vocab_size, float(t.ln_eps), *site_args(p_h, 1))
+        self.m0, self.r0 = alloc("t.m0", (Tt,), F32), alloc("t.r0", (Tt,), F32)
+        type0 = eng.p(TXT + "embeddings.token_type_embeddings.weight")[:Dt] if t.type_vocab > 0 else None
+        f.c("mh_bert_embed_fwd", _ptr(self.ids), _ptr(eng.p(TXT + "embeddings.word_embeddings.weight")),
+            _ptr(eng.p(TXT + "embeddings.position_embeddings.weight")), _ptr(type0),
+            _ptr(eng.p(TXT + "embeddings.LayerNorm.weight")), _ptr(eng.p(TXT + "embeddings.LayerNorm.bias")),
+            _ptr(self.pre0), _ptr(x0d), _ptr(self.m0), _ptr(self.r0), B, S, Dt, t.vocab_size, float(t.ln_eps), *self.site(tw.p_h, 1))
         # padding-free text tower: the encoder layers see only the rows that matter (attention_mask != 0, plus the
         # pooled position), packed back to back.  The row count lives on the device (n_rows): every text launch below
         # is sized for B*S rows and clamps itself at run time, so one plan / one hipGraph serves every batch.
-        pl.packed = pack
-        if pack:
+        if self.pl.packed:
             I32 = torch.int32
             cu, row_map = alloc("pk.cu", (B + 1,), I32, zero=True), alloc("pk.row_map", (Tt,), I32, zero=True)
-            inv_map, pmask = alloc("pk.inv_map", (Tt,), I32, zero=True), alloc("pk.pmask", (Tt,), I64, zero=True)
-            pool_rows, n_rows = alloc("pk.pool_rows", (B,), I32, zero=True), alloc("pk.n_rows", (1,), I32, zero=True)
-            f.c("mh_pack_plan", _ptr(mask), B, S, pool_index, _ptr(cu), _ptr(row_map), _ptr(inv_map), _ptr(pmask),
-                _ptr(pool_rows), _ptr(n_rows))
-            xt = [alloc("t.x0p", (Tt, Dt))]
-            f.c("mh_pack_rows", _ptr(x0d), _ptr(row_map), _ptr(n_rows), _ptr(xt[0]), Tt, Dt)
-            tp = dict(rows_dev=n_rows)                  # every text GEMM problem / LayerNorm job
-            tpd = dict(rows_dev=n_rows, drop_rows=row_map)
+            self.inv_map, pmask = alloc("pk.inv_map", (Tt,), I32, zero=True), alloc("pk.pmask", (Tt,), I64, zero=True)
+            self.pool_rows, n_rows = alloc("pk.pool_rows", (B,), I32, zero=True), alloc("pk.n_rows", (1,), I32, zero=True)
+            f.c("mh_pack_plan", _ptr(self.mask), B, S, self.pool_index, _ptr(cu), _ptr(row_map), _ptr(self.inv_map), _ptr(pmask),
+                _ptr(self.pool_rows), _ptr(n_rows))
+            tw.x.append(alloc("t.x0p", (Tt, Dt)))
+            f.c("mh_pack_rows", _ptr(x0d), _ptr(row_map), _ptr(n_rows), _ptr(tw.x[0]), Tt, Dt)
+            tw.rows_dev, tw.row_map, tw.key_mask, tw.cu = n_rows, row_map, pmask, cu
+            # the pooled rows of the tower's row buffers: by the packing plan's pool_rows, or by arithmetic
+            tw.pool = RowsJob(B, Tt, Dt, idx=self.pool_rows)
         else:
-            cu = row_map = inv_map = pmask = pool_rows = n_rows = None
-            xt = [x0d]
-            tp, tpd = {}, {}
+            self.inv_map = self.pool_rows = None
+            tw.x.append(x0d)
+            tw.key_mask = self.mask
+            tw.pool = RowsJob(B, Tt, Dt, stride=S, offset=self.pool_index)
 
-        def text_attn(a_, sid, **bw):
-            base = dict(qkv=a_["qkv"], out=a_["ctx"], lse=a_["lse"], B=B, S=S, H=Ht, drop=site(p_a, sid), **bw)
-            if pack:
-                return dict(base, key_mask=pmask, cu=cu, row_map=row_map)
-            return dict(base, key_mask=mask)
-
-        # image embeddings
-        Kpp = v.patch_dim_padded                      # contraction of the patch projection (588 -> 640 for CLIP's 14x14 patches)
-        patches = alloc("i.patches", (B * Np, Kpp))
+    def image_embed(self):
+        eng, f, tw, v, B, alloc = self.eng, self.pl.fwd, self.image, self.cfg.image, self.B, self.alloc
+        Np, Ti, Di = v.n_patches, tw.T, tw.D
+        Kp, Kpp = v.patch_dim, v.patch_dim_padded     # contraction of the patch projection (588 -> 640 for CLIP's 14x14 patches)
+        image = alloc("image", (B, v.channels, v.image_size, v.image_size), F32, zero=True)      # static input
+        self.patches = alloc("i.patches", (B * Np, Kpp))
         proj = alloc("i.proj", (B * Np, Di))
-        xi = [alloc("i.x0", (Ti, Di))]
-        wp = self.w(IMG + "embeddings.patch_embeddings.projection.weight")
+        tw.x.append(alloc("i.x0", (Ti, Di)))
+        tw.pool = RowsJob(B, Ti, Di, stride=tw.S, offset=0)
+        wp = eng.w(IMG + "embeddings.patch_embeddings.projection.weight")
         if Kpp == Kp and v.patch % 8 == 0:
-            f.c("mh_patchify", _ptr(image), _ptr(patches), B, v.channels, v.image_size, v.image_size, v.patch)
+            f.c("mh_patchify", _ptr(image), _ptr(self.patches), B, v.channels, v.image_size, v.image_size, v.patch)
         else:
-            f.c("mh_patchify_ld", _ptr(image), _ptr(patches), B, v.channels, v.image_size, v.image_size, v.patch, Kpp)
+            f.c("mh_patchify_ld", _ptr(image), _ptr(self.patches), B, v.channels, v.image_size, v.image_size, v.patch, Kpp)
         if Kpp != Kp:       # zero-padded copy of the [Di][Kp] weight shadow (two 16-bit elements per word)
             wpad = alloc("i.wp_pad", (Di, Kpp))
             f.c("mh_copy2d_u32", _ptr(wp), Kp // 2, _ptr(wpad), Kpp // 2, Di, Kp // 2, Kpp // 2)
             wp = wpad
-        pbias = self.p(IMG + "embeddings.patch_embeddings.projection.bias") if v.patch_bias else None
-        self._gemm(pl, f, [self._fwd_prob(patches, wp, proj, B * Np, Di, Kpp, bias=pbias)], False, False)
+        pbias = eng.p(IMG + "embeddings.patch_embeddings.projection.bias") if v.patch_bias else None
+        self._gemm(f, [self._fwd_prob(self.patches, wp, proj, B * Np, Di, Kpp, bias=pbias)], False, False)
+        x0 = alloc("i.x0pre", (Ti, Di)) if v.pre_ln else tw.x[0]
+        f.c("mh_vit_assemble_fwd", _ptr(proj), _ptr(eng.p(IMG + "embeddings.cls_token")),
+            _ptr(eng.p(IMG + "embeddings.position_embeddings")), _ptr(x0), B, Np, Di)
         if v.pre_ln:        # CLIP: embeddings -> pre_layrnorm -> blocks
-            x0pre = alloc("i.x0pre", (Ti, Di))
-            m_pre, r_pre = alloc("i.mpre", (Ti,), F32), alloc("i.rpre", (Ti,), F32)
-            f.c("mh_vit_assemble_fwd", _ptr(proj), _ptr(self.p(IMG + "embeddings.cls_token")),
-                _ptr(self.p(IMG + "embeddings.position_embeddings")), _ptr(x0pre), B, Np, Di)
-            self._ln_fwd(pl, f, [self._ln_fwd_job(x0pre, IMG + "pre_layernorm.weight", IMG + "pre_layernorm.bias", xi[0],
-                                                  m_pre, r_pre, Ti, Di, v.ln_eps)])
-        else:
-            f.c("mh_vit_assemble_fwd", _ptr(proj), _ptr(self.p(IMG + "embeddings.cls_token")),
-                _ptr(self.p(IMG + "embeddings.position_embeddings")), _ptr(xi[0]), B, Np, Di)
-        quick = dict(quick=True) if v.act == "quick_gelu" else {}
+            self._ln_fwd(f, [self._ln_fwd_job(x0, IMG + "pre_layernorm", tw.x[0], alloc("i.mpre", (Ti,), F32),
+                                              alloc("i.rpre", (Ti,), F32), Ti, Di, v.ln_eps)])
 
-        xt_last32 = alloc("t.xlast32", (Rt, Dt), F32)   # unrounded tower outputs for the fp32 head
-        xf32 = alloc("i.xf32", (Ri, Di), F32)
-        tl: List[dict] = []   # per-layer saved activations, text
-        il: List[dict] = []
-        # "rows" of a layer = the rows of everything behind its attention core ("pctx" / "x": the operands of the first such block,
-        # the attention output and the layer input, at those rows: gathered copies in a compact last layer)
-        for l in range(Lt):
-            R = B if (cmp and l == Lt - 1) else Tt
-            tl.append(dict(qkv=alloc(f"t{l}.qkv", (Tt, 3 * Dt)), ctx=alloc(f"t{l}.ctx", (Tt, Dt)),
-                           lse=alloc(f"t{l}.lse", (B, Ht, S), F32), a=alloc(f"t{l}.a", (R, Dt)),
-                           y=alloc(f"t{l}.y", (R, Dt)), m1=alloc(f"t{l}.m1", (R,), F32), r1=alloc(f"t{l}.r1", (R,), F32),
-                           h=alloc(f"t{l}.h", (R, It)), g=alloc(f"t{l}.g", (R, It)), f=alloc(f"t{l}.f", (R, Dt)),
-                           m2=alloc(f"t{l}.m2", (R,), F32), r2=alloc(f"t{l}.r2", (R,), F32), rows=R))
-            if R != Tt:     # (a [B, D] panel is never clamped by the live-row count)
-                tl[l].update(pctx=alloc(f"t{l}.pctx", (B, Dt)), x=alloc(f"t{l}.xrows", (B, Dt)), tp={}, tpd={})
-            else:
-                tl[l].update(pctx=tl[l]["ctx"], x=xt[l], tp=tp, tpd=tpd)
-            xt.append(alloc(f"t.x{l + 1}", (R, Dt)))
-        for l in range(Li):
-            R = B if (cmp and l == Li - 1) else Ti
-            il.append(dict(u=alloc(f"i{l}.u", (Ti, Di)), m1=alloc(f"i{l}.m1", (Ti,), F32), r1=alloc(f"i{l}.r1", (Ti,), F32),
-                           qkv=alloc(f"i{l}.qkv", (Ti, 3 * Di)), ctx=alloc(f"i{l}.ctx", (Ti, Di)),
-                           lse=alloc(f"i{l}.lse", (B, Hi, Nt), F32), xp=alloc(f"i{l}.xp", (R, Di)),
-                           w=alloc(f"i{l}.w", (R, Di)), m2=alloc(f"i{l}.m2", (R,), F32), r2=alloc(f"i{l}.r2", (R,), F32),
-                           h=alloc(f"i{l}.h", (R, Ii)), g=alloc(f"i{l}.g", (R, Ii)), rows=R))
-            if R != Ti:
-                il[l].update(pctx=alloc(f"i{l}.pctx", (B, Di)), x=alloc(f"i{l}.xrows", (B, Di)))
-            else:
-                il[l].update(pctx=il[l]["ctx"], x=xi[l])
-            xi.append(alloc(f"i.x{l + 1}", (R, Di)))
-        xf = alloc("i.xf", (Ri, Di))
-        mf, rf = alloc("i.mf", (Ri,), F32), alloc("i.rf", (Ri,), F32)
-        # the pooled rows of each tower's row buffers: by the packing plan's pool_rows, or by arithmetic
-        t_rows = dict(idx=pool_rows, n=B, rows=Tt, D=Dt) if pack else dict(stride=S, offset=pool_index, n=B, rows=Tt, D=Dt)
-        i_rows = dict(stride=Nt, offset=0, n=B, rows=Ti, D=Di)
+    def last_layer_form(self):
+        """The head reads ONE row per sample from each tower (the pooled text position, the ViT class token), and behind the
+        attention core every block of a layer is row-wise.  Compact: the last layer of each tower gathers those B rows behind its
+        attention and runs out-proj, LayerNorms and FFN on [B, D] panels (forward and backward); the out-proj input
+        gradient is scattered back, with zeros everywhere else, in front of the attention backward.  Not when somebody
+        reads the full last hidden states ("sequence"), and not with dropout (its masks are indexed by the full row).
+        Everything that follows from that choice is set here."""
+        pl, B, t, v = self.pl, self.B, self.text, self.image
+        cmp = self.last_rows == "pooled" and pl.features != "sequence" and not pl.dropout_on and t.L >= 1 and v.L >= 1
+        pl.last_rows = "pooled" if cmp else "all"
+        # where the head finds its rows: compact towers hand it [B, D] (one "token" per sample)
+        self.head_rows = (1, 1, 0, None) if cmp else (t.S, v.S, self.pool_index, self.pool_rows)     # (S, Nt, pool index, pool rows)
+        for tw, n in ((t, "t"), (v, "i")):
+            tw.compact = B if cmp else 0
+            # the weight-gradient GEMMs of layer l may run on a side stream while the chain of layers l-1 and
+            # l-2 proceeds: everything they read is double-buffered by layer parity (dX: rotation of three),
+            # and layer l-2 waits for them before it overwrites those buffers
+            tw.dX = [self.alloc(f"{n}.dX{i}", (tw.T, tw.D)) for i in range(3)]
+            # the gradient that enters each tower's last layer: non-zero at the pooled rows only.  Full rows: zero-filled (bwd_head),
+            # the head writes the pooled rows.  Compact: [B, D], every row written by the head.
+            tw.d_last = self.alloc(f"{n}.dXrows", (B, tw.D)) if cmp else tw.dX[0]
+        self.zero_fill = not cmp
 
-        def img_ln1(l):
-            """The ViT block's pre-attention LayerNorm of layer l; past the last layer, the final ViT LayerNorm.
-            It is issued together with the text tower's LayerNorm that closes layer l-1 (one grouped launch)."""
-            if l < Li:
-                LI = f"{IMG}encoder.layer.{l}."
-                return self._ln_fwd_job(xi[l], LI + "layernorm_before.weight", LI + "layernorm_before.bias", il[l]["u"],
-                                        il[l]["m1"], il[l]["r1"], Ti, Di, v.ln_eps)
-            if l == Li:
-                return self._ln_fwd_job(xi[Li], IMG + "layernorm.weight", IMG + "layernorm.bias", xf, mf, rf, Ri, Di,
-                                        v.ln_eps, y32=xf32)
-            return None
+    def layer_buffers(self):
+        B, t, v, alloc = self.B, self.text, self.image, self.alloc
+        self.xt_last32 = alloc("t.xlast32", (t.out_rows, t.D), F32)   # unrounded tower outputs for the fp32 head
+        self.xf32 = alloc("i.xf32", (v.out_rows, v.D), F32)
+        for l in range(t.L):
+            R, n = t.rows(l), f"t{l}."
+            ctx = alloc(n + "ctx", (t.T, t.D))
+            t.acts.append(TextActs(
+                qkv=alloc(n + "qkv", (t.T, 3 * t.D)), ctx=ctx, lse=alloc(n + "lse", (B, t.H, t.S), F32), a=alloc(n + "a", (R, t.D)),
+                y=alloc(n + "y", (R, t.D)), m1=alloc(n + "m1", (R,), F32), r1=alloc(n + "r1", (R,), F32),
+                h=alloc(n + "h", (R, t.I)), g=alloc(n + "g", (R, t.I)), f=alloc(n + "f", (R, t.D)),
+                m2=alloc(n + "m2", (R,), F32), r2=alloc(n + "r2", (R,), F32),
+                pctx=alloc(n + "pctx", (B, t.D)) if R != t.T else ctx, x=alloc(n + "xrows", (B, t.D)) if R != t.T else t.x[l], rows=R))
+            t.x.append(alloc(f"t.x{l + 1}", (R, t.D)))
+        for l in range(v.L):
+            R, n = v.rows(l), f"i{l}."
+            ctx = alloc(n + "ctx", (v.T, v.D))
+            v.acts.append(ImageActs(
+                u=alloc(n + "u", (v.T, v.D)), m1=alloc(n + "m1", (v.T,), F32), r1=alloc(n + "r1", (v.T,), F32),
+                qkv=alloc(n + "qkv", (v.T, 3 * v.D)), ctx=ctx, lse=alloc(n + "lse", (B, v.H, v.S), F32),
+                xp=alloc(n + "xp", (R, v.D)), w=alloc(n + "w", (R, v.D)), m2=alloc(n + "m2", (R,), F32), r2=alloc(n + "r2", (R,), F32),
+                h=alloc(n + "h", (R, v.I)), g=alloc(n + "g", (R, v.I)),
+                pctx=alloc(n + "pctx", (B, v.D)) if R != v.T else ctx, x=alloc(n + "xrows", (B, v.D)) if R != v.T else v.x[l], rows=R))
+            v.x.append(alloc(f"i.x{l + 1}", (R, v.D)))
+        self.xf = alloc("i.xf", (v.out_rows, v.D))
+        self.mf, self.rf = alloc("i.mf", (v.out_rows,), F32), alloc("i.rf", (v.out_rows,), F32)
+        # the LayerNorm that opens image layer 0 (every later one shares a launch with the text LayerNorm closing the layer above)
+        self._ln_fwd(self.pl.fwd, [self._img_ln1(0)])
 
-        self._ln_fwd(pl, f, [img_ln1(0)])
-        for l in range(max(Lt, Li)):
-            has_t, has_i = l < Lt, l < Li
-            LT, LI = f"{TXT}encoder.layer.{l}.", f"{IMG}encoder.layer.{l}."
-            a = tl[l] if has_t else None
-            b_ = il[l] if has_i else None
-            # QKV
-            pr = []
-            if has_t:
-                pr.append(self._fwd_prob(xt[l], self.w(LT + "attention.self.query.weight", 3), a["qkv"], Tt, 3 * Dt, Dt,
-                                         bias=self.p(LT + "attention.self.query.bias", 3), **tp))
-            if has_i:
-                pr.append(self._fwd_prob(b_["u"], self.w(LI + "attention.attention.query.weight", 3), b_["qkv"], Ti,
-                                         3 * Di, Di, bias=self.p(LI + "attention.attention.query.bias", 3)))
-            self._gemm(pl, f, pr, False, False)
-            self._attn(pl, f, [
-                dict(qkv=b_["qkv"], out=b_["ctx"], lse=b_["lse"], B=B, S=Nt, H=Hi) if has_i else None,
-                text_attn(a, 16 * (l + 1) + 1) if has_t else None], backward=False)
-            # a compact last layer: from here on, only the pooled rows (of the attention output and of the layer input)
-            jobs = []
-            if has_t and a["rows"] != Tt:
-                jobs += [dict(t_rows, src=a["ctx"], dst=a["pctx"]), dict(t_rows, src=xt[l], dst=a["x"])]
-            if has_i and b_["rows"] != Ti:
-                jobs += [dict(i_rows, src=b_["ctx"], dst=b_["pctx"]), dict(i_rows, src=xi[l], dst=b_["x"])]
-            if jobs:
-                self._rows(pl, f, jobs, scatter=False)
-            Mt, Mi = (a["rows"] if has_t else 0), (b_["rows"] if has_i else 0)
-            tp_l, tpd_l = (a["tp"], a["tpd"]) if has_t else ({}, {})
-            # attention output projection + residual
-            pr = []
-            if has_t:
-                pr.append(self._fwd_prob(a["pctx"], self.w(LT + "attention.output.dense.weight"), a["a"], Mt, Dt, Dt,
-                                         bias=self.p(LT + "attention.output.dense.bias"), residual=a["x"],
-                                         drop=site(p_h, 16 * (l + 1) + 2), **tpd_l))
-            if has_i:
-                pr.append(self._fwd_prob(b_["pctx"], self.w(LI + "attention.output.dense.weight"), b_["xp"], Mi, Di, Di,
-                                         bias=self.p(LI + "attention.output.dense.bias"), residual=b_["x"]))
-            self._gemm(pl, f, pr, False, False)
-            self._ln_fwd(pl, f, [
-                self._ln_fwd_job(a["a"], LT + "attention.output.LayerNorm.weight", LT + "attention.output.LayerNorm.bias",
-                                 a["y"], a["m1"], a["r1"], Mt, Dt, t.ln_eps, **tp_l) if has_t else None,
-                self._ln_fwd_job(b_["xp"], LI + "layernorm_after.weight", LI + "layernorm_after.bias", b_["w"], b_["m2"],
-                                 b_["r2"], Mi, Di, v.ln_eps) if has_i else None])
-            # FFN up + GELU; "h" keeps gelu'(pre-activation) for the backward (computed here from the activation's own exponential:
-            # MH_GEMM_DERIV_AUX; MEMEHIP_GEMM_DERIV_AUX=0 keeps the pre-activation and evaluates gelu' in the backward epilogue)
-            pr = []
-            if has_t:
-                pr.append(self._fwd_prob(a["y"], self.w(LT + "intermediate.dense.weight"), a["g"], Mt, It, Dt,
-                                         bias=self.p(LT + "intermediate.dense.bias"), aux=a["h"], gelu=True, deriv_aux=DERIV_AUX, **tp_l))
-            if has_i:
-                pr.append(self._fwd_prob(b_["w"], self.w(LI + "intermediate.dense.weight"), b_["g"], Mi, Ii, Di,
-                                         bias=self.p(LI + "intermediate.dense.bias"), aux=b_["h"], gelu=True, deriv_aux=DERIV_AUX, **quick))
-            self._gemm(pl, f, pr, False, False)
-            # FFN down + residual
-            pr = []
-            if has_t:
-                pr.append(self._fwd_prob(a["g"], self.w(LT + "output.dense.weight"), a["f"], Mt, Dt, It,
-                                         bias=self.p(LT + "output.dense.bias"), residual=a["y"],
-                                         drop=site(p_h, 16 * (l + 1) + 3), **tpd_l))
-            if has_i:
-                pr.append(self._fwd_prob(b_["g"], self.w(LI + "output.dense.weight"), xi[l + 1], Mi, Di, Ii,
-                                         bias=self.p(LI + "output.dense.bias"), residual=b_["xp"]))
-            self._gemm(pl, f, pr, False, False)
-            # the text LayerNorm closing this layer + the image LayerNorm opening the next (or the final ViT one)
-            self._ln_fwd(pl, f, [
-                self._ln_fwd_job(a["f"], LT + "output.LayerNorm.weight", LT + "output.LayerNorm.bias", xt[l + 1], a["m2"],
-                                 a["r2"], Mt, Dt, t.ln_eps, y32=xt_last32 if l == Lt - 1 else None, **tp_l) if has_t else None,
-                img_ln1(l + 1) if has_i else None])
+    def _img_ln1(self, l) -> Optional[LnFwd]:
+        """The ViT block's pre-attention LayerNorm of layer l; past the last layer, the final ViT LayerNorm.
+        It is issued together with the text tower's LayerNorm that closes layer l-1 (one grouped launch)."""
+        v = self.image
+        if l < v.L:
+            b = v.acts[l]
+            return self._ln_fwd_job(v.x[l], v.name(l, "layernorm_before"), b.u, b.m1, b.r1, v.T, v.D, v.eps)
+        if l == v.L:
+            return self._ln_fwd_job(v.x[l], IMG + "layernorm", self.xf, self.mf, self.rf, v.out_rows, v.D, v.eps, y32=self.xf32)
+        return None
 
-        # head
-        hp, hg = MhHeadParams(), MhHeadGrads()
+    def fwd_layer(self, l):
+        """Layer l of both towers in lockstep: every GEMM stage is one grouped launch over the towers that have a layer l."""
+        f, t, v = self.pl.fwd, self.text, self.image
+        lay = [(tw, tw.acts[l], tw.roles(l), tw.rows(l)) for tw in self.towers if l < tw.L]
+        a, b = (t.acts[l] if l < t.L else None), (v.acts[l] if l < v.L else None)
+        # QKV
+        self._gemm(f, [self._linear(tw, l, tw.attn + "query", r.attn_in, a_.qkv, tw.T, 3 * tw.D, tw.D, 3, **tw.live(tw.T))
+                       for tw, a_, r, M in lay], False, False)
+        self._attn(f, [self._attn_prob(tw, l) for tw, _, _, _ in reversed(lay)], backward=False)
+        # a compact last layer: from here on, only the pooled rows (of the attention output and of the layer input)
+        self._rows(f, [j for tw, a_, r, M in lay if M != tw.T
+                       for j in (tw.pool._replace(src=a_.ctx, dst=a_.pctx), tw.pool._replace(src=tw.x[l], dst=a_.x))], scatter=False)
+        # attention output projection + residual
+        self._gemm(f, [self._linear(tw, l, "attention.output.dense", a_.pctx, r.proj_out, M, tw.D, tw.D, residual=a_.x,
+                                    drop=self.site(tw.p_h, 16 * (l + 1) + 2), **tw.live(M, drop=True)) for tw, a_, r, M in lay], False, False)
+        self._ln_fwd(f, [
+            self._ln_fwd_job(a.a, t.name(l, t.ln_mid), a.y, a.m1, a.r1, a.rows, t.D, t.eps, **t.live(a.rows)) if a else None,
+            self._ln_fwd_job(b.xp, v.name(l, v.ln_mid), b.w, b.m2, b.r2, b.rows, v.D, v.eps) if b else None])
+        # FFN up + GELU; "h" keeps gelu'(pre-activation) for the backward (computed here from the activation's own exponential:
+        # MH_GEMM_DERIV_AUX)
+        self._gemm(f, [self._linear(tw, l, "intermediate.dense", r.ffn_in, a_.g, M, tw.I, tw.D, aux=a_.h, gelu=True, deriv_aux=True,
+                                    quick=tw.quick, **tw.live(M)) for tw, a_, r, M in lay], False, False)
+        # FFN down + residual
+        self._gemm(f, [self._linear(tw, l, "output.dense", a_.g, r.ffn_out, M, tw.D, tw.I, residual=r.ffn_res,
+                                    drop=self.site(tw.p_h, 16 * (l + 1) + 3), **tw.live(M, drop=True)) for tw, a_, r, M in lay], False, False)
+        # the text LayerNorm closing this layer + the image LayerNorm opening the next (or the final ViT one)
+        self._ln_fwd(f, [
+            self._ln_fwd_job(a.f, t.name(l, "output.LayerNorm"), t.x[l + 1], a.m2, a.r2, a.rows, t.D, t.eps,
+                             y32=self.xt_last32 if l == t.L - 1 else None, **t.live(a.rows)) if a else None,
+            self._img_ln1(l + 1) if b else None])
+
+    def head_and_loss(self):
+        eng, pl, f, B, alloc, t, v = self.eng, self.pl, self.pl.fwd, self.B, self.alloc, self.text, self.image
+        P_, Cn = self.cfg.proj, self.cfg.num_classes
+        self.hp, self.hg = MhHeadParams(), MhHeadGrads()
         for fld, nm in (("Wt", "bert_fc.weight"), ("bt", "bert_fc.bias"), ("Wi", "image_fc.weight"),
                         ("bi", "image_fc.bias"), ("Wf", "fusion_fc.weight"), ("bf_", "fusion_fc.bias"),
                         ("Wo", "output_fc.weight"), ("bo", "output_fc.bias")):
-            setattr(hp, fld, _ptr(self.p(nm)))
-            setattr(hg, fld, _ptr(self.g(nm)))
-        pl.keep += [hp, hg]
-        pooled = alloc("h.pooled", (B, Dt + Di), F32)
-        feat, fused = alloc("h.feat", (B, 2 * P_), F32), alloc("h.fused", (B, P_), F32)
+            setattr(self.hp, fld, _ptr(eng.p(nm)))
+            setattr(self.hg, fld, _ptr(eng.g(nm)))
+        pl.keep += [self.hp, self.hg]
+        self.pooled = alloc("h.pooled", (B, t.D + v.D), F32)
+        self.feat, self.fused = alloc("h.feat", (B, 2 * P_), F32), alloc("h.fused", (B, P_), F32)
         logits = alloc("logits", (B, Cn), F32)
-        pl.features = features
-        # where the head finds its rows: compact towers hand it [B, D] (one "token" per sample)
-        S_h, Nt_h, pool_h, rows_h = (1, 1, 0, None) if cmp else (S, Nt, pool_index, pool_rows)
-        if features == "sequence":
-            assert not pack
-            d_seq_t, d_seq_i = alloc("h.d_seq_t", (Tt, Dt), F32, zero=True), alloc("h.d_seq_i", (Ti, Di), F32, zero=True)
-        elif features:
-            d_pooled = alloc("h.d_pooled", (B, Dt + Di), F32, zero=True)
-            f.c("mh_pool_fwd", _ptr(xt_last32), _ptr(xf32), pool_h, _ptr(pooled), B, S_h, Nt_h, Dt, Di, _ptr(rows_h))
+        S_h, Nt_h, pool_h, rows_h = self.head_rows
+        if pl.features == "sequence":
+            assert not pl.packed
+            self.d_seq_t, self.d_seq_i = alloc("h.d_seq_t", (t.T, t.D), F32, zero=True), alloc("h.d_seq_i", (v.T, v.D), F32, zero=True)
+        elif pl.features:
+            self.d_pooled = alloc("h.d_pooled", (B, t.D + v.D), F32, zero=True)
+            f.c("mh_pool_fwd", _ptr(self.xt_last32), _ptr(self.xf32), pool_h, _ptr(self.pooled), B, S_h, Nt_h, t.D, v.D, _ptr(rows_h))
         else:
-            f.c("mh_head_fwd", C.byref(hp), _ptr(xt_last32), _ptr(xf32), pool_h, _ptr(pooled), _ptr(feat), _ptr(fused),
-                _ptr(logits), B, S_h, Nt_h, Dt, Di, P_, Cn, *site_args(p_head, 7), _ptr(rows_h))
-
-        # loss
-        loss = alloc("loss", (1,), F32, zero=True)
-        dlogits = alloc("dlogits", (B, Cn), F32, zero=True)
+            f.c("mh_head_fwd", C.byref(self.hp), _ptr(self.xt_last32), _ptr(self.xf32), pool_h, _ptr(self.pooled), _ptr(self.feat),
+                _ptr(self.fused), _ptr(logits), B, S_h, Nt_h, t.D, v.D, P_, Cn, *self.site(self.p_head, 7), _ptr(rows_h))
+        labels, loss = alloc("labels", (B,), I64, zero=True), alloc("loss", (1,), F32, zero=True)
+        self.dlogits = alloc("dlogits", (B, Cn), F32, zero=True)
         ncorrect = alloc("ncorrect", (1,), torch.int32, zero=True)
-        grad_scale = 1.0
-        pl.loss.c("mh_ce_fwd_bwd", _ptr(logits), _ptr(labels), _ptr(loss), _ptr(dlogits), _ptr(ncorrect), B, Cn,
-                  float(grad_scale), _ptr(self.loss_scale))
+        pl.loss.c("mh_ce_fwd_bwd", _ptr(logits), _ptr(labels), _ptr(loss), _ptr(self.dlogits), _ptr(ncorrect), B, Cn,
+                  1.0, _ptr(eng.loss_scale))
 
-        # ------------------------------------------------------------------ backward -----------------
-        def seg(name):
-            s = Segment(name, self.lib)
-            pl.bwd.append(s)
-            return s
-
-        s = seg("bwd_head")
-        # the weight-gradient GEMMs of layer l may run on a side stream while the chain of layers l-1 and
-        # l-2 proceeds: everything they read is double-buffered by layer parity (dX: rotation of three),
-        # and layer l-2 waits for them before it overwrites those buffers
-        dXt = [alloc(f"t.dX{i}", (Tt, Dt)) for i in range(3)]
-        dXi = [alloc(f"i.dX{i}", (Ti, Di)) for i in range(3)]
-        dXf = alloc("i.dXf", (Ri, Di))
+    # ---- backward -------------------------------------------------------------------------------------------------
+    def bwd_head(self):
+        eng, pl, B, alloc, t, v = self.eng, self.pl, self.B, self.alloc, self.text, self.image
+        P_, Cn = self.cfg.proj, self.cfg.num_classes
+        s = self.seg("bwd_head")
+        dXf = alloc("i.dXf", (v.out_rows, v.D))
         dfeat, dfused = alloc("h.dfeat", (B, 2 * P_), F32), alloc("h.dfused", (B, P_), F32)
-        # the gradient that enters each tower's last layer: non-zero at the pooled rows only.  Full rows: zero-filled, the head
-        # writes the pooled rows.  Compact: [B, D], every row written by the head.
-        if cmp:
-            t_in, i_in = alloc("t.dXrows", (B, Dt)), alloc("i.dXrows", (B, Di))
-        else:
-            t_in, i_in = dXt[0], dXi[0]
-            s.py(t_in.zero_)
+        S_h, Nt_h, pool_h, rows_h = self.head_rows
+        if self.zero_fill:
+            s.py(t.d_last.zero_)
             s.py(dXf.zero_)
-        if features:
+        if pl.features:
             # the built-in head is not part of this graph: its gradient slots must not keep stale values
-            h0 = self.layout.spec["bert_fc.weight"].offset
-            h1 = self.layout.spec["output_fc.bias"].offset + self.layout.spec["output_fc.bias"].numel
-            head_grads = self.G[h0:h1]
+            h0 = eng.layout.spec["bert_fc.weight"].offset
+            h1 = eng.layout.spec["output_fc.bias"].offset + eng.layout.spec["output_fc.bias"].numel
+            head_grads = eng.G[h0:h1]
             s.py(head_grads.zero_)
-            if features == "sequence":      # the caller's gradient w.r.t. every hidden state (already times the stream scale)
-                s.c("mh_cast_f32_bf16", _ptr(d_seq_t), _ptr(t_in), Tt * Dt)
-                s.c("mh_cast_f32_bf16", _ptr(d_seq_i), _ptr(dXf), Ti * Di)
+            if pl.features == "sequence":      # the caller's gradient w.r.t. every hidden state (already times the stream scale)
+                s.c("mh_cast_f32_bf16", _ptr(self.d_seq_t), _ptr(t.d_last), t.T * t.D)
+                s.c("mh_cast_f32_bf16", _ptr(self.d_seq_i), _ptr(dXf), v.T * v.D)
             else:
-                s.c("mh_pool_bwd", _ptr(d_pooled), _ptr(t_in), _ptr(dXf), pool_h, B, S_h, Nt_h, Dt, Di, float(self.gscale),
+                s.c("mh_pool_bwd", _ptr(self.d_pooled), _ptr(t.d_last), _ptr(dXf), pool_h, B, S_h, Nt_h, t.D, v.D, float(eng.gscale),
                     _ptr(rows_h))
         else:
-            s.c("mh_head_bwd", C.byref(hp), C.byref(hg), _ptr(dlogits), _ptr(pooled), _ptr(feat), _ptr(fused), _ptr(dfeat),
-                _ptr(dfused), _ptr(t_in), _ptr(dXf), pool_h, B, S_h, Nt_h, Dt, Di, P_, Cn, float(self.gscale),
-                *site_args(p_head, 7), _ptr(rows_h))
+            s.c("mh_head_bwd", C.byref(self.hp), C.byref(self.hg), _ptr(self.dlogits), _ptr(self.pooled), _ptr(self.feat),
+                _ptr(self.fused), _ptr(dfeat), _ptr(dfused), _ptr(t.d_last), _ptr(dXf), pool_h, B, S_h, Nt_h, t.D, v.D, P_, Cn,
+                float(eng.gscale), *self.site(self.p_head, 7), _ptr(rows_h))
+        t.grads, v.grads = self._text_grads(), self._image_grads()
+        self.t_dpre = alloc("t.dpre", (t.T, t.D))
+        self._ln_bwd(s, [
+            self._ln_bwd_job(dXf, v.x[v.L], IMG + "layernorm", self.mf, self.rf, v.d_last, v.out_rows, v.D),
+            self._text_ln2_bwd(t.L - 1) if t.L >= v.L else None])
+
+    def _text_grads(self) -> List[Grads]:
+        """The gradient buffers of every text layer."""
+        t, B, alloc = self.text, self.B, self.alloc
         # backward temporaries, one set per layer parity
-        T_ = [dict(dh=alloc(f"t.dh{i}", (Tt, It)), da=alloc(f"t.da{i}", (Tt, Dt)),
-                   dqkv=alloc(f"t.dqkv{i}", (Tt, 3 * Dt)),
-                   dam=alloc(f"t.dam{i}", (Tt, Dt)) if p_h > 0 else None)     # da times the dropout mask of the Linear
-              for i in range(2)]                                              # output that fed the LayerNorm
+        dh = [alloc(f"t.dh{i}", (t.T, t.I)) for i in range(2)]
+        da = [alloc(f"t.da{i}", (t.T, t.D)) for i in range(2)]
+        dqkv = [alloc(f"t.dqkv{i}", (t.T, 3 * t.D)) for i in range(2)]
+        # da times the dropout mask of the Linear output that fed the LayerNorm = gradient w.r.t. the (dropped) attention output
+        # dense; without dropout, da itself
+        dam = [alloc(f"t.dam{i}", (t.T, t.D)) for i in range(2)] if t.p_h > 0 else da
         # df (gradient at the FFN output) is written one segment EARLY, by the LayerNorm backward grouped into the
         # end of the layer above: rotation of three, so the side-stream GEMMs of layer l+1 never see it overwritten
-        DF_ = [dict(df=alloc(f"t.df{i}", (Tt, Dt)), dfm=alloc(f"t.dfm{i}", (Tt, Dt)) if p_h > 0 else None)
-               for i in range(3)]
-        I_ = [dict(dh=alloc(f"i.dh{i}", (Ti, Ii)), dxp=alloc(f"i.dxp{i}", (Ti, Di)),
-                   dqkv=alloc(f"i.dqkv{i}", (Ti, 3 * Di))) for i in range(2)]
-        t_dy, t_dctx = alloc("t.dy", (Tt, Dt)), alloc("t.dctx", (Tt, Dt))
-        t_delta = alloc("t.delta", (B, Ht, S), F32)
-        i_dw, i_dctx, i_du = alloc("i.dw", (Ti, Di)), alloc("i.dctx", (Ti, Di)), alloc("i.du", (Ti, Di))
-        i_delta = alloc("i.delta", (B, Hi, Nt), F32)
-        if cmp:
-            # the compact last layers' own gradient panels.  The two that reach past the attention output projection are
+        df = [alloc(f"t.df{i}", (t.T, t.D)) for i in range(3)]
+        dfm = [alloc(f"t.dfm{i}", (t.T, t.D)) for i in range(3)] if t.p_h > 0 else df     # w.r.t. the (dropped) FFN output dense
+        dy, dctx = alloc("t.dy", (t.T, t.D)), alloc("t.dctx", (t.T, t.D))
+        t.delta = alloc("t.delta", (B, t.H, t.S), F32)
+        out = [Grads(d_out=dfm[l % 3], dh=dh[l & 1], d_mid=dy, d_proj=dam[l & 1], res=da[l & 1], dctx=dctx, res_full=da[l & 1],
+                     dctx_full=dctx, dqkv=dqkv[l & 1], d_in=t.d_x(l - 1), df=df[l % 3]) for l in range(t.L)]
+        if t.compact:
+            # the compact last layer's own gradient panels.  The two that reach past the attention output projection are
             # scattered into the full buffers of that layer parity, which the full-size kernels then read as before.
-            tc = dict(df=alloc("t.dfrows", (B, Dt)), dh=alloc("t.dhrows", (B, It)), dy=alloc("t.dyrows", (B, Dt)),
-                      da=alloc("t.darows", (B, Dt)), dctx=alloc("t.dctxrows", (B, Dt)))
-            ic = dict(dh=alloc("i.dhrows", (B, Ii)), dw=alloc("i.dwrows", (B, Di)), dxp=alloc("i.dxprows", (B, Di)),
-                      dctx=alloc("i.dctxrows", (B, Di)))
+            c_df, c_dh, c_dy = alloc("t.dfrows", (B, t.D)), alloc("t.dhrows", (B, t.I)), alloc("t.dyrows", (B, t.D))
+            c_da, c_dctx = alloc("t.darows", (B, t.D)), alloc("t.dctxrows", (B, t.D))
+            if t.rows(t.L - 1) != t.T:
+                out[-1] = out[-1]._replace(d_out=c_df, dh=c_dh, d_mid=c_dy, d_proj=c_da, res=c_da, dctx=c_dctx, df=c_df)
+        return out
 
-        def text_ln2_bwd(l, ct_):
-            """Backward of the LayerNorm that closes text layer l (incoming gradient dXt[ct_]; the last layer's: t_in).
-            Issued at the END of the segment above, grouped with the image tower's LayerNorm there."""
-            if not (0 <= l < Lt):
-                return None
-            LT_ = f"{TXT}encoder.layer.{l}."
-            dy, dx = (t_in, tc["df"] if cmp else DF_[l % 3]["df"]) if l == Lt - 1 else (dXt[ct_], DF_[l % 3]["df"])
-            return self._ln_bwd_job(pl, dy, tl[l]["f"], LT_ + "output.LayerNorm.weight", LT_ + "output.LayerNorm.bias",
-                                    tl[l]["m2"], tl[l]["r2"], dx, tl[l]["rows"], Dt,
-                                    dx_drop=DF_[l % 3]["dfm"] if p_h > 0 else None, drop=site(p_h, 16 * (l + 1) + 3), **tl[l]["tpd"])
+    def _image_grads(self) -> List[Grads]:
+        v, B, alloc = self.image, self.B, self.alloc
+        dh = [alloc(f"i.dh{i}", (v.T, v.I)) for i in range(2)]
+        dxp = [alloc(f"i.dxp{i}", (v.T, v.D)) for i in range(2)]
+        dqkv = [alloc(f"i.dqkv{i}", (v.T, 3 * v.D)) for i in range(2)]
+        dw, dctx, du = alloc("i.dw", (v.T, v.D)), alloc("i.dctx", (v.T, v.D)), alloc("i.du", (v.T, v.D))
+        v.delta = alloc("i.delta", (B, v.H, v.S), F32)
+        out = [Grads(d_out=v.d_x(l), dh=dh[l & 1], d_mid=dw, d_proj=dxp[l & 1], res=dxp[l & 1], dctx=dctx, res_full=dxp[l & 1],
+                     dctx_full=dctx, dqkv=dqkv[l & 1], d_in=du) for l in range(v.L)]
+        if v.compact:
+            c_dh, c_dw = alloc("i.dhrows", (B, v.I)), alloc("i.dwrows", (B, v.D))
+            c_dxp, c_dctx = alloc("i.dxprows", (B, v.D)), alloc("i.dctxrows", (B, v.D))
+            if v.rows(v.L - 1) != v.T:
+                out[-1] = out[-1]._replace(dh=c_dh, d_mid=c_dw, d_proj=c_dxp, res=c_dxp, dctx=c_dctx)
+        return out
 
-        nl = max(Lt, Li)
-        self._ln_bwd(pl, s, [
-            self._ln_bwd_job(pl, dXf, xi[Li], IMG + "layernorm.weight", IMG + "layernorm.bias", mf, rf, i_in, Ri, Di),
-            text_ln2_bwd(nl - 1, 0) if Lt == nl else None])
+    def _text_ln2_bwd(self, l) -> Optional[LnBwd]:
+        """Backward of the LayerNorm that closes text layer l.  Issued at the END of the segment above, grouped with the
+        image tower's LayerNorm there."""
+        t = self.text
+        if not (0 <= l < t.L):
+            return None
+        a, g = t.acts[l], t.grads[l]
+        return self._ln_bwd_job(t.d_x(l), a.f, t.name(l, "output.LayerNorm"), a.m2, a.r2, g.df, a.rows, t.D, dx_drop=g.d_out,
+                                drop=self.site(t.p_h, 16 * (l + 1) + 3), **t.live(a.rows, drop=True))
 
-        t_dpre = alloc("t.dpre", (Tt, Dt))
-        ct, ci = 0, 0   # current ping-pong index of the incoming gradient
-        for l in range(nl - 1, -1, -1):
-            has_t, has_i = l < Lt, l < Li
-            LT, LI = f"{TXT}encoder.layer.{l}.", f"{IMG}encoder.layer.{l}."
-            s = seg(f"bwd_layer_{l}")
-            s.wait(f"bwd_layer_{l + 2}")
-            a = tl[l] if has_t else None
-            b_ = il[l] if has_i else None
-            t_dh, t_da, t_dqkv = (T_[l & 1][k] for k in ("dh", "da", "dqkv"))
-            t_df = DF_[l % 3]["df"]
-            t_dfm = DF_[l % 3]["dfm"] if p_h > 0 else t_df     # gradient w.r.t. the (dropped) FFN output dense
-            t_dam = T_[l & 1]["dam"] if p_h > 0 else t_da      # gradient w.r.t. the (dropped) attention output dense
-            i_dh, i_dxp, i_dqkv = (I_[l & 1][k] for k in ("dh", "dxp", "dqkv"))
-            i_dx = i_in if l == Li - 1 else dXi[ci]            # gradient at this image layer's output
-            # r*: the same gradients as the blocks behind the attention core see them -- the buffers above, or in a compact
-            # last layer its [B, D] panels
-            Mt, Mi = (a["rows"] if has_t else 0), (b_["rows"] if has_i else 0)
-            tp_l, tpd_l = (a["tp"], a["tpd"]) if has_t else ({}, {})
-            rt_df = rt_dfm = rt_dh = rt_dy = rt_da = rt_dam = rt_dctx = ri_dh = ri_dw = ri_dxp = ri_dctx = None
-            if has_t:
-                rt_df, rt_dfm, rt_dh, rt_dy, rt_da, rt_dam, rt_dctx = (t_df, t_dfm, t_dh, t_dy, t_da, t_dam, t_dctx) if Mt == Tt else \
-                    (tc["df"], tc["df"], tc["dh"], tc["dy"], tc["da"], tc["da"], tc["dctx"])
-            if has_i:
-                ri_dh, ri_dw, ri_dxp, ri_dctx = (i_dh, i_dw, i_dxp, i_dctx) if Mi == Ti else (ic["dh"], ic["dw"], ic["dxp"], ic["dctx"])
-            # d gelu_in = (d_out @ W2) * gelu'(h)
-            pr = []
-            if has_t:
-                pr.append(self._dgrad_prob(rt_dfm, self.w(LT + "output.dense.weight"), rt_dh, Mt, Dt, It, mul=a["h"], deriv_aux=DERIV_AUX, **tp_l))
-            if has_i:
-                pr.append(self._dgrad_prob(i_dx, self.w(LI + "output.dense.weight"), ri_dh, Mi, Di, Ii, mul=b_["h"], deriv_aux=DERIV_AUX,
-                                           **quick))
-            self._gemm(pl, s, pr, False, True)
-            # through W1 (text adds the residual branch df)
-            pr = []
-            if has_t:
-                pr.append(self._dgrad_prob(rt_dh, self.w(LT + "intermediate.dense.weight"), rt_dy, Mt, It, Dt, residual=rt_df, **tp_l))
-            if has_i:
-                pr.append(self._dgrad_prob(ri_dh, self.w(LI + "intermediate.dense.weight"), ri_dw, Mi, Ii, Di))
-            self._gemm(pl, s, pr, False, True)
-            self._ln_bwd(pl, s, [
-                self._ln_bwd_job(pl, rt_dy, a["a"], LT + "attention.output.LayerNorm.weight",
-                                 LT + "attention.output.LayerNorm.bias", a["m1"], a["r1"], rt_da, Mt, Dt,
-                                 dx_drop=rt_dam if p_h > 0 else None, drop=site(p_h, 16 * (l + 1) + 2), **tpd_l) if has_t else None,
-                self._ln_bwd_job(pl, ri_dw, b_["xp"], LI + "layernorm_after.weight", LI + "layernorm_after.bias", b_["m2"],
-                                 b_["r2"], ri_dxp, Mi, Di, dx_add=i_dx) if has_i else None])
-            # through the attention output projection
-            pr = []
-            if has_t:
-                pr.append(self._dgrad_prob(rt_dam, self.w(LT + "attention.output.dense.weight"), rt_dctx, Mt, Dt, Dt, **tp_l))
-            if has_i:
-                pr.append(self._dgrad_prob(ri_dxp, self.w(LI + "attention.output.dense.weight"), ri_dctx, Mi, Di, Di))
-            self._gemm(pl, s, pr, False, True)
-            # a compact last layer ends here: its gradient w.r.t. the attention output goes back to the pooled rows of the full
-            # buffer, zeros everywhere else (no row attends for the loss but the pooled one), and the attention backward runs
-            # as ever.  The same for the residual branch around the attention (text: da, the `residual` of the QKV dgrad; image:
-            # dxp, the `dx_add` of the LayerNorm backward that opens the layer): those kernels add a full buffer, so they get one
-            # that is zero off the pooled rows -- adding the panel behind them instead would round twice.
-            jobs = []
-            if has_t and Mt != Tt:
-                jobs += [dict(t_rows, src=rt_dctx, dst=t_dctx, rows_dev=n_rows), dict(t_rows, src=rt_da, dst=t_da, rows_dev=n_rows)]
-            if has_i and Mi != Ti:
-                jobs += [dict(i_rows, src=ri_dctx, dst=i_dctx), dict(i_rows, src=ri_dxp, dst=i_dxp)]
-            if jobs:
-                self._rows(pl, s, jobs, scatter=True)
-            self._attn(pl, s, [
-                dict(qkv=b_["qkv"], out=b_["ctx"], lse=b_["lse"], dout=i_dctx, delta=i_delta, dqkv=i_dqkv, B=B, S=Nt,
-                     H=Hi) if has_i else None,
-                text_attn(a, 16 * (l + 1) + 1, dout=t_dctx, delta=t_delta, dqkv=t_dqkv) if has_t else None], backward=True)
-            # through the QKV projection
-            pr = []
-            if has_t:
-                pr.append(self._dgrad_prob(t_dqkv, self.w(LT + "attention.self.query.weight", 3), dXt[(ct + 1) % 3], Tt, 3 * Dt, Dt,
-                                           residual=t_da, **tp))
-            if has_i:
-                pr.append(self._dgrad_prob(i_dqkv, self.w(LI + "attention.attention.query.weight", 3), i_du, Ti, 3 * Di, Di))
-            self._gemm(pl, s, pr, False, True)
-            # the image LayerNorm that opens this layer + the text LayerNorm that closes the layer below (at layer 0:
-            # the text embedding LayerNorm), one grouped launch
-            ct_next = (ct + 1) % 3 if has_t else ct
-            if l >= 1:
-                t_job = text_ln2_bwd(l - 1, ct_next)
-            else:
-                d_emb = dXt[ct_next]
-                if pack:        # back to dense [B*S] rows (zeros at the dropped positions) for the embedding tables
-                    d_emb = alloc("t.dX_dense", (Tt, Dt))
-                    s.c("mh_unpack_rows", _ptr(dXt[ct_next]), _ptr(inv_map), _ptr(d_emb), Tt, Dt)
-                if p_h > 0:     # gradient w.r.t. the dropped embedding output -> w.r.t. the LayerNorm output
-                    s.c("mh_dropout_apply", _ptr(d_emb), Tt * Dt, rng_t.data_ptr(), float(p_h), 1)
-                t_job = self._ln_bwd_job(pl, d_emb, pre0, TXT + "embeddings.LayerNorm.weight",
-                                         TXT + "embeddings.LayerNorm.bias", m0, r0, t_dpre, Tt, Dt)
-            self._ln_bwd(pl, s, [
-                t_job,
-                self._ln_bwd_job(pl, i_du, xi[l], LI + "layernorm_before.weight", LI + "layernorm_before.bias", b_["m1"],
-                                 b_["r1"], dXi[(ci + 1) % 3], Ti, Di, dx_add=i_dxp) if has_i else None])
-            # weight gradients (+ bias gradients as row sums): one grouped launch per tower.  The 4+4 problems in ONE launch (864 tiles)
-            # measured 254 us against 215 us for the two 432-tile launches back to back (round 1), and in the step 11.2 ms against 10.2 ms
-            # (round 3, with or without a tile order giving every XCD its share of every problem, tools/lab/RESULTS.md (r3k)): the side stream must not hold every workgroup
-            # slot -- two 432-tile launches leave 80 of the 512 slots to the main chain.
-            wg_t = [
-                    self._wgrad_prob(rt_dfm, a["g"], self.g(LT + "output.dense.weight"), self.g(LT + "output.dense.bias"), Mt, Dt, It, **tp_l),
-                    self._wgrad_prob(rt_dh, a["y"], self.g(LT + "intermediate.dense.weight"), self.g(LT + "intermediate.dense.bias"), Mt, It, Dt, **tp_l),
-                    self._wgrad_prob(rt_dam, a["pctx"], self.g(LT + "attention.output.dense.weight"), self.g(LT + "attention.output.dense.bias"), Mt, Dt, Dt, **tp_l),
-                    self._wgrad_prob(t_dqkv, xt[l], self.g(LT + "attention.self.query.weight", 3), self.g(LT + "attention.self.query.bias", 3), Tt, 3 * Dt, Dt, **tp)] if has_t else []
-            wg_i = [
-                    self._wgrad_prob(i_dx, b_["g"], self.g(LI + "output.dense.weight"), self.g(LI + "output.dense.bias"), Mi, Di, Ii),
-                    self._wgrad_prob(ri_dh, b_["w"], self.g(LI + "intermediate.dense.weight"), self.g(LI + "intermediate.dense.bias"), Mi, Ii, Di),
-                    self._wgrad_prob(ri_dxp, b_["pctx"], self.g(LI + "attention.output.dense.weight"), self.g(LI + "attention.output.dense.bias"), Mi, Di, Di),
-                    self._wgrad_prob(i_dqkv, b_["u"], self.g(LI + "attention.attention.query.weight", 3), self.g(LI + "attention.attention.query.bias", 3), Ti, 3 * Di, Di)] if has_i else []
-            self._gemm(pl, s, wg_t, True, True, lane=1)
-            self._gemm(pl, s, wg_i, True, True, lane=1)
-            if has_t:
-                ct = (ct + 1) % 3
-            if has_i:
-                ci = (ci + 1) % 3
-            rng = [r for r in self.layout.layer_ranges if r[0] == l][0]
-            pl.bucket_after[s.name] = (rng[1], rng[2])
+    def _text_embed_ln_bwd(self, s: Segment) -> LnBwd:
+        """Backward of the text embedding LayerNorm, with what has to run in front of it."""
+        t = self.text
+        d_emb = t.d_x(-1)
+        if self.pl.packed:        # back to dense [B*S] rows (zeros at the dropped positions) for the embedding tables
+            d_emb = self.alloc("t.dX_dense", (t.T, t.D))
+            s.c("mh_unpack_rows", _ptr(t.d_x(-1)), _ptr(self.inv_map), _ptr(d_emb), t.T, t.D)
+        if t.p_h > 0:     # gradient w.r.t. the dropped embedding output -> w.r.t. the LayerNorm output
+            s.c("mh_dropout_apply", _ptr(d_emb), t.T * t.D, self.rng.data_ptr(), float(t.p_h), 1)
+        return self._ln_bwd_job(d_emb, self.pre0, TXT + "embeddings.LayerNorm", self.m0, self.r0, self.t_dpre, t.T, t.D)
 
-        # embeddings
-        s = seg("bwd_embed")
-        gword = self.g(TXT + "embeddings.word_embeddings.weight")
-        gtype0 = self.g(TXT + "embeddings.token_type_embeddings.weight")[:Dt] if t.type_vocab > 0 else None
-        gpos = self.g(TXT + "embeddings.position_embeddings.weight")
+    def bwd_layer(self, l):
+        """Backward of layer l of both towers.  The GEMM stages are stated once; where the dataflow differs -- the post-LN text
+        tower adds its residual gradients as the `residual` of a dgrad GEMM, the pre-LN image tower as `dx_add` of a LayerNorm
+        backward -- the two towers have a job each."""
+        t, v = self.text, self.image
+        s = self.seg(f"bwd_layer_{l}")
+        s.wait(f"bwd_layer_{l + 2}")
+        lay = [(tw, tw.acts[l], tw.roles(l), tw.grads[l], tw.rows(l)) for tw in self.towers if l < tw.L]
+        a, ga = (t.acts[l], t.grads[l]) if l < t.L else (None, None)
+        b, gb = (v.acts[l], v.grads[l]) if l < v.L else (None, None)
+        # d gelu_in = (d_out @ W2) * gelu'(h)
+        self._gemm(s, [self._linear_dgrad(tw, l, "output.dense", g.d_out, g.dh, M, tw.D, tw.I, mul=a_.h, deriv_aux=True, quick=tw.quick,
+                                          **tw.live(M)) for tw, a_, r, g, M in lay], False, True)
+        # through W1 (text adds the residual branch df)
+        self._gemm(s, [self._linear_dgrad(tw, l, "intermediate.dense", g.dh, g.d_mid, M, tw.I, tw.D, residual=g.df, **tw.live(M))
+                       for tw, a_, r, g, M in lay], False, True)
+        self._ln_bwd(s, [
+            self._ln_bwd_job(ga.d_mid, a.a, t.name(l, t.ln_mid), a.m1, a.r1, ga.res, a.rows, t.D, dx_drop=ga.d_proj,
+                             drop=self.site(t.p_h, 16 * (l + 1) + 2), **t.live(a.rows, drop=True)) if a else None,
+            self._ln_bwd_job(gb.d_mid, b.xp, v.name(l, v.ln_mid), b.m2, b.r2, gb.res, b.rows, v.D, dx_add=gb.d_out) if b else None])
+        # through the attention output projection
+        self._gemm(s, [self._linear_dgrad(tw, l, "attention.output.dense", g.d_proj, g.dctx, M, tw.D, tw.D, **tw.live(M))
+                       for tw, a_, r, g, M in lay], False, True)
+        # a compact last layer ends here: its gradient w.r.t. the attention output goes back to the pooled rows of the full
+        # buffer, zeros everywhere else (no row attends for the loss but the pooled one), and the attention backward runs
+        # as ever.  The same for the residual branch around the attention (text: da, the `residual` of the QKV dgrad; image:
+        # dxp, the `dx_add` of the LayerNorm backward that opens the layer): those kernels add a full buffer, so they get one
+        # that is zero off the pooled rows -- adding the panel behind them instead would round twice.
+        self._rows(s, [j for tw, a_, r, g, M in lay if M != tw.T
+                       for j in (tw.pool._replace(src=g.dctx, dst=g.dctx_full, rows_dev=tw.rows_dev),
+                                 tw.pool._replace(src=g.res, dst=g.res_full, rows_dev=tw.rows_dev))], scatter=True)
+        self._attn(s, [self._attn_prob(tw, l, dout=g.dctx_full, delta=tw.delta, dqkv=g.dqkv) for tw, a_, r, g, M in reversed(lay)],
+                   backward=True)
+        # through the QKV projection (text adds the residual branch da)
+        self._gemm(s, [self._linear_dgrad(tw, l, tw.attn + "query", g.dqkv, g.d_in, tw.T, 3 * tw.D, tw.D, 3,
+                                          residual=g.res_full if tw.post_ln else None, **tw.live(tw.T)) for tw, a_, r, g, M in lay], False, True)
+        # the image LayerNorm that opens this layer + the text LayerNorm that closes the layer below (at layer 0:
+        # the text embedding LayerNorm), one grouped launch
+        t_job = self._text_ln2_bwd(l - 1) if l >= 1 else self._text_embed_ln_bwd(s)
+        self._ln_bwd(s, [
+            t_job,
+            self._ln_bwd_job(gb.d_in, v.x[l], v.name(l, "layernorm_before"), b.m1, b.r1, v.d_x(l - 1), v.T, v.D,
+                             dx_add=gb.res_full) if b else None])
+        # weight gradients (+ bias gradients as row sums): one grouped launch per tower.  The 4+4 problems in ONE launch (864 tiles)
+        # measured 254 us against 215 us for the two 432-tile launches back to back (round 1), and in the step 11.2 ms against 10.2 ms
+        # (round 3, with or without a tile order giving every XCD its share of every problem, tools/lab/RESULTS.md (r3k)): the side stream must not hold every workgroup
+        # slot -- two 432-tile launches leave 80 of the 512 slots to the main chain.
+        for tw, a_, r, g, M in lay:
+            self._gemm(s, [
+                self._linear_wgrad(tw, l, "output.dense", g.d_out, a_.g, M, tw.D, tw.I, **tw.live(M)),
+                self._linear_wgrad(tw, l, "intermediate.dense", g.dh, r.ffn_in, M, tw.I, tw.D, **tw.live(M)),
+                self._linear_wgrad(tw, l, "attention.output.dense", g.d_proj, a_.pctx, M, tw.D, tw.D, **tw.live(M)),
+                self._linear_wgrad(tw, l, tw.attn + "query", g.dqkv, r.attn_in, tw.T, 3 * tw.D, tw.D, 3, **tw.live(tw.T))],
+                True, True, lane=1)
+        rng = [r for r in self.eng.layout.layer_ranges if r[0] == l][0]
+        self.pl.bucket_after[s.name] = (rng[1], rng[2])
 
-        def table_grads(sg, ids_, dpre_, prev_, nb):
-            # dense-Adam semantics: the table gradient is dense; only rows touched last step need re-zeroing
-            sg.c("mh_zero_rows_f32", _ptr(prev_), _ptr(gword), nb * S, Dt, t.vocab_size)
-            sg.c("mh_bert_embed_bwd", _ptr(ids_), _ptr(dpre_), _ptr(gword), _ptr(gpos), _ptr(gtype0), nb, S, Dt, t.vocab_size,
-                 int(t.pad_token_id), 1.0 / self.gscale, self.word_row_live.data_ptr(), self.word_first.data_ptr(),
-                 self.word_count.data_ptr())
-            sg.py(lambda: prev_.copy_(ids_))
-
+    def bwd_embed(self):
+        eng, pl, B, alloc, v, tw = self.eng, self.pl, self.B, self.alloc, self.cfg.image, self.image
+        Np, Ti, Di = v.n_patches, tw.T, tw.D
+        s = self.seg("bwd_embed")
         i_dproj = alloc("i.dproj", (B * Np, Di))
-        d_x0 = dXi[ci]
+        d_x0 = tw.d_x(-1)
         if v.pre_ln:        # through CLIP's pre_layrnorm
             d_x0 = alloc("i.dx0pre", (Ti, Di))
-            self._ln_bwd(pl, s, [self._ln_bwd_job(pl, dXi[ci], pl.buf["i.x0pre"], IMG + "pre_layernorm.weight",
-                                                  IMG + "pre_layernorm.bias", pl.buf["i.mpre"], pl.buf["i.rpre"], d_x0, Ti, Di)])
-        s.c("mh_vit_assemble_bwd", _ptr(d_x0), _ptr(i_dproj), _ptr(self.g(IMG + "embeddings.cls_token")),
-            _ptr(self.g(IMG + "embeddings.position_embeddings")), B, Np, Di, 1.0 / self.gscale)
-        # (the patch-projection weight gradient is a 36-tile GEMM with a 6272-deep contraction, 115 us on 14 % of the CUs;
-        #  moving it to the side stream beside the table gradients measured 0.12 ms SLOWER per step: it delays the join
-        #  in front of the optimizer tail)
-        gw = self.g(IMG + "embeddings.patch_embeddings.projection.weight")
-        gb = self.g(IMG + "embeddings.patch_embeddings.projection.bias") if v.patch_bias else None
-        gw_out = gw
+            self._ln_bwd(s, [self._ln_bwd_job(tw.d_x(-1), pl.buf["i.x0pre"], IMG + "pre_layernorm", pl.buf["i.mpre"], pl.buf["i.rpre"],
+                                              d_x0, Ti, Di)])
+        s.c("mh_vit_assemble_bwd", _ptr(d_x0), _ptr(i_dproj), _ptr(eng.g(IMG + "embeddings.cls_token")),
+            _ptr(eng.g(IMG + "embeddings.position_embeddings")), B, Np, Di, 1.0 / eng.gscale)
+        self._patch_wgrad(s, i_dproj)
+        if self.gather_world <= 0:
+            self._table_grads(s, self.ids, self.t_dpre, self.prev_ids, B)
+        # finish every LayerNorm's dgamma / dbeta from the partials
+        for D, jobs in pl._ln_jobs.items():
+            for i0 in range(0, len(jobs), _lib.MH_COLSUM_MAX_JOBS):
+                chunk = jobs[i0:i0 + _lib.MH_COLSUM_MAX_JOBS]
+                arr = (MhColsumJob * len(chunk))()
+                for j, (part, o0, o1) in enumerate(chunk):
+                    arr[j].part, arr[j].out0, arr[j].out1 = _ptr(part), _ptr(o0), _ptr(o1)
+                pl.keep.append(arr)
+                s.c("mh_colsum_partials_f32", arr, len(chunk), LN_PARTS, D, 1.0 / eng.gscale)
+        tail0 = eng.layout.layer_ranges[-1][2]
+        if self.gather_world <= 0:
+            pl.bucket_after[s.name] = (tail0, eng.layout.n_total)
+        else:
+            self._bwd_embed_tables(s, tail0)
+
+    def _patch_wgrad(self, s: Segment, i_dproj):
+        """Weight (and bias) gradient of the patch projection.
+        (it is a 36-tile GEMM with a 6272-deep contraction, 115 us on 14 % of the CUs; moving it to the side stream beside the
+        table gradients measured 0.12 ms SLOWER per step: it delays the join in front of the optimizer tail)"""
+        eng, pl, alloc, v, Di = self.eng, self.pl, self.alloc, self.cfg.image, self.image.D
+        Kp, Kpp, Tp = v.patch_dim, v.patch_dim_padded, self.B * v.n_patches
+        gw = gw_out = eng.g(IMG + "embeddings.patch_embeddings.projection.weight")
+        gb = eng.g(IMG + "embeddings.patch_embeddings.projection.bias") if v.patch_bias else None
         if Kpp != Kp:       # the GEMM writes a [Di][Kpp] gradient; its first Kp columns are copied into the flat buffer
             gw = alloc("i.dwp_pad", (Di * Kpp,), F32)
-        Tp = B * Np
         nsplit = min(_lib.MH_GEMM_MAX_GROUP, max(1, Tp // 512))
         if nsplit > 1:
             # split-K: the contraction over B*Np patches is cut into `nsplit` grouped problems with their own f32
@@ -891,8 +921,8 @@ class Engine:
                 if kk <= 0:
                     part_w[0, i].zero_(), part_b[0, i].zero_()
                     continue
-                probs.append(self._wgrad_prob(i_dproj[k0:], patches[k0:], part_w[0, i], part_b[0, i], kk, Di, Kpp))
-            self._gemm(pl, s, probs, True, True)
+                probs.append(self._wgrad_prob(i_dproj[k0:], self.patches[k0:], part_w[0, i], part_b[0, i], kk, Di, Kpp))
+            self._gemm(s, probs, True, True)
             for part, out, D_ in ((part_w, gw, Di * Kpp), (part_b, gb, Di)):
                 if out is None:
                     continue
@@ -901,37 +931,34 @@ class Engine:
                 pl.keep.append(arr)
                 s.c("mh_colsum_partials_f32", arr, 1, nsplit, D_, 1.0)
         else:
-            self._gemm(pl, s, [self._wgrad_prob(i_dproj, patches, gw, gb, Tp, Di, Kpp)], True, True)
+            self._gemm(s, [self._wgrad_prob(i_dproj, self.patches, gw, gb, Tp, Di, Kpp)], True, True)
         if Kpp != Kp:
             s.c("mh_copy2d_u32", _ptr(gw), Kpp, _ptr(gw_out), Kp, Di, Kp, Kp)
-        if gather_world <= 0:
-            table_grads(s, ids, t_dpre, prev_ids, B)
-        # finish every LayerNorm's dgamma / dbeta from the partials
-        for D, jobs in pl._ln_jobs.items():
-            for i0 in range(0, len(jobs), _lib.MH_COLSUM_MAX_JOBS):
-                chunk = jobs[i0:i0 + _lib.MH_COLSUM_MAX_JOBS]
-                arr = (MhColsumJob * len(chunk))()
-                for j, (part, o0, o1) in enumerate(chunk):
-                    arr[j].part, arr[j].out0, arr[j].out1 = _ptr(part), _ptr(o0), _ptr(o1)
-                pl.keep.append(arr)
-                s.c("mh_colsum_partials_f32", arr, len(chunk), LN_PARTS, D, 1.0 / self.gscale)
-        tail0 = self.layout.layer_ranges[-1][2]
-        if gather_world <= 0:
-            pl.bucket_after[s.name] = (tail0, self.layout.n_total)
-        else:
-            # data parallel: word / position / token-type tables sit at the end of the flat buffer; their gradients
-            # come from the gathered rows of every rank (already the global sum), so the all-reduce stops before them
-            first_tbl = TXT + ("embeddings.token_type_embeddings.weight" if t.type_vocab > 0
-                               else "embeddings.position_embeddings.weight")
-            tbl0 = self.layout.spec[first_tbl].offset
-            assert self.layout.spec[TXT + "embeddings.word_embeddings.weight"].offset + t.vocab_size * Dt + 3 >= self.layout.n_total - 3
-            pl.bucket_after[s.name] = (tail0, tbl0)
-            W = gather_world
-            ids_all = alloc("ids_all", (W * B, S), I64, zero=True)
-            prev_all = alloc("prev_ids_all", (W * B, S), I64, zero=True)
-            dpre_all = alloc("t.dpre_all", (W * Tt, Dt))
-            pl.gather = [(ids, ids_all), (t_dpre, dpre_all)]      # (local, gathered) pairs, exchanged between segments
-            s2 = seg("bwd_embed_tables")
-            table_grads(s2, ids_all, dpre_all, prev_all, W * B)
-        pl.n_launches = sum(1 for sg in [pl.fwd, pl.loss] + pl.bwd for c in sg.calls if c[0] is not None)
-        return pl
+
+    def _table_grads(self, sg: Segment, ids_, dpre_, prev_, nb):
+        eng, t, S, Dt = self.eng, self.cfg.text, self.S, self.text.D
+        gword = eng.g(TXT + "embeddings.word_embeddings.weight")
+        gtype0 = eng.g(TXT + "embeddings.token_type_embeddings.weight")[:Dt] if t.type_vocab > 0 else None
+        gpos = eng.g(TXT + "embeddings.position_embeddings.weight")
+        # dense-Adam semantics: the table gradient is dense; only rows touched last step need re-zeroing
+        sg.c("mh_zero_rows_f32", _ptr(prev_), _ptr(gword), nb * S, Dt, t.vocab_size)
+        sg.c("mh_bert_embed_bwd", _ptr(ids_), _ptr(dpre_), _ptr(gword), _ptr(gpos), _ptr(gtype0), nb, S, Dt, t.vocab_size,
+             int(t.pad_token_id), 1.0 / eng.gscale, eng.word_row_live.data_ptr(), eng.word_first.data_ptr(),
+             eng.word_count.data_ptr())
+        sg.py(lambda: prev_.copy_(ids_))
+
+    def _bwd_embed_tables(self, s: Segment, tail0: int):
+        """Data parallel: word / position / token-type tables sit at the end of the flat buffer; their gradients
+        come from the gathered rows of every rank (already the global sum), so the all-reduce stops before them."""
+        eng, pl, t, B, S, W, alloc = self.eng, self.pl, self.cfg.text, self.B, self.S, self.gather_world, self.alloc
+        Tt, Dt = self.text.T, self.text.D
+        first_tbl = TXT + ("embeddings.token_type_embeddings.weight" if t.type_vocab > 0
+                           else "embeddings.position_embeddings.weight")
+        tbl0 = eng.layout.spec[first_tbl].offset
+        assert eng.layout.spec[TXT + "embeddings.word_embeddings.weight"].offset + t.vocab_size * Dt + 3 >= eng.layout.n_total - 3
+        pl.bucket_after[s.name] = (tail0, tbl0)
+        ids_all = alloc("ids_all", (W * B, S), I64, zero=True)
+        prev_all = alloc("prev_ids_all", (W * B, S), I64, zero=True)
+        dpre_all = alloc("t.dpre_all", (W * Tt, Dt))
+        pl.gather = [(self.ids, ids_all), (self.t_dpre, dpre_all)]      # (local, gathered) pairs, exchanged between segments
+        self._table_grads(self.seg("bwd_embed_tables"), ids_all, dpre_all, prev_all, W * B)

@@ -13,7 +13,6 @@ Checked here:
   * packed step vs the CPU oracle on a mask with holes (the oracle applies the additive mask the way the
     reference's BertModel does).
 """
-import os
 
 import numpy as np
 import pytest
@@ -197,8 +196,6 @@ def test_packed_step_equals_dense_step(pkg, pool, kind, dropout):
 
 
 def test_packed_step_with_mask_holes_matches_oracle(pkg):
-    if os.environ.get("MEMEHIP_PACK_TEXT", "1") == "0":
-        pytest.skip("row packing switched off by MEMEHIP_PACK_TEXT=0")
     O = _oracle()
     B, S = 5, 24
     cfg = O.tiny_config("cls")
@@ -291,8 +288,6 @@ def test_one_graph_serves_batches_with_different_masks(pkg):
     """The packed plan is captured ONCE into a hipGraph; the live row count is read on the device at replay time, so
     batches with other attention masks (other numbers of live rows) replay the same graph.  Must equal the eager
     autograd-style loop step for step (same kernels, same order: bit-identical parameters)."""
-    if os.environ.get("MEMEHIP_PACK_TEXT", "1") == "0":
-        pytest.skip("row packing switched off by MEMEHIP_PACK_TEXT=0")
     O = _oracle()
     cfg = O.tiny_config("cls")
     B, S = 6, 32
