@@ -11,8 +11,11 @@ the way the reference writes it:
     gamma=2.0, reduction="mean"); loss.backward(); clip to 1.0; optimizer.step(); scheduler.step()
 
 Towers, poolings, Linear+BatchNorm1d+ReLU projections, ConcatAttention3, the focal loss and Adam all run in libmemehip.
-Synthetic inputs (no dataset or checkpoints offline).   python examples/task2c_kevin.py [--full]
+Synthetic inputs (no dataset or checkpoints offline).   python examples/task2c_kevin.py [--full] [--caption-model {bert,roberta}]
+--caption-model roberta: the caption tower is the submitted model's ``english_text_model = "roberta-base"`` (:81) --
+TextConfig.roberta_base (position ids from the input ids) with the RoBERTa tokenizers' special ids.
 """
+import argparse
 import os
 import sys
 
@@ -23,18 +26,25 @@ import multimodal_propaganda_meme_classification_amd as memehip
 
 
 def main():
-    small = "--full" not in sys.argv
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--caption-model", choices=("bert", "roberta"), default="bert")
+    args = ap.parse_args()
+    small, roberta = not args.full, args.caption_model == "roberta"
     device = torch.device("cuda")
     torch.manual_seed(0)
     if small:
         tc = memehip.TextConfig(vocab_size=2000, hidden=128, layers=2, heads=2, intermediate=256, max_position=64)
         ic = memehip.ImageConfig(image_size=64, hidden=128, layers=2, heads=2, intermediate=256)
         cc = memehip.TextConfig(vocab_size=2000, hidden=128, layers=2, heads=2, intermediate=256, max_position=64)
+        if roberta:
+            cc = memehip.TextConfig.roberta_base(vocab_size=2000, hidden=128, layers=2, heads=2, intermediate=256, max_position=66)
         model = memehip.KevinMultimodalClassifier("concatenation", text=tc, image=ic, caption=cc, proj=128, compute_dtype="fp16")
         B, S = 8, 32
     else:          # AraBERT-base + ViT-B/16 + bert-base-uncased captions
-        model = memehip.KevinMultimodalClassifier("concatenation", compute_dtype="fp16")
-        tc, ic, cc = model.towers.config.text, model.towers.config.image, memehip.TextConfig(vocab_size=30522)
+        cc = memehip.TextConfig.roberta_base(hidden_dropout=0.1, attention_dropout=0.1) if roberta else None
+        model = memehip.KevinMultimodalClassifier("concatenation", caption=cc, compute_dtype="fp16")
+        tc, ic, cc = model.towers.config.text, model.towers.config.image, cc or memehip.TextConfig(vocab_size=30522)
         B, S = 32, 128
     model.to(device).train()
     g = torch.Generator().manual_seed(1)
@@ -44,7 +54,12 @@ def main():
     mask = (torch.arange(S)[None] < lens[:, None]).long()
     image = torch.randn((B, 3, ic.image_size, ic.image_size), generator=g)
     labels = (torch.rand(B, generator=g) < 0.28).float().to(device)
-    batch = [x.to(device) for x in (text * mask, image, mask, cap * mask, mask)]
+    cap, cap_mask = cap * mask, mask
+    if roberta:         # captions through the tokenizer: <s> words </s> <pad>...; the position ids follow the pad pattern
+        tok = memehip.HashTokenizer.roberta(cc.vocab_size)
+        enc = [tok.encode_plus(" ".join(f"w{int(t)}" for t in row[:n - 2]), max_length=S) for row, n in zip(cap, lens.clamp(min=2))]
+        cap, cap_mask = torch.cat([e["input_ids"] for e in enc]), torch.cat([e["attention_mask"] for e in enc])
+    batch = [x.to(device) for x in (text * mask, image, mask, cap, cap_mask)]
 
     lr = 2e-5
     optimizer = memehip.Adam(model.get_params(lr), lr=lr, max_grad_norm=1.0)      # clip_grad_norm_(model.parameters(), 1.0), fused

@@ -270,6 +270,34 @@ int mh_bert_embed_bwd(const int64_t* ids, const void* d_pre /*bf16 [T][D]*/, flo
                       /* both NULL, or a persistent id index (restored to INT32_MAX / 0 on return): makes the duplicate-id
                          sum linear in the token count instead of quadratic -- the gathered batch of 8 ranks has 32 768 ids */,
                       mh_stream_t stream);
+/* RoBERTa-family embeddings (transformers RobertaEmbeddings: roberta-base, xlm-roberta-base): the same sum and LayerNorm with
+ * the position row taken from the input ids,
+ *     position_id = pad_id + (non-pad ids of the sequence up to and including the token)     for a non-pad token,
+ *     position_id = pad_id                                                                    for a pad token,
+ * and a position table whose row pad_id gets no gradient (nn.Embedding padding_idx).
+ * mh_position_ids_from_input_ids (one wave per sequence, no atomics):
+ *   pos_ids int32 [B][S]              the position id of every token
+ *   pos_inv int32 [B][max_position]   the position s whose token reads table row p, or -1 (row pad_id: always -1); non-pad
+ *                                     position ids ascend strictly, so a row has at most one token per sequence.  Every entry
+ *                                     is written.
+ *   A position id that would reach max_position (S + pad_id + 1 > max_position: the caller's error) is clamped to the last row
+ *   in pos_ids and left out of pos_inv, so no kernel leaves the table.
+ * mh_bert_embed_fwd_pos: mh_bert_embed_fwd with the position row pos_ids[t] (clamped into [0, max_position)); same f32
+ *   additions in the same order, so a batch without pad tokens and a table shifted by pad_id + 1 rows give the same bits.
+ * mh_embed_pos_bwd: dpos[p] = scale * sum_b d_pre[b*S + pos_inv[b][p]] over the b with pos_inv[b][p] >= 0, for EVERY row p of
+ *   the table (rows nobody reads are written as zeros), samples summed in the order of mh_bert_embed_bwd's dpos (bitwise
+ *   reproducible, and the same bits whenever both sum the same rows).  dtype0 != NULL: additionally dtype0 = scale * sum of
+ *   d_pre over every token, pad tokens included (the token-type table has no padding_idx), through scratch (f32 [S][D]) as
+ *   mh_bert_embed_bwd computes it.  The word table stays with mh_bert_embed_bwd. */
+int mh_position_ids_from_input_ids(const int64_t* ids /*[B][S]*/, int32_t* pos_ids, int32_t* pos_inv, int B, int S, int pad_id,
+                                   int max_position, mh_stream_t stream);
+int mh_bert_embed_fwd_pos(const int64_t* ids, const float* word, const float* pos /*[max_position][D]*/, const float* type0,
+                          const float* gamma, const float* beta, void* pre, void* y, float* mean, float* rstd, int B, int S,
+                          int D, int vocab, float eps, const uint32_t* rng, float drop_p, uint32_t drop_stream,
+                          const int32_t* pos_ids /*[B][S]*/, int max_position, mh_stream_t stream);
+int mh_embed_pos_bwd(const void* d_pre /*bf16 [B*S][D]*/, const int32_t* pos_inv /*[B][max_position]*/,
+                     float* dpos /*[max_position][D]*/, float* dtype0 /*[D] or NULL*/, float* scratch /*[S][D], with dtype0*/,
+                     int B, int S, int D, int max_position, float scale, mh_stream_t stream);
 /* Input pipeline on the device: ToTensor + Normalize of the reference transform
  * (Multimodal_example_task2C.txt:37-41) from decoded / resized / cropped uint8 pixels.
  *   src uint8 [B][H][W][3] (device) -> dst f32 [B][3][H][W] = (src/255 - mean[c]) / std[c]; W % 4 == 0; bit-exact

@@ -155,6 +155,10 @@ _PROTOS = {
     "mh_dropout_apply": [c_void_p, c_int64, c_void_p, c_float, C.c_uint32, c_void_p],
     "mh_dropout_mask_u8": [c_void_p, c_int64, c_void_p, c_float, C.c_uint32, c_void_p],
     "mh_bert_embed_bwd": [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
+    "mh_position_ids_from_input_ids": [c_void_p] * 3 + [c_int] * 4 + [c_void_p],
+    "mh_bert_embed_fwd_pos": [c_void_p] * 10 + [c_int, c_int, c_int, c_int, c_float, c_void_p, c_float, C.c_uint32, c_void_p, c_int,
+                              c_void_p],
+    "mh_embed_pos_bwd": [c_void_p] * 5 + [c_int] * 4 + [c_float, c_void_p],
     "mh_zero_rows_f32": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "mh_patchify": [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
     "mh_patchify_ld": [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p],

@@ -30,6 +30,35 @@ class TextConfig:
     ln_eps: float = 1e-12
     hidden_dropout: float = 0.0        # BertConfig.hidden_dropout_prob (0.1 in the reference's checkpoints)
     attention_dropout: float = 0.0     # BertConfig.attention_probs_dropout_prob (0.1)
+    # which position-table row a token reads: "absolute" = its position s (BertEmbeddings); "roberta" = pad_token_id + the
+    # count of non-pad ids up to and including it, pad tokens row pad_token_id, which gets no gradient (RobertaEmbeddings)
+    position_scheme: str = "absolute"
+
+    @classmethod
+    def roberta_base(cls, **overrides) -> "TextConfig":
+        """roberta-base: BertModel's encoder under BertModel's key names, RobertaEmbeddings' position ids."""
+        kw = dict(vocab_size=50265, max_position=514, type_vocab=1, pad_token_id=1, ln_eps=1e-5, position_scheme="roberta")
+        kw.update(overrides)
+        return cls(**kw)
+
+    @classmethod
+    def xlm_roberta_base(cls, **overrides) -> "TextConfig":
+        """FacebookAI/xlm-roberta-base: roberta-base with the 250 002-entry vocabulary."""
+        return cls.roberta_base(**{"vocab_size": 250002, **overrides})
+
+
+POSITION_SCHEMES = ("absolute", "roberta")
+
+
+def check_sequence_length(text: TextConfig, S: int) -> None:
+    """Raises ValueError when a sequence of S tokens would read past the position table (host check, before any launch):
+    the roberta scheme's largest position id is S + pad_token_id, where transformers raises an index error."""
+    if text.position_scheme == "roberta":
+        if S + text.pad_token_id + 1 > text.max_position:
+            raise ValueError(f"sequence length {S} + pad_token_id {text.pad_token_id} + 1 > max_position {text.max_position} "
+                             f"(roberta position ids start at pad_token_id + 1)")
+    elif S > text.max_position:
+        raise ValueError(f"sequence length {S} > max_position {text.max_position}")
 
 
 @dataclass
@@ -112,6 +141,11 @@ class ModelConfig:
             raise ValueError(f"image_fc_name must be 'image_fc' or 'resnet_fc', got {self.image_fc_name!r}")
         if self.compute_dtype not in ("bf16", "fp16"):
             raise ValueError(f"compute_dtype must be 'bf16' or 'fp16', got {self.compute_dtype!r}")
+        if self.text.position_scheme not in POSITION_SCHEMES:
+            raise ValueError(f"text: position_scheme must be one of {POSITION_SCHEMES}, got {self.text.position_scheme!r}")
+        if self.text.position_scheme == "roberta" and not 0 <= self.text.pad_token_id < self.text.max_position - 1:
+            raise ValueError(f"text: the roberta position scheme needs 0 <= pad_token_id < max_position - 1, got "
+                             f"{self.text.pad_token_id} / {self.text.max_position}")
         for pr in (self.text.hidden_dropout, self.text.attention_dropout, self.head_dropout):
             if not 0.0 <= pr < 1.0:
                 raise ValueError(f"dropout probability has to be in [0, 1), got {pr}")

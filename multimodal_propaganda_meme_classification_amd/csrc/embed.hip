@@ -6,21 +6,13 @@
 namespace {
 
 // ---- BERT embeddings forward: one wave per token ------------------------------------------------
+// token t: word row w + position row p (+ type0), LayerNorm, dropout.  Shared by the two kernels below, which differ only in
+// where the position row comes from.
 template <int NCH>
-__global__ __launch_bounds__(256) void bert_embed_fwd_kernel(
-    const int64_t* __restrict__ ids, const float* __restrict__ word, const float* __restrict__ pos,
-    const float* __restrict__ type0, const float* __restrict__ gamma, const float* __restrict__ beta,
-    h16* __restrict__ pre, h16* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd, int T, int S,
-    int D, int vocab, float eps, const uint32_t* __restrict__ rng, float drop_p, uint32_t drop_stream) {
-    const DropCtx drop = mh_drop_ctx(rng, drop_p, drop_stream);
-    const int lane = threadIdx.x & 63;
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= T) return;
-    int64_t id = ids[t];
-    if (id < 0 || id >= vocab) id = 0;  // never read outside the table
-    const int s = t % S;
-    const float* w = word + (size_t)id * D;
-    const float* p = pos + (size_t)s * D;
+MH_DEV void bert_embed_fwd_token(const float* __restrict__ w, const float* __restrict__ p, const float* __restrict__ type0,
+                                 const float* __restrict__ gamma, const float* __restrict__ beta, h16* __restrict__ pre,
+                                 h16* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd, int t, int lane, int D,
+                                 float eps, const DropCtx& drop) {
     float v[NCH][8];
     float sum = 0.f;
 #pragma unroll
@@ -72,6 +64,43 @@ __global__ __launch_bounds__(256) void bert_embed_fwd_kernel(
         }
     }
     if (lane == 0) { mean[t] = mu; rstd[t] = rs; }
+}
+
+template <int NCH>
+__global__ __launch_bounds__(256) void bert_embed_fwd_kernel(
+    const int64_t* __restrict__ ids, const float* __restrict__ word, const float* __restrict__ pos,
+    const float* __restrict__ type0, const float* __restrict__ gamma, const float* __restrict__ beta,
+    h16* __restrict__ pre, h16* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd, int T, int S,
+    int D, int vocab, float eps, const uint32_t* __restrict__ rng, float drop_p, uint32_t drop_stream) {
+    const DropCtx drop = mh_drop_ctx(rng, drop_p, drop_stream);
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= T) return;
+    int64_t id = ids[t];
+    if (id < 0 || id >= vocab) id = 0;  // never read outside the table
+    const int s = t % S;
+    bert_embed_fwd_token<NCH>(word + (size_t)id * D, pos + (size_t)s * D, type0, gamma, beta, pre, y, mean, rstd, t, lane, D,
+                              eps, drop);
+}
+
+// The same with the position row named by pos_ids[t] (RoBERTa-family towers: mh_position_ids_from_input_ids); the id and the
+// position id are two independent loads in front of the row loads.
+template <int NCH>
+__global__ __launch_bounds__(256) void bert_embed_fwd_pos_kernel(
+    const int64_t* __restrict__ ids, const int32_t* __restrict__ pos_ids, const float* __restrict__ word,
+    const float* __restrict__ pos, const float* __restrict__ type0, const float* __restrict__ gamma,
+    const float* __restrict__ beta, h16* __restrict__ pre, h16* __restrict__ y, float* __restrict__ mean,
+    float* __restrict__ rstd, int T, int D, int vocab, int max_position, float eps, const uint32_t* __restrict__ rng,
+    float drop_p, uint32_t drop_stream) {
+    const DropCtx drop = mh_drop_ctx(rng, drop_p, drop_stream);
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= T) return;
+    int64_t id = ids[t];
+    const int s = min(max(pos_ids[t], 0), max_position - 1);      // never read outside either table
+    if (id < 0 || id >= vocab) id = 0;
+    bert_embed_fwd_token<NCH>(word + (size_t)id * D, pos + (size_t)s * D, type0, gamma, beta, pre, y, mean, rstd, t, lane, D,
+                              eps, drop);
 }
 
 // ---- word-embedding gradient: the first occurrence of an id owns the row and sums all of its
@@ -228,6 +257,33 @@ __global__ __launch_bounds__(256) void bert_embed_bwd_word_indexed_kernel(const 
     }
 }
 
+// the four waves' partial sums of one output row, combined in wave order through LDS and stored times `scale`
+template <int NCH>
+MH_DEV void waves_sum_store(float (&acc)[NCH][8], float (&red)[3][NCH * 512], float* __restrict__ o, int D, float scale,
+                            int lane, int wave) {
+    if (wave > 0) {
+#pragma unroll
+        for (int i = 0; i < NCH; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) red[wave - 1][(i * 64 + lane) * 8 + e] = acc[i][e];
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int c = (lane + 64 * i) * 8;
+            if (c < D) {
+#pragma unroll
+                for (int w = 0; w < 3; ++w)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[i][e] += red[w][(i * 64 + lane) * 8 + e];
+                *(f32x4*)(o + c) = f32x4{acc[i][0], acc[i][1], acc[i][2], acc[i][3]} * scale;
+                *(f32x4*)(o + c + 4) = f32x4{acc[i][4], acc[i][5], acc[i][6], acc[i][7]} * scale;
+            }
+        }
+    }
+}
+
 // dpos[s] = sum_b d[b][s]  (rows: tokens per sample = S, B samples).  One workgroup per position s: the four waves
 // take the samples b = w, w+4, ... (independent 16-B loads, four in flight per wave) and are summed in wave order
 // through LDS -- a fixed order, so the result is bitwise reproducible.
@@ -262,28 +318,54 @@ __global__ __launch_bounds__(256) void sum_over_batch_kernel(const h16* __restri
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc[i][e] += mh_bf2f(u[k][i].e[e]);
     }
-    if (wave > 0) {
+    waves_sum_store<NCH>(acc, red, out + (size_t)s * D, D, scale, lane, wave);
+}
+
+// dpos[p] = sum_b d[b][pos_inv[b][p]] over the b that have a token at table row p (pos_inv >= 0): the position-table gradient
+// of a RoBERTa-family tower.  One workgroup per table row; the same sample order as sum_over_batch_kernel (wave w takes
+// b = w, w+4, ..., ascending; waves combined in wave order), a sample without a token adds +0 like a zero row would, so the
+// two kernels give the same bits whenever they sum the same rows.  A row nobody reads is written as zeros.
+// The four pos_inv reads of a trip (wave-uniform) are issued before its row loads: one dependent round trip per four samples.
+template <int NCH>
+__global__ __launch_bounds__(256) void sum_over_batch_inv_kernel(const h16* __restrict__ d, const int32_t* __restrict__ pos_inv,
+                                                                 float* __restrict__ out, int B, int S, int D,
+                                                                 int max_position, float scale) {
+    __shared__ float red[3][NCH * 512];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int p = blockIdx.x;
+    float acc[NCH][8];
 #pragma unroll
-        for (int i = 0; i < NCH; ++i)
+    for (int i = 0; i < NCH; ++i)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) red[wave - 1][(i * 64 + lane) * 8 + e] = acc[i][e];
-    }
-    __syncthreads();
-    if (wave == 0) {
-        float* o = out + (size_t)s * D;
+        for (int e = 0; e < 8; ++e) acc[i][e] = 0.f;
+    for (int b0 = wave; b0 < B; b0 += 16) {
+        int sp[4];
 #pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            const int c = (lane + 64 * i) * 8;
-            if (c < D) {
+        for (int k = 0; k < 4; ++k) {
+            const int b = b0 + 4 * k;
+            sp[k] = b < B ? pos_inv[(size_t)b * max_position + p] : -1;
+        }
+        Pack8 u[4][NCH];
 #pragma unroll
-                for (int w = 0; w < 3; ++w)
+        for (int k = 0; k < 4; ++k) {
+            const int b = b0 + 4 * k;
+            const bool on = sp[k] >= 0 && sp[k] < S;        // never outside d, whatever pos_inv holds
+            const h16* row = d + ((size_t)min(b, B - 1) * S + (on ? sp[k] : 0)) * D;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) acc[i][e] += red[w][(i * 64 + lane) * 8 + e];
-                *(f32x4*)(o + c) = f32x4{acc[i][0], acc[i][1], acc[i][2], acc[i][3]} * scale;
-                *(f32x4*)(o + c + 4) = f32x4{acc[i][4], acc[i][5], acc[i][6], acc[i][7]} * scale;
+            for (int i = 0; i < NCH; ++i) {
+                const int c = (lane + 64 * i) * 8;
+                u[k][i].v = i32x4{0, 0, 0, 0};
+                if (c < D && on) u[k][i].v = *(const i32x4*)(row + c);
             }
         }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int i = 0; i < NCH; ++i)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[i][e] += mh_bf2f(u[k][i].e[e]);
     }
+    waves_sum_store<NCH>(acc, red, out + (size_t)p * D, D, scale, lane, wave);
 }
 
 // out[d] = sum_{r<R} in[r][d]   (R small: <= 1024 rows).  Workgroup = 64 columns; the four waves take rows
@@ -476,6 +558,35 @@ extern "C" int mh_bert_embed_bwd(const int64_t* ids, const void* d_pre, float* d
     return mh_launch_status();
 }
 
+extern "C" int mh_bert_embed_fwd_pos(const int64_t* ids, const float* word, const float* pos, const float* type0,
+                                     const float* gamma, const float* beta, void* pre, void* y, float* mean, float* rstd,
+                                     int B, int S, int D, int vocab, float eps, const uint32_t* rng, float drop_p,
+                                     uint32_t drop_stream, const int32_t* pos_ids, int max_position, mh_stream_t stream) {
+    if (!ids || !word || !pos || !gamma || !beta || !pre || !y || !mean || !rstd || !pos_ids) return MH_EINVAL;
+    if (B < 1 || S < 1 || D < 8 || (D % 8) || D > 4096 || vocab < 1 || max_position < 1) return MH_ESHAPE;
+    const int T = B * S;
+    hipStream_t s = (hipStream_t)stream;
+    NCH_DISPATCH(bert_embed_fwd_pos_kernel, dim3((T + 3) / 4), dim3(256), 0, s, ids, pos_ids, word, pos, type0, gamma, beta,
+                 (h16*)pre, (h16*)y, mean, rstd, T, D, vocab, max_position, eps, rng, drop_p, drop_stream);
+    return mh_launch_status();
+}
+
+extern "C" int mh_embed_pos_bwd(const void* d_pre, const int32_t* pos_inv, float* dpos, float* dtype0, float* scratch, int B,
+                                int S, int D, int max_position, float scale, mh_stream_t stream) {
+    if (!d_pre || !pos_inv || !dpos) return MH_EINVAL;
+    if (dtype0 && !scratch) return MH_EINVAL;
+    if (((uintptr_t)d_pre | (uintptr_t)dpos | (uintptr_t)scratch) & 15) return MH_EINVAL;
+    if (B < 1 || S < 1 || D < 8 || (D % 8) || D > 4096 || max_position < 1) return MH_ESHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    NCH_DISPATCH(sum_over_batch_inv_kernel, dim3(max_position), dim3(256), 0, s, (const h16*)d_pre, pos_inv, dpos, B, S, D,
+                 max_position, scale);
+    if (dtype0) {       // every token, pad tokens included: the same two launches as mh_bert_embed_bwd
+        NCH_DISPATCH(sum_over_batch_kernel, dim3(S), dim3(256), 0, s, (const h16*)d_pre, scratch, B, S, D, scale);
+        hipLaunchKernelGGL(colsum_rows_f32_kernel, dim3((D + 63) / 64), dim3(256), 0, s, scratch, dtype0, S, D);
+    }
+    return mh_launch_status();
+}
+
 extern "C" int mh_zero_rows_f32(const int64_t* ids, float* table, int n_ids, int D, int vocab, mh_stream_t stream) {
     if (!ids || !table) return MH_EINVAL;
     if (n_ids < 1 || D < 4 || (D % 4) || vocab < 1) return MH_ESHAPE;
@@ -634,6 +745,39 @@ __global__ __launch_bounds__(1024) void pack_plan_kernel(const int64_t* __restri
     }
 }
 
+// RoBERTa-family position ids (transformers create_position_ids_from_input_ids): a non-pad token reads table row
+// pad_id + (non-pad tokens of its sequence up to and including it), a pad token row pad_id.  One wave per sequence, 64
+// positions per trip, the same ballot + popcount prefix as above.  pos_inv[b][p] = the position whose token reads row p, or -1:
+// non-pad position ids ascend strictly, so a row has at most one token per sequence.  The wave clears its pos_inv row first;
+// the fence orders those stores in front of the scatter, which other lanes of the wave issue.  A position id past the table
+// is clamped to its last row and left out of pos_inv.
+__global__ __launch_bounds__(256) void position_ids_kernel(const int64_t* __restrict__ ids, int32_t* __restrict__ pos_ids,
+                                                           int32_t* __restrict__ pos_inv, int B, int S, int pad_id,
+                                                           int max_position) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    int32_t* __restrict__ inv = pos_inv + (size_t)b * max_position;
+    for (int p = lane; p < max_position; p += 64) inv[p] = -1;
+    __threadfence_block();
+    int run = 0;        // non-pad tokens in front of this trip
+    for (int i0 = 0; i0 < S; i0 += 64) {
+        const int i = i0 + lane;
+        const bool live = i < S && ids[(size_t)b * S + i] != (int64_t)pad_id;
+        const unsigned long long bal = __ballot(live);
+        if (i < S) {
+            int p = pad_id;
+            if (live) {
+                p += run + __popcll(bal & ((2ull << lane) - 1ull));      // inclusive count
+                if (p < max_position) inv[p] = i;
+                else p = max_position - 1;
+            }
+            pos_ids[(size_t)b * S + i] = p;
+        }
+        run += __popcll(bal);
+    }
+}
+
 // wave per row, 16-B chunks
 __global__ __launch_bounds__(256) void pack_rows_kernel(const h16* __restrict__ src, const int32_t* __restrict__ row_map,
                                                         const int32_t* __restrict__ n_rows, h16* __restrict__ dst,
@@ -664,6 +808,15 @@ extern "C" int mh_pack_plan(const int64_t* mask, int B, int S, int pool_index, i
     if (B < 1 || B > 1024 || S < 1 || pool_index < 0 || pool_index >= S) return MH_ESHAPE;
     hipLaunchKernelGGL(pack_plan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, mask, B, S, pool_index, cu, row_map,
                        inv_map, pmask, pool_rows, n_rows);
+    return mh_launch_status();
+}
+
+extern "C" int mh_position_ids_from_input_ids(const int64_t* ids, int32_t* pos_ids, int32_t* pos_inv, int B, int S, int pad_id,
+                                              int max_position, mh_stream_t stream) {
+    if (!ids || !pos_ids || !pos_inv) return MH_EINVAL;
+    if (B < 1 || S < 1 || max_position < 1 || pad_id < 0 || pad_id >= max_position) return MH_ESHAPE;
+    hipLaunchKernelGGL(position_ids_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, ids, pos_ids, pos_inv, B, S,
+                       pad_id, max_position);
     return mh_launch_status();
 }
 

@@ -49,8 +49,14 @@ class HashTokenizer:
 
     cls_token_id, sep_token_id, pad_token_id = 2, 3, 0
 
-    def __init__(self, vocab_size: int = 64000):
+    def __init__(self, vocab_size: int = 64000, cls_token_id: int = 2, sep_token_id: int = 3, pad_token_id: int = 0):
         self.vocab_size = vocab_size
+        self.cls_token_id, self.sep_token_id, self.pad_token_id = int(cls_token_id), int(sep_token_id), int(pad_token_id)
+
+    @classmethod
+    def roberta(cls, vocab_size: int = 50265) -> "HashTokenizer":
+        """The special ids of the RoBERTa-family tokenizers: <s> = 0, <pad> = 1, </s> = 2."""
+        return cls(vocab_size, cls_token_id=0, sep_token_id=2, pad_token_id=1)
 
     def _id(self, tok: str) -> int:
         h = int.from_bytes(hashlib.blake2s(tok.encode("utf-8"), digest_size=8).digest(), "little")

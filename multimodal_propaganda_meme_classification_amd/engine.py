@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from ._lib import (MH_GEMM_DERIV_AUX, MH_GEMM_GELU, MH_GEMM_OUT_F32, MH_GEMM_QUICK_GELU, MhAttnProblem, MhColsumJob, MhGemmProblem, MhHeadGrads,
                    MhHeadParams, MhLnBwdJob, MhLnFwdJob, MhRowsJob)
-from .config import Layout, ModelConfig
+from .config import Layout, ModelConfig, check_sequence_length
 
 BF16, F32, I64 = torch.bfloat16, torch.float32, torch.int64
 LN_PARTS = 512     # workgroups (= sets of dgamma/dbeta partials) per LayerNorm backward
@@ -368,8 +368,7 @@ class _PlanBuilder:
 
     def __init__(self, eng: Engine, B: int, S: int, dropout_on: bool, gather_world: int, pack: bool, features, last_rows: str):
         cfg, t, v = eng.cfg, eng.cfg.text, eng.cfg.image
-        if S > t.max_position:
-            raise ValueError(f"sequence length {S} > max_position {t.max_position}")
+        check_sequence_length(t, S)
         if B > 1024:
             raise ValueError("batch > 1024 not supported by the loss kernel")
         self.eng, self.cfg, self.B, self.S = eng, cfg, B, S
@@ -537,10 +536,20 @@ class _PlanBuilder:
         x0d = alloc("t.x0", (Tt, Dt))
         self.m0, self.r0 = alloc("t.m0", (Tt,), F32), alloc("t.r0", (Tt,), F32)
         type0 = eng.p(TXT + "embeddings.token_type_embeddings.weight")[:Dt] if t.type_vocab > 0 else None
-        f.c("mh_bert_embed_fwd", _ptr(self.ids), _ptr(eng.p(TXT + "embeddings.word_embeddings.weight")),
-            _ptr(eng.p(TXT + "embeddings.position_embeddings.weight")), _ptr(type0),
-            _ptr(eng.p(TXT + "embeddings.LayerNorm.weight")), _ptr(eng.p(TXT + "embeddings.LayerNorm.bias")),
-            _ptr(self.pre0), _ptr(x0d), _ptr(self.m0), _ptr(self.r0), B, S, Dt, t.vocab_size, float(t.ln_eps), *self.site(tw.p_h, 1))
+        embed = (_ptr(self.ids), _ptr(eng.p(TXT + "embeddings.word_embeddings.weight")),
+                 _ptr(eng.p(TXT + "embeddings.position_embeddings.weight")), _ptr(type0),
+                 _ptr(eng.p(TXT + "embeddings.LayerNorm.weight")), _ptr(eng.p(TXT + "embeddings.LayerNorm.bias")),
+                 _ptr(self.pre0), _ptr(x0d), _ptr(self.m0), _ptr(self.r0), B, S, Dt, t.vocab_size, float(t.ln_eps), *self.site(tw.p_h, 1))
+        if t.position_scheme == "roberta":
+            # the position rows depend on the batch's ids: computed on the device, inside the (captured) forward.  pos_inv (table
+            # row -> position, per sequence) is what the position-table gradient of the local batch reads
+            pos_ids = alloc("t.pos_ids", (B, S), torch.int32, zero=True)
+            self.pos_inv = alloc("t.pos_inv", (B, t.max_position), torch.int32, zero=True)
+            f.c("mh_position_ids_from_input_ids", _ptr(self.ids), _ptr(pos_ids), _ptr(self.pos_inv), B, S, int(t.pad_token_id),
+                t.max_position)
+            f.c("mh_bert_embed_fwd_pos", *embed, _ptr(pos_ids), t.max_position)
+        else:
+            f.c("mh_bert_embed_fwd", *embed)
         # padding-free text tower: the encoder layers see only the rows that matter (attention_mask != 0, plus the
         # pooled position), packed back to back.  The row count lives on the device (n_rows): every text launch below
         # is sized for B*S rows and clamps itself at run time, so one plan / one hipGraph serves every batch.
@@ -942,9 +951,23 @@ class _PlanBuilder:
         gpos = eng.g(TXT + "embeddings.position_embeddings.weight")
         # dense-Adam semantics: the table gradient is dense; only rows touched last step need re-zeroing
         sg.c("mh_zero_rows_f32", _ptr(prev_), _ptr(gword), nb * S, Dt, t.vocab_size)
-        sg.c("mh_bert_embed_bwd", _ptr(ids_), _ptr(dpre_), _ptr(gword), _ptr(gpos), _ptr(gtype0), nb, S, Dt, t.vocab_size,
+        roberta = t.position_scheme == "roberta"
+        # roberta scheme: the per-position sums of mh_bert_embed_bwd (which the token-type gradient is made of) go to a scratch,
+        # and the position table gets its gradient by table row below
+        dpos = self.alloc("t.dpos_by_s", (S, Dt), F32) if roberta else gpos
+        sg.c("mh_bert_embed_bwd", _ptr(ids_), _ptr(dpre_), _ptr(gword), _ptr(dpos), _ptr(gtype0), nb, S, Dt, t.vocab_size,
              int(t.pad_token_id), 1.0 / eng.gscale, eng.word_row_live.data_ptr(), eng.word_first.data_ptr(),
              eng.word_count.data_ptr())
+        if roberta:
+            pos_inv = self.pos_inv
+            if ids_ is not self.ids:       # the gathered sequences of every rank: their own position ids
+                pos_ids = self.alloc("t.pos_ids_all", (nb, S), torch.int32, zero=True)
+                pos_inv = self.alloc("t.pos_inv_all", (nb, t.max_position), torch.int32, zero=True)
+                sg.c("mh_position_ids_from_input_ids", _ptr(ids_), _ptr(pos_ids), _ptr(pos_inv), nb, S, int(t.pad_token_id),
+                     t.max_position)
+            # writes every row of the table gradient (zeros where no token reads the row): nothing to re-zero
+            sg.c("mh_embed_pos_bwd", _ptr(dpre_), _ptr(pos_inv), _ptr(gpos), None, None, nb, S, Dt, t.max_position,
+                 1.0 / eng.gscale)
         sg.py(lambda: prev_.copy_(ids_))
 
     def _bwd_embed_tables(self, s: Segment, tail0: int):

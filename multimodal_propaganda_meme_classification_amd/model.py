@@ -623,8 +623,11 @@ class TextEncoder(nn.Module):
         res = self.load_state_dict(mine, strict=False)
         missing_keys.extend(prefix + k for k in res.missing_keys)
 
+    # buffers that some transformers versions persist in a BertModel / RobertaModel state dict; not parameters
+    _BUFFERS = ("embeddings.position_ids", "embeddings.token_type_ids")
+
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        sd = {("bert." + self._to_bert_name(k)): v for k, v in state_dict.items()}
+        sd = {("bert." + self._to_bert_name(k)): v for k, v in state_dict.items() if k not in self._BUFFERS}
         res = self.inner.load_state_dict(sd, strict=False)
         missing = [k[len("bert."):] for k in res.missing_keys if k.startswith("bert.")]
         if strict and (missing or res.unexpected_keys):

@@ -441,6 +441,46 @@ def bert_embed_bwd(ids, d_pre, dword, dpos, dtype0, pad_id: int, scale: float = 
                                       _p(index[1]) if index else None, _stream()), "mh_bert_embed_bwd")
 
 
+def position_ids_from_input_ids(ids, pad_id: int, max_position: int, pos_ids=None, pos_inv=None, kind: str = "bf16"):
+    """RoBERTa-family position ids (mh_position_ids_from_input_ids): returns (pos_ids int32 [B, S], pos_inv int32 [B, max_position])."""
+    _chk(ids, I64, "ids")
+    B, S = ids.shape
+    I32 = torch.int32
+    pos_ids = torch.empty((B, S), dtype=I32, device=ids.device) if pos_ids is None else _chk(pos_ids, I32, "pos_ids")
+    pos_inv = torch.empty((B, max_position), dtype=I32, device=ids.device) if pos_inv is None else _chk(pos_inv, I32, "pos_inv")
+    assert pos_ids.numel() >= B * S and pos_inv.numel() >= B * max_position
+    check(_lib.load(kind).mh_position_ids_from_input_ids(_p(ids), _p(pos_ids), _p(pos_inv), B, S, int(pad_id), int(max_position),
+                                                         _stream()), "mh_position_ids_from_input_ids")
+    return pos_ids, pos_inv
+
+
+def bert_embed_fwd_pos(ids, pos_ids, word, pos, type0, gamma, beta, eps, pre, y, mean, rstd, drop=None):
+    """bert_embed_fwd with the position row of token t named by pos_ids[t] (mh_bert_embed_fwd_pos)."""
+    _chk(ids, I64, "ids"), _chk(pos_ids, torch.int32, "pos_ids"), _chk(word, F32, "word"), _chk(pos, F32, "pos")
+    B, S = ids.shape
+    V, D = word.shape
+    assert pos_ids.numel() >= B * S and pos.shape[1] == D
+    assert pre.numel() >= B * S * D and y.numel() >= B * S * D and mean.numel() >= B * S and rstd.numel() >= B * S
+    check(_L(pre).mh_bert_embed_fwd_pos(_p(ids), _p(word), _p(pos), _p(type0), _p(gamma), _p(beta), _p(_chk(pre, BF16, "pre")),
+                                        _p(_chk(y, BF16, "y")), _p(mean), _p(rstd), B, S, D, V, float(eps), *_drop(drop),
+                                        _p(pos_ids), pos.shape[0], _stream()), "mh_bert_embed_fwd_pos")
+
+
+def embed_pos_bwd(d_pre, pos_inv, dpos, dtype0=None, scratch=None, scale: float = 1.0):
+    """Position-table gradient of a RoBERTa-family tower (mh_embed_pos_bwd): d_pre 16-bit [B*S, D], pos_inv int32 [B, P],
+    dpos f32 [P, D] (every row written); dtype0 f32 [D] with scratch f32 [S, D] additionally gives the token-type gradient."""
+    _chk(d_pre, BF16, "d_pre"), _chk(pos_inv, torch.int32, "pos_inv"), _chk(dpos, F32, "dpos")
+    B, P = pos_inv.shape
+    D = dpos.shape[1]
+    S = d_pre.numel() // (B * D)
+    assert d_pre.numel() == B * S * D and dpos.shape[0] == P
+    if dtype0 is not None:
+        _chk(dtype0, F32, "dtype0"), _chk(scratch, F32, "scratch")
+        assert dtype0.numel() >= D and scratch.numel() >= S * D
+    check(_L(d_pre).mh_embed_pos_bwd(_p(d_pre), _p(pos_inv), _p(dpos), _p(dtype0), _p(scratch), B, S, D, P, float(scale),
+                                     _stream()), "mh_embed_pos_bwd")
+
+
 def zero_rows(ids, table):
     _chk(ids, I64, "ids"), _chk(table, F32, "table")
     V, D = table.shape
