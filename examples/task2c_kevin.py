@@ -12,6 +12,9 @@ the way the reference writes it:
 
 Towers, poolings, Linear+BatchNorm1d+ReLU projections, ConcatAttention3, the focal loss and Adam all run in libmemehip.
 Synthetic inputs (no dataset or checkpoints offline).   python examples/task2c_kevin.py [--full] [--caption-model {bert,roberta}]
+                                                                                          [--image-model {vit,resnet18}]
+--image-model resnet18: the image tower is the submitted model's ``image_model = "resnet18"`` (:82 default; the only family its
+hard-coded ``Linear(512, 512)`` admits) -- resnet.ResNet18 under FineTuneMLP(512, proj), the text tower a TextEncoder of its own.
 --caption-model roberta: the caption tower is the submitted model's ``english_text_model = "roberta-base"`` (:81) --
 TextConfig.roberta_base (position ids from the input ids) with the RoBERTa tokenizers' special ids.
 """
@@ -29,8 +32,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--full", action="store_true")
     ap.add_argument("--caption-model", choices=("bert", "roberta"), default="bert")
+    ap.add_argument("--image-model", choices=("vit", "resnet18"), default="vit")
     args = ap.parse_args()
-    small, roberta = not args.full, args.caption_model == "roberta"
+    small, roberta, resnet = not args.full, args.caption_model == "roberta", args.image_model == "resnet18"
     device = torch.device("cuda")
     torch.manual_seed(0)
     if small:
@@ -39,12 +43,14 @@ def main():
         cc = memehip.TextConfig(vocab_size=2000, hidden=128, layers=2, heads=2, intermediate=256, max_position=64)
         if roberta:
             cc = memehip.TextConfig.roberta_base(vocab_size=2000, hidden=128, layers=2, heads=2, intermediate=256, max_position=66)
-        model = memehip.KevinMultimodalClassifier("concatenation", text=tc, image=ic, caption=cc, proj=128, compute_dtype="fp16")
+        model = memehip.KevinMultimodalClassifier("concatenation", text=tc, image="resnet18" if resnet else ic, caption=cc, proj=128,
+                                                  compute_dtype="fp16", resnet_layers=(1, 1, 1, 1) if resnet else None)
         B, S = 8, 32
     else:          # AraBERT-base + ViT-B/16 + bert-base-uncased captions
         cc = memehip.TextConfig.roberta_base(hidden_dropout=0.1, attention_dropout=0.1) if roberta else None
-        model = memehip.KevinMultimodalClassifier("concatenation", caption=cc, compute_dtype="fp16")
-        tc, ic, cc = model.towers.config.text, model.towers.config.image, cc or memehip.TextConfig(vocab_size=30522)
+        tc, ic = memehip.TextConfig(hidden_dropout=0.1, attention_dropout=0.1), memehip.ImageConfig()
+        model = memehip.KevinMultimodalClassifier("concatenation", text=tc, image="resnet18" if resnet else ic, caption=cc, compute_dtype="fp16")
+        cc = cc or memehip.TextConfig(vocab_size=30522)
         B, S = 32, 128
     model.to(device).train()
     g = torch.Generator().manual_seed(1)

@@ -610,6 +610,17 @@ typedef struct MhConvBnBwd {
 } MhConvBnBwd;
 int mh_conv_dgrad(const void* dy, const void* wk, void* dx, float* workspace, const MhConvGeom* g, const MhConvBnBwd* bn,
                   mh_stream_t stream);
+/* The input gradient of TWO convolutions that read the same [B][H][W][C] tensor, dx = dgrad(conv) + dgrad(conv2), both accumulated in f32
+ * and rounded to 16 bits once -- a residual stage's first BasicBlock (ResNet-18/34), where the 3x3 / 2 conv1 and the 1x1 / 2 downsample
+ * both send a gradient to the block input.  g: conv's geometry, what mh_conv_dgrad's strided branch accepts (k x k, k > 1, stride 2, even
+ * H x W, Cout % 64 == 0) with the output grid (H/2) x (W/2) (k = 2 pad + 1 or 2 pad + 2).  conv2 is 1x1 / stride 2 / pad 0: dy2
+ * [B*(H/2)*(W/2)][Cout2], wk2 its packed weight [Cout2][ldk2] (Cout2 % 64 == 0, ldk2 % 64 == 0, ldk2 >= C).  Still ONE launch of the four
+ * parity-class problems: conv2 touches pixel (2h', 2w') from output (h', w') only, exactly what the class holding conv's centre tap does,
+ * so its gradient is Cout2 / 64 more K tiles of that class (class (0, 0): 1 + 1 taps instead of 1 for a 3x3) -- no dgrad GEMM into an
+ * [M][ldk2] panel, no mh_col2im_nhwc, no add.  bn: as for mh_conv_dgrad's strided branch (part: 4 * ceil(B*(H/2)*(W/2) / 128) columns).
+ * MH_EINVAL: a null or misaligned pointer, a bn with missing fields; MH_ESHAPE: any other geometry (nothing is written). */
+int mh_conv_dgrad_pair(const void* dy, const void* wk, const void* dy2, const void* wk2, int ldk2, int Cout2, void* dx, const MhConvGeom* g,
+                       const MhConvBnBwd* bn, mh_stream_t stream);
 /* BatchNorm2d backward from mh_conv_dgrad's partial sums: dy is ALREADY masked; finish (dgamma, dbeta, sums) + apply (dx) */
 int mh_bn2d_bwd_parts(const void* dy_masked, const void* x, const float* part, int nblk, const float* gamma, const float* save_mean,
                       const float* save_rstd, void* dx, float* dgamma, float* dbeta, float* sums /* f32 [2][C] scratch */, int M, int C,

@@ -199,6 +199,7 @@ _PROTOS = {
     "mh_conv_splitk": [C.POINTER(MhConvGeom), c_int],
     "mh_conv_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.POINTER(MhConvGeom), c_void_p],
     "mh_conv_dgrad": [c_void_p, c_void_p, c_void_p, c_void_p, C.POINTER(MhConvGeom), C.POINTER(MhConvBnBwd), c_void_p],
+    "mh_conv_dgrad_pair": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, C.POINTER(MhConvGeom), C.POINTER(MhConvBnBwd), c_void_p],
     "mh_bn2d_bwd_parts": [c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_int, c_int, c_float, c_void_p],
     "mh_conv_wgrad": [c_void_p, c_void_p, c_void_p, c_int, c_float, C.POINTER(MhConvGeom), c_void_p],
     "mh_conv_wgrad_grouped": [C.POINTER(MhConvWgradProblem), c_int, c_void_p],

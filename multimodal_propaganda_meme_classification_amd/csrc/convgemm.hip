@@ -82,8 +82,21 @@ struct ConvGroup {
     ConvArgs a[CONV_MAX_GROUP];
 };
 
-template <int MODE, bool UNI>
-__global__ __launch_bounds__(NW * 64, NW / 2) void conv_gemm_kernel(const ConvGroup grp) {
+// A SECOND K segment for one problem of a dgrad launch (mh_conv_dgrad_pair): after that problem's own K tiles, the tiles of a 1x1 / stride-2 /
+// pad-0 convolution over the same input tensor -- its dy2 row is the GEMM row itself (the class's pixel (2h', 2w') is read by output (h', w')
+// alone), its weight a plain [C2][ldreg] matrix -- go into the same accumulators.  Still UNI: a K tile lies inside one segment.
+struct ConvPair {
+    const h16* src;      // dy2 [Mpix][C2]
+    const h16* reg;      // packed weight of the 1x1 convolution [C2][ldreg]
+    uint32_t src_bytes, reg_bytes;
+    int prob;            // the problem (parity class) that takes the segment
+    int nk1;             // its K tiles before the segment (its own taps); K tiles nk1 .. are the segment's
+    int C2, ldreg;
+};
+
+// One tile of one problem of `grp`: the body of conv_gemm_kernel and (PAIR) of conv_dgrad_pair_kernel.
+template <int MODE, bool UNI, bool PAIR>
+MH_DEV void conv_tile(const ConvGroup& grp, const ConvPair& pr) {
     constexpr int LA = (MODE == MODE_WGRAD) ? 1 : 0;
     constexpr int LB = (MODE == MODE_FWD) ? 0 : 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -177,6 +190,24 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_gemm_kernel(const ConvGr
         }
     }
 
+    // PAIR: both descriptors and the per-lane row offset into dy2 are made HERE, so the K loop's switch to the second segment is a scalar
+    // compare + select of values already in registers (no load behind the switch)
+    __amdgpu_buffer_rsrc_t rs2 = rs, rr2 = rr;
+    int nk1 = nk;
+    uint32_t p_off2[2] = {OOB, OOB};
+    if (PAIR) {
+        rs2 = mh_rsrc(pr.src, pr.src_bytes);
+        rr2 = mh_rsrc(pr.reg, pr.reg_bytes);
+        if (pi == pr.prob) nk1 = pr.nk1;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int row = (wave * 2 + i) * 8 + (lane >> 3);
+            const int c = (lane & 7) ^ (row & 7);
+            const int m = m0 + row;
+            if (m < a.M) p_off2[i] = (uint32_t)(m * pr.C2 + c * 8) * 2u;      // (rows past M stay beyond num_records: zeros)
+        }
+    }
+
     // wave-uniform tap walk of the K tiles (fwd / dgrad), from this split's first K tile
     int u_kh = 0, u_kw = 0, u_c0 = 0;
     if (UNI && MODE != MODE_WGRAD && kbeg > 0) {
@@ -206,6 +237,14 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_gemm_kernel(const ConvGr
                 }
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(void, lb + piece * 1024), 16, off, 0, 0, 0);
             }
+            return;
+        }
+        if (PAIR && kt >= nk1) {      // second segment (wave-uniform): rows co2 = c0.. of the 1x1 weight, the same pixel's channels c0.. of dy2
+            const int c0 = (kt - nk1) * BK;
+            dma_tile<1, 2>(rr2, pr.ldreg, n0, c0, wave, lane, lb);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs2, LDS_PTR(void, la + (wave * 2 + i) * 1024), 16, p_off2[i] + (uint32_t)c0 * 2u, 0, 0, 0);
             return;
         }
         // regular B first (it needs the tap BEFORE the walk advances)
@@ -386,6 +425,16 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_gemm_kernel(const ConvGr
     }
 }
 
+template <int MODE, bool UNI>
+__global__ __launch_bounds__(NW * 64, NW / 2) void conv_gemm_kernel(const ConvGroup grp) {
+    conv_tile<MODE, UNI, false>(grp, ConvPair{});
+}
+
+// the four parity classes of a k x k / stride-2 input gradient, one of them with the 1x1 / stride-2 downsample's gradient as a second K segment
+__global__ __launch_bounds__(NW * 64, NW / 2) void conv_dgrad_pair_kernel(const ConvGroup grp, const ConvPair pr) {
+    conv_tile<MODE_DGRAD, true, true>(grp, pr);
+}
+
 // split-K forward / dgrad: y = 16-bit(sum of the f32 slabs, in slab order); with `part`, the BatchNorm partial sums of the stored
 // values per 128-row block (what the unsplit epilogue leaves).  Block = 128 rows x 64 columns: thread (ty = row lane of 32, tx = 8
 // columns), 4 rows each; column sums through LDS in row-lane order.
@@ -500,14 +549,9 @@ int splitk_for(int tiles, int K) {
     return ksplit_fit(K, sp);
 }
 
-template <int MODE, bool UNI>
-int conv_launch_group(const ConvGroup& grp, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv_gemm_kernel<MODE, UNI>, hipFuncAttributeMaxDynamicSharedMemorySize, CONV_LDS);
-        attr_set = true;
-    }
-    int per_xcd = 0;      // the largest per-XCD tile count when every XCD takes its eighth of every problem (see the kernel's prologue)
+// the largest per-XCD tile count when every XCD takes its eighth of every problem (see the tile body's prologue)
+int per_xcd_tiles(const ConvGroup& grp) {
+    int per_xcd = 0;
     for (int x = 0; x < 8; ++x) {
         int c = 0;
         for (int i = 0; i < grp.n; ++i) {
@@ -516,7 +560,26 @@ int conv_launch_group(const ConvGroup& grp, hipStream_t s) {
         }
         per_xcd = c > per_xcd ? c : per_xcd;
     }
-    hipLaunchKernelGGL((conv_gemm_kernel<MODE, UNI>), dim3(8 * per_xcd), dim3(NW * 64), CONV_LDS, s, grp);
+    return per_xcd;
+}
+
+template <int MODE, bool UNI>
+int conv_launch_group(const ConvGroup& grp, hipStream_t s) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)conv_gemm_kernel<MODE, UNI>, hipFuncAttributeMaxDynamicSharedMemorySize, CONV_LDS);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((conv_gemm_kernel<MODE, UNI>), dim3(8 * per_xcd_tiles(grp)), dim3(NW * 64), CONV_LDS, s, grp);
+    return mh_launch_status();
+}
+int conv_launch_pair(const ConvGroup& grp, const ConvPair& pr, hipStream_t s) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)conv_dgrad_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CONV_LDS);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(conv_dgrad_pair_kernel, dim3(8 * per_xcd_tiles(grp)), dim3(NW * 64), CONV_LDS, s, grp, pr);
     return mh_launch_status();
 }
 template <int MODE, bool UNI>
@@ -609,6 +672,63 @@ extern "C" int mh_conv_fwd(const void* x, const void* wk, void* y, float* bn_par
     return uni ? conv_launch<MODE_FWD, true>(a, (hipStream_t)stream) : conv_launch<MODE_FWD, false>(a, (hipStream_t)stream);
 }
 
+namespace {
+// whether mh_conv_dgrad takes g as four parity-class problems: k x k (k > 1) / stride 2 on an even image
+bool parity_geom(const MhConvGeom* g) {
+    return g->stride == 2 && g->KH == g->KW && !(g->H & 1) && !(g->W & 1) && g->pad <= g->KH - 1 && (g->Cout % BK) == 0 && g->KH > 1;
+}
+bool bn_incomplete(const MhConvBnBwd* bn) { return bn && (!bn->z || !bn->mean || !bn->rstd || !bn->gamma || !bn->beta || !bn->part); }
+
+// STRIDE 2 (round 4, second session): input pixel (h, w) only meets the taps kh = (h + pad) mod 2 + 2 j (same along w), so the
+// pixels of one parity class (ph, pw) form a stride-1 problem over dY with a ceil / floor(K / 2)-tap window whose result lands in
+// every second row and column of dX: four problems (1 + 2 + 2 + 4 taps for a 3x3 filter: every multiply-add useful) in ONE
+// launch, no [M][K*K*C] panel in HBM and no col2im pass.  `bn`: as for stride 1, the epilogue masks the gradient and leaves
+// the BatchNorm sums -- part holds 2 x C x (4 x ceil(B (H/2) (W/2) / 128)) partials (mh_bn2d_bwd_parts sums them all).
+int parity_group(const void* dy, const void* wk, void* dx, const MhConvGeom* g, int Ho, int Wo, const MhConvBnBwd* bn, ConvGroup& grp) {
+    grp = ConvGroup{};
+    const int Hh = g->H / 2, Wh = g->W / 2;
+    int total = 0, ptiles = 0, n = 0;
+    for (int ph = 0; ph < 2; ++ph)
+        for (int pw = 0; pw < 2; ++pw) {
+            const int kh0 = (ph + g->pad) & 1, kw0 = (pw + g->pad) & 1;
+            const int nkh = (g->KH - kh0 + 1) / 2, nkw = (g->KW - kw0 + 1) / 2;
+            if (nkh < 1 || nkw < 1) return MH_ESHAPE;              // (a class without taps: 1x1 filters keep the explicit path)
+            const int padh = nkh - 1 - (ph + g->pad - kh0) / 2, padw = nkw - 1 - (pw + g->pad - kw0) / 2;
+            if (padh != padw || padh < 0) return MH_ESHAPE;
+            ConvArgs a = {};
+            a.src = (const h16*)dy; a.reg = (const h16*)wk; a.out = dx; a.part = nullptr;
+            a.src_bytes = (uint32_t)((size_t)g->B * Ho * Wo * g->Cout * 2);
+            a.reg_bytes = (uint32_t)((size_t)g->Cout * g->ldk * 2);
+            a.H = Ho; a.W = Wo; a.C = g->Cout;
+            a.KH = nkh; a.KW = nkw; a.stride = 1; a.pad = padh;
+            a.Ho = Hh; a.Wo = Wh; a.Mpix = g->B * Hh * Wh;
+            a.M = a.Mpix; a.N = g->C; a.K = nkh * nkw * g->Cout;
+            a.ldreg = g->ldk; a.ldc = g->C; a.Cw = g->C;
+            a.tiles_m = (a.M + BM - 1) / BM; a.tiles_n = (a.N + BN - 1) / BN;
+            a.total_tiles = a.tiles_m * a.tiles_n;
+            a.group_m = group_m_setting();
+            a.kchunk = 0; a.nsplit = 1; a.alpha = 1.f;
+            a.inv_wo = 1.0f / (float)a.Wo; a.inv_howo = 1.0f / (float)(a.Ho * a.Wo);
+            a.wstep = 2; a.wkh0 = kh0; a.wkw0 = kw0; a.wkwfull = g->KW;
+            a.out_s = 2; a.out_ph = ph; a.out_pw = pw; a.out_H = g->H; a.out_W = g->W;
+            a.part_tm0 = ptiles;
+            if (bn) {
+                a.bn_z = (const h16*)bn->z; a.bn_mean = bn->mean; a.bn_rstd = bn->rstd; a.bn_gamma = bn->gamma; a.bn_beta = bn->beta;
+                a.bn_part = bn->part; a.bn_relu = bn->relu;
+                a.bn_add = (const h16*)bn->addend; a.bn_y = (const h16*)bn->y_mask;
+            }
+            grp.tile_start[n] = total;
+            grp.a[n++] = a;
+            total += a.total_tiles;
+            ptiles += a.tiles_m;
+        }
+    for (int i = 0; i < n; ++i) grp.a[i].part_tiles = ptiles;
+    grp.n = n;
+    grp.total_tiles = total;
+    return MH_OK;
+}
+}  // namespace
+
 extern "C" int mh_conv_dgrad(const void* dy, const void* wk, void* dx, float* workspace, const MhConvGeom* g, const MhConvBnBwd* bn,
                              mh_stream_t stream) {
     int Ho, Wo;
@@ -616,53 +736,11 @@ extern "C" int mh_conv_dgrad(const void* dy, const void* wk, void* dx, float* wo
     if (st != MH_OK) return st;
     if (!dy || !wk || !dx) return MH_EINVAL;
     if (((uintptr_t)dy | (uintptr_t)wk | (uintptr_t)dx) & 15) return MH_EINVAL;
-    if (g->stride == 2 && g->KH == g->KW && !(g->H & 1) && !(g->W & 1) && g->pad <= g->KH - 1 && (g->Cout % BK) == 0 && g->KH > 1) {
-        // STRIDE 2 (round 4, second session): input pixel (h, w) only meets the taps kh = (h + pad) mod 2 + 2 j (same along w), so the
-        // pixels of one parity class (ph, pw) form a stride-1 problem over dY with a ceil / floor(K / 2)-tap window whose result lands in
-        // every second row and column of dX: four problems (1 + 2 + 2 + 4 taps for a 3x3 filter: every multiply-add useful) in ONE
-        // launch, no [M][K*K*C] panel in HBM and no col2im pass.  `bn`: as for stride 1, the epilogue masks the gradient and leaves
-        // the BatchNorm sums -- part holds 2 x C x (4 x ceil(B (H/2) (W/2) / 128)) partials (mh_bn2d_bwd_parts sums them all).
-        if (bn && (!bn->z || !bn->mean || !bn->rstd || !bn->gamma || !bn->beta || !bn->part)) return MH_EINVAL;
-        ConvGroup grp = {};
-        const int Hh = g->H / 2, Wh = g->W / 2;
-        int total = 0, ptiles = 0, n = 0;
-        for (int ph = 0; ph < 2; ++ph)
-            for (int pw = 0; pw < 2; ++pw) {
-                const int kh0 = (ph + g->pad) & 1, kw0 = (pw + g->pad) & 1;
-                const int nkh = (g->KH - kh0 + 1) / 2, nkw = (g->KW - kw0 + 1) / 2;
-                if (nkh < 1 || nkw < 1) return MH_ESHAPE;              // (a class without taps: 1x1 filters keep the explicit path)
-                const int padh = nkh - 1 - (ph + g->pad - kh0) / 2, padw = nkw - 1 - (pw + g->pad - kw0) / 2;
-                if (padh != padw || padh < 0) return MH_ESHAPE;
-                ConvArgs a = {};
-                a.src = (const h16*)dy; a.reg = (const h16*)wk; a.out = dx; a.part = nullptr;
-                a.src_bytes = (uint32_t)((size_t)g->B * Ho * Wo * g->Cout * 2);
-                a.reg_bytes = (uint32_t)((size_t)g->Cout * g->ldk * 2);
-                a.H = Ho; a.W = Wo; a.C = g->Cout;
-                a.KH = nkh; a.KW = nkw; a.stride = 1; a.pad = padh;
-                a.Ho = Hh; a.Wo = Wh; a.Mpix = g->B * Hh * Wh;
-                a.M = a.Mpix; a.N = g->C; a.K = nkh * nkw * g->Cout;
-                a.ldreg = g->ldk; a.ldc = g->C; a.Cw = g->C;
-                a.tiles_m = (a.M + BM - 1) / BM; a.tiles_n = (a.N + BN - 1) / BN;
-                a.total_tiles = a.tiles_m * a.tiles_n;
-                a.group_m = group_m_setting();
-                a.kchunk = 0; a.nsplit = 1; a.alpha = 1.f;
-                a.inv_wo = 1.0f / (float)a.Wo; a.inv_howo = 1.0f / (float)(a.Ho * a.Wo);
-                a.wstep = 2; a.wkh0 = kh0; a.wkw0 = kw0; a.wkwfull = g->KW;
-                a.out_s = 2; a.out_ph = ph; a.out_pw = pw; a.out_H = g->H; a.out_W = g->W;
-                a.part_tm0 = ptiles;
-                if (bn) {
-                    a.bn_z = (const h16*)bn->z; a.bn_mean = bn->mean; a.bn_rstd = bn->rstd; a.bn_gamma = bn->gamma; a.bn_beta = bn->beta;
-                    a.bn_part = bn->part; a.bn_relu = bn->relu;
-                    a.bn_add = (const h16*)bn->addend; a.bn_y = (const h16*)bn->y_mask;
-                }
-                grp.tile_start[n] = total;
-                grp.a[n++] = a;
-                total += a.total_tiles;
-                ptiles += a.tiles_m;
-            }
-        for (int i = 0; i < n; ++i) grp.a[i].part_tiles = ptiles;
-        grp.n = n;
-        grp.total_tiles = total;
+    if (parity_geom(g)) {
+        if (bn_incomplete(bn)) return MH_EINVAL;
+        ConvGroup grp;
+        const int st2 = parity_group(dy, wk, dx, g, Ho, Wo, bn, grp);
+        if (st2 != MH_OK) return st2;
         return conv_launch_group<MODE_DGRAD, true>(grp, (hipStream_t)stream);
     }
     // stride 1 (or the strided case above), window inside the padding, a K tile inside one tap of dY; other strided shapes (1x1 / s2
@@ -686,7 +764,7 @@ extern "C" int mh_conv_dgrad(const void* dy, const void* wk, void* dx, float* wo
     a.kchunk = 0; a.nsplit = 1;
     a.alpha = 1.f;
     a.inv_wo = 1.0f / (float)a.Wo; a.inv_howo = 1.0f / (float)(a.Ho * a.Wo);
-    if (bn && (!bn->z || !bn->mean || !bn->rstd || !bn->gamma || !bn->beta || !bn->part)) return MH_EINVAL;
+    if (bn_incomplete(bn)) return MH_EINVAL;
     const int nsplit = workspace ? mh_conv_splitk(g, 1) : 1;
     if (nsplit > 1) {
         set_split(a, nsplit, workspace);
@@ -704,6 +782,45 @@ extern "C" int mh_conv_dgrad(const void* dy, const void* wk, void* dx, float* wo
         a.bn_add = (const h16*)bn->addend; a.bn_y = (const h16*)bn->y_mask;
     }
     return conv_launch<MODE_DGRAD, true>(a, (hipStream_t)stream);
+}
+
+// dx = dgrad(k x k / 2) + dgrad(1x1 / 2, pad 0) of two convolutions that read the same [B][H][W][C] tensor (a residual stage's first block:
+// conv1 and the downsample).  The 1x1 reads pixel (2h', 2w') for its output (h', w') and nothing else; among the k x k's parity classes the
+// one that holds the centre tap (kh, kw) = (pad, pad) covers exactly those pixels from the same output position -- so the 1x1's gradient is
+// Cout2 / 64 more K tiles of that class (its own dy2 and weight, the same f32 accumulators, ONE 16-bit rounding), and the dgrad GEMM into
+// an [M][ldk2] panel + col2im pass + add of the explicit route disappear.
+extern "C" int mh_conv_dgrad_pair(const void* dy, const void* wk, const void* dy2, const void* wk2, int ldk2, int Cout2, void* dx,
+                                  const MhConvGeom* g, const MhConvBnBwd* bn, mh_stream_t stream) {
+    int Ho, Wo;
+    const int st = geom_check(g, Ho, Wo);
+    if (st != MH_OK) return st;
+    if (!dy || !wk || !dy2 || !wk2 || !dx) return MH_EINVAL;
+    if (((uintptr_t)dy | (uintptr_t)wk | (uintptr_t)dy2 | (uintptr_t)wk2 | (uintptr_t)dx) & 15) return MH_EINVAL;
+    if (bn_incomplete(bn)) return MH_EINVAL;
+    if (!parity_geom(g)) return MH_ESHAPE;
+    if (Cout2 < BK || (Cout2 % BK) || ldk2 < g->C || (ldk2 % BK)) return MH_ESHAPE;
+    if ((size_t)g->B * (g->H / 2) * (g->W / 2) * Cout2 * 2 >= 0x80000000ull || (size_t)Cout2 * ldk2 * 2 >= 0x80000000ull) return MH_ESHAPE;
+    // the 1x1 / 2 / pad 0 grid is (H/2) x (W/2); dy2 shares dy's pixel grid, so the k x k must produce the same one (k = 2 pad + 1 or + 2)
+    if (Ho != g->H / 2 || Wo != g->W / 2) return MH_ESHAPE;
+    ConvGroup grp;
+    const int st2 = parity_group(dy, wk, dx, g, Ho, Wo, bn, grp);
+    if (st2 != MH_OK) return st2;
+    ConvPair pr = {};
+    pr.prob = -1;
+    for (int i = 0; i < grp.n; ++i) {
+        const ConvArgs& a = grp.a[i];
+        // tap (pad, pad) is one of the class's taps wkh0 + 2 j: row (b, h', w') of the class IS pixel (2h', 2w'), fed by output (h', w')
+        const bool centre = g->pad >= a.wkh0 && ((g->pad - a.wkh0) & 1) == 0 && g->pad >= a.wkw0 && ((g->pad - a.wkw0) & 1) == 0;
+        if (centre && a.out_ph == 0 && a.out_pw == 0 && a.Ho == Ho && a.Wo == Wo) pr.prob = i;
+    }
+    if (pr.prob < 0) return MH_ESHAPE;
+    pr.src = (const h16*)dy2; pr.reg = (const h16*)wk2;
+    pr.src_bytes = (uint32_t)((size_t)g->B * Ho * Wo * Cout2 * 2);
+    pr.reg_bytes = (uint32_t)((size_t)Cout2 * ldk2 * 2);
+    pr.C2 = Cout2; pr.ldreg = ldk2;
+    pr.nk1 = grp.a[pr.prob].K / BK;
+    grp.a[pr.prob].K += Cout2;
+    return conv_launch_pair(grp, pr, (hipStream_t)stream);
 }
 
 namespace {

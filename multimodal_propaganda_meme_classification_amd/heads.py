@@ -18,7 +18,7 @@ the HIP kernels of ops.py (pool_* / linear_bn_act_* / softmax_gate_*).
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Union
 
 import torch
 import torch.nn as nn
@@ -272,27 +272,45 @@ class KevinMultimodalClassifier(_Composite):
     text tower + image tower = one lockstep ``MultimodalClassifier`` (``towers``; the reference's ``text_model`` and
     ``image_model.image_model``), caption tower = ``TextEncoder`` (``caption_text_model``).  The image tower's
     ``fine_tune`` MLP of ``CustomDenseNet161`` (:571-574) takes the tower's feature width instead of the hard-coded 512
-    (the reference shape-errors for anything but ResNet-18/34)."""
+    (the reference shape-errors for anything but ResNet-18/34).
+
+    ``image="resnet18" | "resnet34"``: the model as SUBMITTED (``image_model = "resnet18"``, the only family the hard-coded
+    ``Linear(512, 512)`` admits): the image tower is ``resnet.ResNet18 / ResNet34`` (``image_model``; its 512-d ``features`` are what
+    timm's ``reset_classifier(0)`` leaves) under ``FineTuneMLP(512, proj)``, the text tower a ``TextEncoder`` of its own
+    (``text_model``), as in ``OrganizersMultimodalClassifier``; ``towers`` is then None.  ``resnet_layers`` / ``resnet_width``: the
+    tower's ``layers=`` / ``width=`` overrides (tests)."""
 
     def __init__(self, fusion_method: str = "concatenation", text: Optional[TextConfig] = None,
-                 image: Optional[ImageConfig] = None, caption: Optional[TextConfig] = None, proj: int = 512,
-                 compute_dtype: str = "bf16", seed: int = 0, grad_stream_scale: float = 0.0):
+                 image: Union[ImageConfig, str, None] = None, caption: Optional[TextConfig] = None, proj: int = 512,
+                 compute_dtype: str = "bf16", seed: int = 0, grad_stream_scale: float = 0.0, resnet_layers=None, resnet_width: int = 64):
         super().__init__()
         # the reference lists four methods (:86); "cross_modal" and "self_attention" build two-input modules that its own
         # three-input forward (:677) cannot call (TypeError on the first batch), so only the two that run are offered
         if fusion_method not in ("concatenation", "mca"):
             raise ValueError(f"Unsupported fusion method: {fusion_method}")
         # defaults = the checkpoints' own dropout (0.1 / 0.1); explicit configs say what they want
-        tc, ic = text or TextConfig(hidden_dropout=0.1, attention_dropout=0.1), image or ImageConfig()
+        tc = text or TextConfig(hidden_dropout=0.1, attention_dropout=0.1)
         cc = caption or TextConfig(vocab_size=30522, hidden_dropout=0.1, attention_dropout=0.1)
         self.fusion_method = fusion_method
-        self.towers = MultimodalClassifier.from_config(ModelConfig(text=tc, image=ic, compute_dtype=compute_dtype,
-                                                                   grad_stream_scale=grad_stream_scale), seed=seed)
+        if isinstance(image, str):
+            from .resnet import RESNETS
+            if image not in ("resnet18", "resnet34"):
+                raise ValueError(f"image must be an ImageConfig, 'resnet18' or 'resnet34', got {image!r}")
+            self.towers = None
+            self.text_model = TextEncoder(tc, pool="cls", compute_dtype=compute_dtype, seed=seed, grad_stream_scale=grad_stream_scale)
+            self.image_model = RESNETS[image](num_classes=0, compute_dtype=compute_dtype, layers=resnet_layers, width=resnet_width, seed=seed + 2,
+                                              grad_stream_scale=grad_stream_scale)
+            image_features = self.image_model.feature_dim
+        else:
+            ic = image or ImageConfig()
+            self.towers = MultimodalClassifier.from_config(ModelConfig(text=tc, image=ic, compute_dtype=compute_dtype,
+                                                                       grad_stream_scale=grad_stream_scale), seed=seed)
+            image_features = ic.hidden
         self.caption_text_model = TextEncoder(cc, pool="cls", compute_dtype=compute_dtype, seed=seed + 1, grad_stream_scale=grad_stream_scale)
         self.text_dropout, self.caption_text_dropout = nn.Dropout(0.3), nn.Dropout(0.3)
         self.text_fc = LinearBNReLU(tc.hidden, proj)
         self.caption_text_fc = LinearBNReLU(cc.hidden, proj)
-        self.image_fine_tune = FineTuneMLP(ic.hidden, proj)
+        self.image_fine_tune = FineTuneMLP(image_features, proj)
         self.fusion_layer = ConcatAttention3(3 * proj, proj) if fusion_method == "concatenation" else MCA3(proj)
         self.output_fc = LinearBNReLU(proj, 1, relu=False)
         self._head_flat = False
@@ -300,11 +318,15 @@ class KevinMultimodalClassifier(_Composite):
     def head_modules(self):
         return [self.text_fc, self.caption_text_fc, self.image_fine_tune, self.fusion_layer, self.output_fc]
 
+    def _loose_modules(self):
+        """every module whose parameters are plain nn.Parameters: the head, and the ResNet tower (it accumulates into an f32 .grad in place)"""
+        return self.head_modules() + ([] if self.towers is not None else [self.image_model])
+
     def _flatten_head(self):
         """The head's parameters live in one flat buffer (flatten_parameters), so the ONE fused ``memehip.Adam`` over
         ``get_params(lr)`` updates them in a single launch and counts them in the global clip norm."""
         if not self._head_flat and next(self.output_fc.parameters()).is_cuda:
-            holder = nn.ModuleList(self.head_modules())
+            holder = nn.ModuleList(self._loose_modules())
             flatten_parameters(holder)
             self._head_holder_flat = holder._memehip_flat
             self._head_flat = True
@@ -321,8 +343,12 @@ class KevinMultimodalClassifier(_Composite):
         ``image_model`` parameters (the whole CustomDenseNet161, its fine_tune MLP included) at ``0.8 * lr``."""
         self._flatten_head()
         attention, text, image = [], [], []
-        for name, p in self.towers.named_parameters():
-            (text if name.startswith("bert.") else image if name.startswith("image_model.") else attention).append(p)
+        if self.towers is not None:
+            for name, p in self.towers.named_parameters():
+                (text if name.startswith("bert.") else image if name.startswith("image_model.") else attention).append(p)
+        else:
+            text += list(self.text_model.parameters())
+            image += list(self.image_model.parameters())
         text += list(self.caption_text_model.parameters())
         image += list(self.image_fine_tune.parameters())
         for m in (self.text_fc, self.caption_text_fc, self.fusion_layer, self.output_fc):
@@ -367,15 +393,18 @@ class KevinMultimodalClassifier(_Composite):
         / ``caption_text_model.model.*`` (transformers BertModel keys), ``image_model.image_model.*`` (timm ViT keys, or the
         transformers ViTModel keys), ``image_model.fine_tune.*``, and the head modules under their own names."""
         mapped, vit = {}, {}
+        prefixes = self._REF_PREFIXES if self.towers is not None else (("text_model.model.", "text_model."),) + self._REF_PREFIXES[1:]
         for k, v in state_dict.items():
             if k.startswith("image_model.image_model."):
                 vit[k[len("image_model.image_model."):]] = v
                 continue
-            for a, b in self._REF_PREFIXES:
+            for a, b in prefixes:
                 if k.startswith(a):
                     k = b + k[len(a):]
                     break
             mapped[k] = v
+        if self.towers is None:
+            return self._load_reference_resnet(mapped, vit, strict)
         if any(k.startswith("blocks.") for k in vit):
             vit = self._timm_vit_to_hf(vit)
         mapped.update({"towers.image_model." + k: v for k, v in vit.items()})
@@ -389,11 +418,30 @@ class KevinMultimodalClassifier(_Composite):
             raise RuntimeError(f"load_reference_state_dict: missing {missing[:4]} unexpected {unexpected[:4]}")
         return nn.modules.module._IncompatibleKeys(missing, unexpected)
 
+    def _load_reference_resnet(self, mapped: dict, resnet: dict, strict: bool):
+        """image="resnet18" | "resnet34": ``image_model.image_model.*`` are timm ResNet keys = torchvision's = the tower's own (no ``fc.*``:
+        Identity after ``reset_classifier(0)`` there, ``num_classes=0`` here)."""
+        mapped.update({"image_model." + k: v for k, v in resnet.items()})
+        own = set(self.state_dict().keys())
+        res = self.load_state_dict(mapped, strict=False)
+        missing = list(res.missing_keys)
+        unexpected = [k for k in res.unexpected_keys if k in mapped and k not in own and not k.endswith("position_ids")
+                      and "token_type_ids" not in k and "pooler." not in k]
+        if strict and (missing or unexpected):
+            raise RuntimeError(f"load_reference_state_dict: missing {missing[:4]} unexpected {unexpected[:4]}")
+        return nn.modules.module._IncompatibleKeys(missing, unexpected)
+
+    def encode_towers(self, text, image, mask):
+        """(text features [B, Dt], image features [B, Di]) f32: the lockstep pair, or the text encoder and the ResNet on their own"""
+        if self.towers is not None:
+            return self.towers.encode(text, image, mask)
+        return self.text_model(text, mask), self.image_model.features(image)
+
     def forward(self, text, image, mask, caption_text, caption_text_mask):
         for t_ in (text, image, mask, caption_text, caption_text_mask):
             if not t_.is_cuda:
                 raise _lib.MemehipError("memehip runs on the HIP device only (no CPU fallback): move the batch with .to(device)")
-        t, v = self.towers.encode(text, image, mask)
+        t, v = self.encode_towers(text, image, mask)
         c = self.caption_text_model(caption_text, caption_text_mask)
         text_output = self.text_fc(self.text_dropout(t))
         caption_output = self.caption_text_fc(self.caption_text_dropout(c))

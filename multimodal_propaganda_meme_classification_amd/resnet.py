@@ -1,5 +1,7 @@
-"""ResNet-50 image tower on the HIP path (BASELINE config 2; the organizers' image encoder:
-``models.resnet50(pretrained=True)`` -> 1000 logits -> ``Linear(1000, 512)``, Multimodal_example_task2C.txt:164-165,183-184).
+"""ResNet image towers on the HIP path: ResNet-50 (BASELINE config 2; the organizers' image encoder:
+``models.resnet50(pretrained=True)`` -> 1000 logits -> ``Linear(1000, 512)``, Multimodal_example_task2C.txt:164-165,183-184) and the
+basic-block ResNet-18 / 34 (the image tower of the submitted Subtask-2C model: ``timm.create_model("resnet18")`` +
+``reset_classifier(0)`` -> 512 features, example_scripts/Multimodal_example_task2C.py:569-574).
 
 ``ResNet50`` has torchvision's module tree and state_dict keys (``conv1.weight``, ``bn1.running_mean``,
 ``layer3.4.conv2.weight``, ``layer2.0.downsample.0.weight``, ``fc.bias`` ...): the ``nn.Conv2d / nn.BatchNorm2d / nn.Linear``
@@ -12,7 +14,8 @@ submodules only HOLD the parameters and running statistics; the arithmetic runs 
   the convolution epilogue's per-tile column sums (``mh_bn2d_fwd_parts``: no pass over the activation), the normalisation is
   fused with the residual add and the ReLU; max pool, global average pool, the 2048 -> 1000 classifier in exact f32;
 * the backward is one opaque autograd node over a typed tape (``Tape``): ``mh_conv_wgrad``, the input gradient by the route
-  ``dgrad_route`` names (``mh_conv_dgrad``; the strided 1x1 downsamples keep the dgrad GEMM + ``mh_col2im_nhwc``), BatchNorm
+  ``dgrad_route`` names (``mh_conv_dgrad``; the strided 1x1 downsamples keep the dgrad GEMM + ``mh_col2im_nhwc`` -- except next to a
+  basic block's 3x3 / 2 conv1, where ``pairs_with`` sends both gradients through one ``mh_conv_dgrad_pair`` launch), BatchNorm
   backward; ``ResNet50.options`` (``TowerOptions``) holds its A/B switches;
 * the 16-bit gradient stream carries ``grad_stream_scale`` (8192 for fp16), removed where parameter gradients are produced.
 
@@ -44,6 +47,8 @@ class TowerOptions:
     strided_dgrad: bool = True       # 3x3 / 2 input gradient as four parity classes of mh_conv_dgrad (off: GEMM + col2im)
     # weight gradients launched together (1: one launch each), clamped to MH_CONV_MAX_GROUP.  6 since the conv kernels deal every problem's
     wgrad_group: int = 6             # tiles to all eight XCDs (round 4, second session: 6.29 -> 6.24 ms; with one run over the concatenated tile list 4 was the best)
+    # a stage's first BasicBlock: the 1x1 / 2 downsample's input gradient as a second K segment of the 3x3 / 2 conv1's centre-tap parity class
+    pair_dgrad: bool = True          # (mh_conv_dgrad_pair; off: GEMM + col2im, then added).  ResNet-50 has no such pair.
 
 
 def dgrad_route(cv, H, W, opts: TowerOptions) -> str:
@@ -56,6 +61,13 @@ def dgrad_route(cv, H, W, opts: TowerOptions) -> str:
     if (cv.stride == 1 or parity) and cv.kh == cv.kw and cv.cout % 64 == 0:
         return IMPLICIT
     return COL2IM
+
+
+def pairs_with(cv, ds, H, W, opts: TowerOptions) -> bool:
+    """Whether the input gradients of `cv` (k x k / 2) and `ds` (1x1 / 2 / pad 0), two _Conv that read the same H x W tensor, go as ONE
+    mh_conv_dgrad_pair launch: cv by parity classes (so an even image), both on the (H/2) x (W/2) output grid, ds.cout % 64 == 0."""
+    return (opts.pair_dgrad and ds.kh == 1 and ds.kw == 1 and ds.stride == 2 and ds.pad == 0 and ds.cout % 64 == 0 and ds.cp == cv.cp
+            and cv.stride == 2 and cv.kh > 1 and dgrad_route(cv, H, W, opts) == IMPLICIT and cv.out_hw(H, W) == (H // 2, W // 2))
 
 
 def epilogue_takes_bn(cv, H, W, opts: TowerOptions, block_out: bool = False) -> bool:
@@ -130,12 +142,15 @@ class _Conv:
         want = max(1, min(64, -(-target // tiles), M // 256))
         return max(1, lib.mh_gemm_ksplit_for(int(M), int(want)))
 
-    def backward(self, lib, dy, x, wk, B, H, W, Ho, Wo, gscale, wjobs, opts, need_dx=True, wq=None, below=None, addend=None):
+    def backward(self, lib, dy, x, wk, B, H, W, Ho, Wo, gscale, wjobs, opts, need_dx=True, wq=None, below=None, addend=None, y_mask=None,
+                 pair=None):
         """dy [M, cout] 16-bit -> (dx [B*H*W, cp] 16-bit or None, the statistics partials of `below` or None).  The weight gradient
         (implicit GEMM over x, mh_conv_wgrad) is deferred into `wq` (flush_wgrads) or launched here; its split-K slabs are queued in
         `wjobs` (summed, un-packed and added to .grad for all convolutions at once at the end of the backward).  The input gradient
         goes by dgrad_route.  `below` (implicit route only: epilogue_takes_bn): the tape record whose BatchNorm (+ReLU) produced x
-        -- the epilogue masks dx for it and sums its statistics, after adding `addend` and by the sign of below.y if that is given."""
+        -- the epilogue masks dx for it and sums its statistics, after adding `addend` and by the sign of `y_mask` if that is given.
+        `pair` (pairs_with): (ds, dy2, wk2) -- the 1x1 / 2 downsample that reads the same x, its dy and packed weight: dx is the sum of both
+        input gradients, from one mh_conv_dgrad_pair launch."""
         M, dev = B * Ho * Wo, dy.device
         if wq is not None:
             wq.append((self, dy, x, B, H, W, Ho, Wo))
@@ -149,6 +164,8 @@ class _Conv:
         route = dgrad_route(self, H, W, opts)
         if below is not None and route != IMPLICIT:
             raise _lib.MemehipError(f"the {route} input gradient has no BatchNorm epilogue")
+        if pair is not None and not pairs_with(self, pair[0], H, W, opts):
+            raise _lib.MemehipError("these two convolutions' input gradients do not pair")
         dx = torch.empty((B * H * W, self.cp), dtype=dy.dtype, device=dev)
         if route == IMPLICIT:
             geom = self.geom(B, H, W)
@@ -158,7 +175,12 @@ class _Conv:
             if below is not None:
                 nblk = (B * H * W + 127) // 128 if self.stride == 1 else 4 * ((B * (H // 2) * (W // 2) + 127) // 128)
                 part = torch.empty((2, self.cp, nblk), dtype=F32, device=dev)
-                fuse = _bn_epilogue(below, part, addend=addend, y_mask=None if addend is None else below.y)
+                fuse = _bn_epilogue(below, part, addend=addend, y_mask=y_mask)
+            if pair is not None:
+                ds, dy2, wk2 = pair
+                check(lib.mh_conv_dgrad_pair(dy.data_ptr(), wk.data_ptr(), dy2.data_ptr(), wk2.data_ptr(), ds.ldk, ds.cout, dx.data_ptr(), geom, fuse,
+                                             _stream()), "mh_conv_dgrad_pair")
+                return dx, part
             check(lib.mh_conv_dgrad(dy.data_ptr(), wk.data_ptr(), dx.data_ptr(), None if ws is None else ws.data_ptr(), geom, fuse, _stream()),
                   "mh_conv_dgrad")
             return dx, part
@@ -270,11 +292,20 @@ class ConvBnRec:
 
 @dataclass
 class BlockRec:
-    """One bottleneck's four layers: ResNet50._block_units, and on the tape their records of one forward."""
+    """One residual block's layers (bottleneck: conv1-3; basic block: conv1-2) + downsample: _ResNet._block_units, and on the tape their
+    records of one forward.  `chain`: the main branch in order; its last unit takes the residual and the block's ReLU."""
     conv1: ConvBnRec
     conv2: ConvBnRec
-    conv3: ConvBnRec
+    conv3: Optional[ConvBnRec] = None
     downsample: Optional[ConvBnRec] = None
+
+    @property
+    def chain(self) -> List[ConvBnRec]:
+        return [u for u in (self.conv1, self.conv2, self.conv3) if u is not None]
+
+    @property
+    def units(self) -> List[ConvBnRec]:
+        return self.chain + ([] if self.downsample is None else [self.downsample])
 
 
 @dataclass
@@ -312,6 +343,20 @@ class Bottleneck(nn.Module):
         self.stride = stride
 
 
+class BasicBlock(nn.Module):
+    """torchvision.models.resnet.BasicBlock (= timm's for resnet18 / 34): parameter holder."""
+    expansion = 1
+
+    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: bool = False):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, 3, stride=stride, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, 3, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes, 1, stride=stride, bias=False), nn.BatchNorm2d(planes)) if downsample else None
+        self.stride = stride
+
+
 class _TowerFn(torch.autograd.Function):
     """Opaque autograd node: the whole conv tower forward; backward walks the saved tape."""
 
@@ -328,13 +373,18 @@ class _TowerFn(torch.autograd.Function):
         return (None, None) + tuple(grads[id(p)] for p in ctx.net._tower_params)
 
 
-class ResNet50(nn.Module):
-    """torchvision ``resnet50`` topology and state_dict on the HIP kernels.  ``forward(image f32 [B,3,H,W]) -> logits [B,1000]``
-    (``num_classes`` outputs); ``features(image)`` returns the pooled 2048-d features; ``options``: the backward's TowerOptions."""
+class _ResNet(nn.Module):
+    """torchvision ResNet topology and state_dict over one block type (`block`: Bottleneck / BasicBlock) on the HIP kernels.
+    ``forward(image f32 [B,3,H,W]) -> logits [B, num_classes]`` (``num_classes=0``: no classifier, the features, as timm's
+    ``reset_classifier(0)``); ``features(image)`` returns the pooled ``feature_dim`` features;
+    ``options``: the backward's TowerOptions."""
+    block = None
+    default_layers = None
 
-    def __init__(self, num_classes: int = 1000, compute_dtype: str = "fp16", layers=(3, 4, 6, 3), width: int = 64,
+    def __init__(self, num_classes: int = 1000, compute_dtype: str = "fp16", layers=None, width: int = 64,
                  grad_stream_scale: float = 0.0, seed: int = 0, options: TowerOptions = TowerOptions()):
         super().__init__()
+        block, layers = self.block, (self.default_layers if layers is None else layers)
         if compute_dtype not in ("bf16", "fp16"):
             raise ValueError(f"compute_dtype must be 'bf16' or 'fp16', got {compute_dtype!r}")
         torch.manual_seed(seed)
@@ -348,11 +398,11 @@ class ResNet50(nn.Module):
             blocks = []
             for bi in range(n):
                 s = stride if bi == 0 else 1
-                blocks.append(Bottleneck(inplanes, planes, s, downsample=(bi == 0 and (s != 1 or inplanes != planes * 4))))
-                inplanes = planes * 4
+                blocks.append(block(inplanes, planes, s, downsample=(bi == 0 and (s != 1 or inplanes != planes * block.expansion))))
+                inplanes = planes * block.expansion
             setattr(self, f"layer{li}", nn.Sequential(*blocks))
         self.feature_dim = inplanes
-        self.fc = nn.Linear(inplanes, num_classes)
+        self.fc = nn.Linear(inplanes, num_classes) if num_classes > 0 else nn.Identity()      # 0: timm's reset_classifier(0), forward = features
         for m in self.modules():          # torchvision's initialisation
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
@@ -361,20 +411,20 @@ class ResNet50(nn.Module):
         def unit(conv, bn, cin_pad=None):
             return ConvBnRec(_Conv(conv, cin_pad), _BN(bn))
         self._stem_unit = unit(self.conv1, self.bn1, 8)
-        self._block_units = [BlockRec(unit(b.conv1, b.bn1), unit(b.conv2, b.bn2), unit(b.conv3, b.bn3),
+        self._block_units = [BlockRec(unit(b.conv1, b.bn1), unit(b.conv2, b.bn2), unit(b.conv3, b.bn3) if hasattr(b, "conv3") else None,
                                       None if b.downsample is None else unit(b.downsample[0], b.downsample[1]))
                              for li in range(1, 5) for b in getattr(self, f"layer{li}")]
-        self._units = [self._stem_unit] + [u for b in self._block_units for u in (b.conv1, b.conv2, b.conv3, b.downsample) if u is not None]
+        self._units = [self._stem_unit] + [u for b in self._block_units for u in b.units]
 
     # ---- launches ----------------------------------------------------------------------------------------------
     def _forward_tape(self, image: torch.Tensor, training: bool) -> Tape:
         if not image.is_cuda:
-            raise _lib.MemehipError("ResNet50 runs on the HIP device only (no CPU fallback): move the batch with .to(device)")
+            raise _lib.MemehipError(f"{type(self).__name__} runs on the HIP device only (no CPU fallback): move the batch with .to(device)")
         lib = _lib.load(self.compute_dtype)
         T16 = torch.float16 if self.compute_dtype == "fp16" else torch.bfloat16
         B, Cc, H, W = image.shape
         if Cc != 3:
-            raise ValueError("ResNet50 expects 3-channel images")
+            raise ValueError(f"{type(self).__name__} expects 3-channel images")
         x = torch.empty((B * H * W, 8), dtype=T16, device=image.device)
         img32 = image.to(F32).contiguous()      # named: a temporary would be freed (and its block re-used) before the launch
         check(lib.mh_nchw_to_nhwc(img32.data_ptr(), x.data_ptr(), B, 3, H, W, 8, _stream()), "mh_nchw_to_nhwc")
@@ -392,16 +442,19 @@ class ResNet50(nn.Module):
         arg = torch.empty((B * h * w, C1), dtype=torch.uint8, device=image.device)
         check(lib.mh_maxpool_fwd(stem.y.data_ptr(), x.data_ptr(), arg.data_ptr(), B, stem.Ho, stem.Wo, C1, 3, 2, 1, _stream()), "mh_maxpool_fwd")
         blocks = []
-        for u in self._block_units:
-            c1 = conv_bn(u.conv1, x, h, w)
-            c2 = conv_bn(u.conv2, c1.y, c1.Ho, c1.Wo)
+        for u in self._block_units:      # one rule for both block types: the chain but its last unit, the downsample, the last unit + residual
+            *body, last = u.chain
+            recs, y, hh, ww = [], x, h, w
+            for v in body:
+                recs.append(conv_bn(v, y, hh, ww))
+                y, hh, ww = recs[-1].y, recs[-1].Ho, recs[-1].Wo
             ds = None if u.downsample is None else conv_bn(u.downsample, x, h, w, relu=False)
-            c3 = conv_bn(u.conv3, c2.y, c2.Ho, c2.Wo, residual=x if ds is None else ds.y, relu=True)
-            blocks.append(BlockRec(c1, c2, c3, ds))
-            x, h, w = c3.y, c3.Ho, c3.Wo
+            recs.append(conv_bn(last, y, hh, ww, residual=x if ds is None else ds.y, relu=True))
+            blocks.append(BlockRec(*recs, downsample=ds))
+            x, h, w = recs[-1].y, recs[-1].Ho, recs[-1].Wo
         pooled = torch.empty((B, self.feature_dim), dtype=F32, device=image.device)
         check(lib.mh_avgpool_fwd(x.data_ptr(), pooled.data_ptr(), B, h * w, self.feature_dim, _stream()), "mh_avgpool_fwd")
-        if training:      # nn.BatchNorm2d's step counter, all 53 of them in one multi-tensor launch
+        if training:      # nn.BatchNorm2d's step counter, all of them (53 in ResNet-50) in one multi-tensor launch
             torch._foreach_add_([u.bn.mod.num_batches_tracked for u in self._units], 1)
         return Tape(B, stem, PoolRec(arg, stem.Ho, stem.Wo, C1), blocks, pooled, (h, w), T16)
 
@@ -439,11 +492,12 @@ class ResNet50(nn.Module):
         group = max(1, min(opts.wgrad_group, _lib.MH_CONV_MAX_GROUP))
         wq = [] if group > 1 else None
 
-        def conv_bn_bwd(rec, dy, want_dres=False, need_dx=True, pre_part=None, below=None, addend=None):
-            """Backward of one conv + BatchNorm (+ReLU) -> (dx, the residual branch's gradient, statistics partials of `below`).
+        def conv_bn_bwd(rec, dy, want_dres=False, need_dx=True, pre_part=None, below=None, block_out=False, addend=None, pair=None):
+            """Backward of one conv + BatchNorm (+ReLU) -> (dx, the residual branch's gradient, statistics partials of `below`, dz).
             `pre_part`: dy arrives MASKED with its column sums already taken by the dgrad epilogue that produced it.  `below`: the
             record whose output is this convolution's input -- when its BatchNorm has a ReLU and no residual, this dgrad's epilogue
-            does that BatchNorm's masking and statistics (epilogue_takes_bn).  `addend`: the block_out form, see the block loop."""
+            does that BatchNorm's masking and statistics (epilogue_takes_bn).  `block_out` (+ `addend`): the block_out form, `pair`
+            (a downsample's record and its dz): the two input gradients in one launch; see the block loop."""
             M = B * rec.Ho * rec.Wo
             if pre_part is not None:
                 dz = rec.bn.backward_parts(lib, dy, rec.z, rec.mean, rec.rstd, pre_part, M, self.gscale, grads)
@@ -452,31 +506,43 @@ class ResNet50(nn.Module):
                 # the ReLU mask: from y where a residual was added before the ReLU, recomputed from z otherwise (one tensor less to read)
                 dz, dres = rec.bn.backward(lib, dy, rec.z, rec.y if (rec.relu and rec.has_res) else None, rec.mean, rec.rstd, M, rec.relu,
                                            want_dres, self.gscale, grads)
-            if addend is None and not (below is not None and below.relu and not below.has_res
-                                       and epilogue_takes_bn(rec.conv, rec.H, rec.W, opts)):
+            if not block_out and not (below is not None and below.relu and not below.has_res
+                                      and epilogue_takes_bn(rec.conv, rec.H, rec.W, opts)):
                 below = None
             dxin, part = rec.conv.backward(lib, dz, rec.x, rec.wk, B, rec.H, rec.W, rec.Ho, rec.Wo, self.gscale, wjobs, opts, need_dx,
-                                           wq=wq, below=below, addend=addend)
+                                           wq=wq, below=below, addend=addend, y_mask=below.y if block_out else None,
+                                           pair=None if pair is None else (pair[0].conv, pair[1], pair[0].wk))
             if wq is not None and len(wq) >= group:
                 flush_wgrads(lib, wq, wjobs, self.gscale)
-            return dxin, dres, part
+            return dxin, dres, part, dz
 
         dx_part = None       # statistics partials of the gradient in `dx` when a block's conv1 epilogue already masked it for the bn3 below
         for k in reversed(range(len(tape.blocks))):
             blk, below = tape.blocks[k], (tape.blocks[k - 1] if k else None)
-            # conv3 + bn3 (+ residual + relu): d_ident is the gradient of the identity branch; its dgrad epilogue already does
-            # bn2's masking + statistics, conv2's does bn1's
-            d_o, d_ident, part2 = conv_bn_bwd(blk.conv3, dx, want_dres=True, below=blk.conv2, pre_part=dx_part)
-            if blk.downsample is not None:
-                d_ident, _, _ = conv_bn_bwd(blk.downsample, d_ident)      # downsample conv + bn (no relu)
-            d_o, _, part1 = conv_bn_bwd(blk.conv2, d_o, below=blk.conv1, pre_part=part2)
-            c1 = blk.conv1
+            # One rule for both block types.  The chain's last unit (bn3 / bn2 + residual + relu): d_ident is the gradient of the identity branch;
+            # every unit's dgrad epilogue already does the masking + statistics of the BatchNorm below it in the chain
+            *body, last = blk.chain
+            c1, ds = blk.conv1, blk.downsample
+            d_o, d_ident, part, _ = conv_bn_bwd(last, dx, want_dres=True, below=body[-1], pre_part=dx_part)
+            # a basic block's 3x3 / 2 conv1 next to the 1x1 / 2 downsample: both read the block input -- the downsample leaves only its dz here,
+            # its input gradient is a second K segment of conv1's dgrad (mh_conv_dgrad_pair)
+            pair = None
+            if ds is not None:
+                paired = pairs_with(c1.conv, ds.conv, c1.H, c1.W, opts)
+                d_ident, _, _, dz_ds = conv_bn_bwd(ds, d_ident, need_dx=not paired)      # downsample conv + bn (no relu)
+                pair = (ds, dz_ds) if paired else None
+            for j in range(len(body) - 1, 0, -1):
+                d_o, _, part, _ = conv_bn_bwd(body[j], d_o, below=body[j - 1], pre_part=part)
             if below is not None and epilogue_takes_bn(c1.conv, c1.H, c1.W, opts, block_out=True):
-                # conv1's input is the output y = relu(bn3(z) + residual) of the block below: its dgrad epilogue adds the gradient arriving
-                # through the other branch (d_ident), masks by y > 0 and takes bn3's statistics -- no mh_add_h16 pass, no statistics pass (round 4)
-                dx, _, dx_part = conv_bn_bwd(c1, d_o, pre_part=part1, below=below.conv3, addend=d_ident)
+                # conv1's input is the output y = relu(bn(z) + residual) of the block below: its dgrad epilogue adds the gradient arriving
+                # through the other branch (d_ident; paired: already in the accumulators), masks by y > 0 and takes that BatchNorm's statistics
+                # -- no mh_add_h16 pass, no statistics pass (round 4)
+                dx, _, dx_part, _ = conv_bn_bwd(c1, d_o, pre_part=part, below=below.chain[-1], block_out=True, addend=d_ident, pair=pair)
+            elif pair is not None:
+                dx, _, _, _ = conv_bn_bwd(c1, d_o, pre_part=part, pair=pair)
+                dx_part = None
             else:
-                d_o, _, _ = conv_bn_bwd(c1, d_o, pre_part=part1)
+                d_o, _, _, _ = conv_bn_bwd(c1, d_o, pre_part=part)
                 dx, dx_part = torch.empty_like(d_o), None
                 check(lib.mh_add_h16(d_o.data_ptr(), d_ident.data_ptr(), dx.data_ptr(), d_o.numel(), _stream()), "mh_add_h16")
         pool = tape.pool
@@ -503,16 +569,37 @@ class ResNet50(nn.Module):
         return self._forward_tape(image, training=self.training).pooled
 
     def forward(self, image: torch.Tensor) -> torch.Tensor:
-        return fused.linear(self.features(image), self.fc.weight, self.fc.bias)
+        f = self.features(image)
+        return f if isinstance(self.fc, nn.Identity) else fused.linear(f, self.fc.weight, self.fc.bias)
+
+
+class ResNet50(_ResNet):
+    """torchvision ``resnet50``: bottleneck blocks (3, 4, 6, 3), 2048-d features."""
+    block, default_layers = Bottleneck, (3, 4, 6, 3)
+
+
+class ResNet18(_ResNet):
+    """torchvision / timm ``resnet18``: basic blocks (2, 2, 2, 2), 512-d features (what ``reset_classifier(0)`` leaves)."""
+    block, default_layers = BasicBlock, (2, 2, 2, 2)
+
+
+class ResNet34(_ResNet):
+    """torchvision / timm ``resnet34``: basic blocks (3, 4, 6, 3), 512-d features."""
+    block, default_layers = BasicBlock, (3, 4, 6, 3)
+
+
+RESNETS = {"resnet50": ResNet50, "resnet18": ResNet18, "resnet34": ResNet34}
 
 
 class ResNetClassifier(nn.Module):
-    """Subtask-2B surface over ``ResNet50`` (ResNet_example_task2B.py:206-221): ``model(pixel_values=..., labels=...)`` ->
-    ``(loss, logits)``; without labels ``logits``."""
+    """Subtask-2B surface over a ResNet tower (ResNet_example_task2B.py:206-221): ``model(pixel_values=..., labels=...)`` ->
+    ``(loss, logits)``; without labels ``logits``.  ``arch``: "resnet50" (default) | "resnet18" | "resnet34"."""
 
-    def __init__(self, num_labels: int = 2, compute_dtype: str = "fp16", **kw):
+    def __init__(self, num_labels: int = 2, compute_dtype: str = "fp16", arch: str = "resnet50", **kw):
         super().__init__()
-        self.resnet = ResNet50(num_classes=num_labels, compute_dtype=compute_dtype, **kw)
+        if arch not in RESNETS:
+            raise ValueError(f"arch must be one of {sorted(RESNETS)}, got {arch!r}")
+        self.resnet = RESNETS[arch](num_classes=num_labels, compute_dtype=compute_dtype, **kw)
         self.loss_fct = CrossEntropyLoss()
 
     def forward(self, pixel_values=None, labels=None, **unused):
