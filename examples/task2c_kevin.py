@@ -12,9 +12,12 @@ the way the reference writes it:
 
 Towers, poolings, Linear+BatchNorm1d+ReLU projections, ConcatAttention3, the focal loss and Adam all run in libmemehip.
 Synthetic inputs (no dataset or checkpoints offline).   python examples/task2c_kevin.py [--full] [--caption-model {bert,roberta}]
-                                                                                          [--image-model {vit,resnet18}]
+                                                                                          [--image-model {vit,resnet18,convnext_tiny}]
 --image-model resnet18: the image tower is the submitted model's ``image_model = "resnet18"`` (:82 default; the only family its
 hard-coded ``Linear(512, 512)`` admits) -- resnet.ResNet18 under FineTuneMLP(512, proj), the text tower a TextEncoder of its own.
+--image-model convnext_tiny: the organizers' own image backbone (baselines/extract_feat.py) under the same head --
+convnext.ConvNeXtTiny through its differentiable tower() under FineTuneMLP(768, proj); bf16, since a from-scratch layer_scale of 1e-6
+underflows in fp16's folded weight (a released checkpoint's 0.1 ... 1 does not).
 --caption-model roberta: the caption tower is the submitted model's ``english_text_model = "roberta-base"`` (:81) --
 TextConfig.roberta_base (position ids from the input ids) with the RoBERTa tokenizers' special ids.
 """
@@ -32,9 +35,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--full", action="store_true")
     ap.add_argument("--caption-model", choices=("bert", "roberta"), default="bert")
-    ap.add_argument("--image-model", choices=("vit", "resnet18"), default="vit")
+    ap.add_argument("--image-model", choices=("vit", "resnet18", "convnext_tiny"), default="vit")
     args = ap.parse_args()
     small, roberta, resnet = not args.full, args.caption_model == "roberta", args.image_model == "resnet18"
+    convnext = args.image_model == "convnext_tiny"
+    named = args.image_model if (resnet or convnext) else None          # a tower picked by name instead of an ImageConfig
+    dtype = "bf16" if convnext else "fp16"
     device = torch.device("cuda")
     torch.manual_seed(0)
     if small:
@@ -43,13 +49,14 @@ def main():
         cc = memehip.TextConfig(vocab_size=2000, hidden=128, layers=2, heads=2, intermediate=256, max_position=64)
         if roberta:
             cc = memehip.TextConfig.roberta_base(vocab_size=2000, hidden=128, layers=2, heads=2, intermediate=256, max_position=66)
-        model = memehip.KevinMultimodalClassifier("concatenation", text=tc, image="resnet18" if resnet else ic, caption=cc, proj=128,
-                                                  compute_dtype="fp16", resnet_layers=(1, 1, 1, 1) if resnet else None)
+        model = memehip.KevinMultimodalClassifier("concatenation", text=tc, image=named or ic, caption=cc, proj=128,
+                                                  compute_dtype=dtype, resnet_layers=(1, 1, 1, 1) if resnet else None,
+                                                  convnext_depths=(1, 1, 1, 1) if convnext else None)
         B, S = 8, 32
     else:          # AraBERT-base + ViT-B/16 + bert-base-uncased captions
         cc = memehip.TextConfig.roberta_base(hidden_dropout=0.1, attention_dropout=0.1) if roberta else None
         tc, ic = memehip.TextConfig(hidden_dropout=0.1, attention_dropout=0.1), memehip.ImageConfig()
-        model = memehip.KevinMultimodalClassifier("concatenation", text=tc, image="resnet18" if resnet else ic, caption=cc, compute_dtype="fp16")
+        model = memehip.KevinMultimodalClassifier("concatenation", text=tc, image=named or ic, caption=cc, compute_dtype=dtype)
         cc = cc or memehip.TextConfig(vocab_size=30522)
         B, S = 32, 128
     model.to(device).train()

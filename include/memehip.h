@@ -652,15 +652,34 @@ int mh_add_h16(const void* a, const void* b, void* y, int64_t n, mh_stream_t str
 /* ------------------------------------------------------------------------------------------
  * Depthwise convolution (ConvNeXt-tiny, the SVM baseline's image features: baselines/extract_feat.py:52-60 calls
  * img_model.avgpool(img_model.features(images)) on torchvision convnext_tiny; CNBlock's Conv2d(dim, dim, 7, padding=3, groups=dim)).
- * Forward only (the extractor runs under torch.no_grad()).
+ * The extractor runs the forward under torch.no_grad(); the backward trains the same tower (convnext.ConvNeXtTiny.tower).
  *   mh_dwconv_weight_pack: torch weight f32 [C][1][K][K] -> tap-major f32 [K*K][C]
  *   mh_dwconv_nhwc: y[b][h][w][c] = bias[c] + sum_{i,j} wt[i*K+j][c] * x[b][h+i-K/2][w+j-K/2][c] (zero outside), 16-bit NHWC in / out,
  *                   f32 accumulation; C % 8 == 0, K == 7, stride 1.
+ *   mh_dwconv_nhwc_dgrad: dx[b][h][w][c] = addend[b][h][w][c] + sum_{i,j} wt[(K-1-i)*K + (K-1-j)][c] * dy[b][h+i-K/2][w+j-K/2][c]: the
+ *                   forward kernel with the taps of the SAME [K*K][C] weight image read in reverse; addend (16-bit, or NULL): the
+ *                   CNBlock's residual-branch gradient, added in f32 before the one rounding.  Shape rules of the forward.
+ *   mh_dwconv_nhwc_wgrad: dw[c][0][i][j] (f32, torch layout) = scale * sum_{b,h,w} dy[b][h][w][c] * x[b][h+i-K/2][w+j-K/2][c] (zero
+ *                   outside), dbias[c] (or NULL) = scale * sum dy[b][h][w][c]; accum != 0 adds into dw / dbias.  x and dy are read
+ *                   once; workgroups leave one f32 partial per slab of (image, tile) units in `workspace` (>=
+ *                   mh_dwconv_wgrad_workspace_elems(B, H, W, C, K) f32 elements; 0 = the shape is refused), a second kernel sums the
+ *                   slabs in a fixed order: no atomics, bit-identical from run to run.
+ *   mh_layer_scale_bwd: CNBlock.layer_scale is folded into the second Linear (W' = gamma W, b' = gamma b), so the weight-gradient GEMM
+ *                   yields dWp = dout^T h [C][K] and dbp = colsum(dout) [C] (f32).  One wave per row c:
+ *                   dgamma[c] = sum_k W[c][k] dWp[c][k] + b[c] dbp[c], dW = gamma[c] dWp, db = gamma[c] dbp.  dW / db may BE dWp / dbp (in
+ *                   place) when accum == 0; accum != 0 adds into dW, db and dgamma (then they must be buffers of their own).  K % 4 == 0.
  * The block's LayerNorm / Linear / GELU / Linear + residual run on mh_layernorm_fwd and mh_gemm_bf16_grouped; the patchify
  * stem and the 2x2 / stride-2 downsampling convolutions on mh_im2col_nhwc + mh_gemm_bf16_grouped (bias in the epilogue).
  * ------------------------------------------------------------------------------------------ */
 int mh_dwconv_weight_pack(const float* w, float* wt, int C, int K, mh_stream_t stream);
 int mh_dwconv_nhwc(const void* x, const float* wt, const float* bias, void* y, int B, int H, int W, int C, int K, mh_stream_t stream);
+int mh_dwconv_nhwc_dgrad(const void* dy, const float* wt, const void* addend, void* dx, int B, int H, int W, int C, int K,
+                         mh_stream_t stream);
+int64_t mh_dwconv_wgrad_workspace_elems(int B, int H, int W, int C, int K);
+int mh_dwconv_nhwc_wgrad(const void* x, const void* dy, float* dw, float* dbias, float* workspace, int B, int H, int W, int C, int K,
+                         float scale, int accum, mh_stream_t stream);
+int mh_layer_scale_bwd(const float* W, const float* b, const float* gamma, const float* dWp, const float* dbp, float* dW, float* db,
+                       float* dgamma, int C, int K, int accum, mh_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimizer (torch.optim.Adam / AdamW, Multimodal_example_task2C.txt:249,217; HF Trainer

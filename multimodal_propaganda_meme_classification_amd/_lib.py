@@ -215,6 +215,10 @@ _PROTOS = {
     "mh_add_h16": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
     "mh_dwconv_weight_pack": [c_void_p, c_void_p, c_int, c_int, c_void_p],
     "mh_dwconv_nhwc": [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
+    "mh_dwconv_nhwc_dgrad": [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
+    "mh_dwconv_wgrad_workspace_elems": [c_int] * 5,
+    "mh_dwconv_nhwc_wgrad": [c_void_p] * 5 + [c_int] * 5 + [c_float, c_int, c_void_p],
+    "mh_layer_scale_bwd": [c_void_p] * 8 + [c_int, c_int, c_int, c_void_p],
     "mh_ce_fwd_bwd": [c_void_p] * 5 + [c_int, c_int, c_float, c_void_p, c_void_p],
     "mh_focal_fwd_bwd": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_void_p, c_void_p],
     "mh_adam_skip_account": [C.POINTER(MhAdamSkipGroups), c_void_p, c_void_p, c_void_p, C.POINTER(MhLossScale), c_void_p],
@@ -231,7 +235,8 @@ _PROTOS = {
     "mh_version": [],
     "mh_status_str": [c_int],
 }
-_RESTYPES = {"mh_version": C.c_char_p, "mh_status_str": C.c_char_p, "mh_bn2d_workspace_elems": c_int64}
+_RESTYPES = {"mh_version": C.c_char_p, "mh_status_str": C.c_char_p, "mh_bn2d_workspace_elems": c_int64,
+             "mh_dwconv_wgrad_workspace_elems": c_int64}
 # extra entry points of the LAB build (csrc/lab/memehip_lab.h; `make LAB=1`), bound only when the loaded library has them
 _LAB_PROTOS = {"mh_gemm_set_variant": ([c_int], c_int), "mh_gemm_streamk_workspace_bytes": ([], c_int64),
                "mh_gemm_set_streamk": ([c_void_p, c_int], c_int)}

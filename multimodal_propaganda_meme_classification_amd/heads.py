@@ -278,11 +278,21 @@ class KevinMultimodalClassifier(_Composite):
     ``Linear(512, 512)`` admits): the image tower is ``resnet.ResNet18 / ResNet34`` (``image_model``; its 512-d ``features`` are what
     timm's ``reset_classifier(0)`` leaves) under ``FineTuneMLP(512, proj)``, the text tower a ``TextEncoder`` of its own
     (``text_model``), as in ``OrganizersMultimodalClassifier``; ``towers`` is then None.  ``resnet_layers`` / ``resnet_width``: the
-    tower's ``layers=`` / ``width=`` overrides (tests)."""
+    tower's ``layers=`` / ``width=`` overrides (tests).
+
+    ``image="convnext_tiny"``: the organizers' own image backbone (baselines/extract_feat.py) under the submitted model's head --
+    ``timm.create_model(image_model)`` takes any backbone name, and ``FineTuneMLP`` is sized from the tower here.  The image tower is
+    ``convnext.ConvNeXtTiny(num_classes=0)`` called through its differentiable ``tower()`` (768 features) under ``FineTuneMLP(768, proj)``;
+    text tower, ``towers=None``, parameter groups and the flat head as for the ResNet branch.  ``convnext_depths`` / ``convnext_dims``: the
+    tower's ``depths=`` / ``dims=`` overrides (tests).  The tower has torchvision's ``convnext_tiny`` module names and
+    ``load_reference_state_dict`` accepts exactly those under ``image_model.image_model.``; timm's ConvNeXt key names (``stem.*``,
+    ``stages.N.blocks.M.conv_dw`` ...) and its pooled-then-normalised head are NOT mapped.  No stochastic depth (timm's default of 0);
+    in fp16 a layer_scale near 1e-6 underflows in the folded 16-bit weight -- train from scratch in bf16 (convnext.py)."""
 
     def __init__(self, fusion_method: str = "concatenation", text: Optional[TextConfig] = None,
                  image: Union[ImageConfig, str, None] = None, caption: Optional[TextConfig] = None, proj: int = 512,
-                 compute_dtype: str = "bf16", seed: int = 0, grad_stream_scale: float = 0.0, resnet_layers=None, resnet_width: int = 64):
+                 compute_dtype: str = "bf16", seed: int = 0, grad_stream_scale: float = 0.0, resnet_layers=None, resnet_width: int = 64,
+                 convnext_depths=None, convnext_dims=None):
         super().__init__()
         # the reference lists four methods (:86); "cross_modal" and "self_attention" build two-input modules that its own
         # three-input forward (:677) cannot call (TypeError on the first batch), so only the two that run are offered
@@ -294,12 +304,17 @@ class KevinMultimodalClassifier(_Composite):
         self.fusion_method = fusion_method
         if isinstance(image, str):
             from .resnet import RESNETS
-            if image not in ("resnet18", "resnet34"):
-                raise ValueError(f"image must be an ImageConfig, 'resnet18' or 'resnet34', got {image!r}")
+            if image not in ("resnet18", "resnet34", "convnext_tiny"):
+                raise ValueError(f"image must be an ImageConfig, 'resnet18' or 'resnet34', or 'convnext_tiny', got {image!r}")
             self.towers = None
             self.text_model = TextEncoder(tc, pool="cls", compute_dtype=compute_dtype, seed=seed, grad_stream_scale=grad_stream_scale)
-            self.image_model = RESNETS[image](num_classes=0, compute_dtype=compute_dtype, layers=resnet_layers, width=resnet_width, seed=seed + 2,
-                                              grad_stream_scale=grad_stream_scale)
+            if image == "convnext_tiny":
+                from .convnext import ConvNeXtTiny
+                self.image_model = ConvNeXtTiny(num_classes=0, compute_dtype=compute_dtype, depths=convnext_depths or (3, 3, 9, 3),
+                                                dims=convnext_dims or (96, 192, 384, 768), seed=seed + 2, grad_stream_scale=grad_stream_scale)
+            else:
+                self.image_model = RESNETS[image](num_classes=0, compute_dtype=compute_dtype, layers=resnet_layers, width=resnet_width, seed=seed + 2,
+                                                  grad_stream_scale=grad_stream_scale)
             image_features = self.image_model.feature_dim
         else:
             ic = image or ImageConfig()
@@ -319,7 +334,7 @@ class KevinMultimodalClassifier(_Composite):
         return [self.text_fc, self.caption_text_fc, self.image_fine_tune, self.fusion_layer, self.output_fc]
 
     def _loose_modules(self):
-        """every module whose parameters are plain nn.Parameters: the head, and the ResNet tower (it accumulates into an f32 .grad in place)"""
+        """every module whose parameters are plain nn.Parameters: the head, and the ResNet / ConvNeXt tower (it accumulates into an f32 .grad in place)"""
         return self.head_modules() + ([] if self.towers is not None else [self.image_model])
 
     def _flatten_head(self):
@@ -420,7 +435,11 @@ class KevinMultimodalClassifier(_Composite):
 
     def _load_reference_resnet(self, mapped: dict, resnet: dict, strict: bool):
         """image="resnet18" | "resnet34": ``image_model.image_model.*`` are timm ResNet keys = torchvision's = the tower's own (no ``fc.*``:
-        Identity after ``reset_classifier(0)`` there, ``num_classes=0`` here)."""
+        Identity after ``reset_classifier(0)`` there, ``num_classes=0`` here).  image="convnext_tiny": torchvision's ``convnext_tiny`` keys
+        (``features.N...``; its ``classifier.*`` has no counterpart in a ``num_classes=0`` tower and is left out); timm's names are not mapped."""
+        from .convnext import ConvNeXtTiny
+        if isinstance(self.image_model, ConvNeXtTiny):
+            resnet = {k: v for k, v in resnet.items() if not k.startswith("classifier.")}
         mapped.update({"image_model." + k: v for k, v in resnet.items()})
         own = set(self.state_dict().keys())
         res = self.load_state_dict(mapped, strict=False)
@@ -435,7 +454,9 @@ class KevinMultimodalClassifier(_Composite):
         """(text features [B, Dt], image features [B, Di]) f32: the lockstep pair, or the text encoder and the ResNet on their own"""
         if self.towers is not None:
             return self.towers.encode(text, image, mask)
-        return self.text_model(text, mask), self.image_model.features(image)
+        from .convnext import ConvNeXtTiny
+        tower = self.image_model.tower if isinstance(self.image_model, ConvNeXtTiny) else self.image_model.features
+        return self.text_model(text, mask), tower(image)
 
     def forward(self, text, image, mask, caption_text, caption_text_mask):
         for t_ in (text, image, mask, caption_text, caption_text_mask):

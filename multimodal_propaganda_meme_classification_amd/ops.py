@@ -528,6 +528,64 @@ def copy2d_words(src, ld_src, dst, ld_dst, rows, cols, pad_to):
     return dst
 
 
+def dwconv_dgrad(dy, wt, B, H, W, addend=None, dx=None, K: int = 7):
+    """mh_dwconv_nhwc_dgrad: dx [B*H*W, C] 16-bit = (addend +) the depthwise K x K input gradient of dy, over the forward's tap-major
+    f32 weight image wt [K*K, C]."""
+    _chk(dy, BF16, "dy"), _chk(wt, F32, "wt")
+    C = dy.shape[-1]
+    if dy.numel() != B * H * W * C or wt.numel() != K * K * C:
+        raise ValueError("dwconv_dgrad: dy / wt do not have the sizes B, H, W, C, K imply")
+    dx = torch.empty_like(dy) if dx is None else _chk(dx, BF16, "dx")
+    if addend is not None:
+        _chk(addend, BF16, "addend")
+    if dx.numel() != dy.numel() or dx.dtype != dy.dtype or (addend is not None and (addend.numel() != dy.numel() or addend.dtype != dy.dtype)):
+        raise ValueError("dwconv_dgrad: dx / addend must match dy")
+    check(_L(dy).mh_dwconv_nhwc_dgrad(_p(dy), _p(wt), _p(addend), _p(dx), B, H, W, C, K, _stream()), "mh_dwconv_nhwc_dgrad")
+    return dx
+
+
+def dwconv_wgrad_workspace_elems(B, H, W, C, K: int = 7) -> int:
+    """f32 elements of mh_dwconv_nhwc_wgrad's slab workspace (0: the shape is refused)"""
+    return int(_lib.load().mh_dwconv_wgrad_workspace_elems(B, H, W, C, K))
+
+
+def dwconv_wgrad(x, dy, dw, dbias, B, H, W, scale: float = 1.0, accum: bool = False, workspace=None, K: int = 7):
+    """mh_dwconv_nhwc_wgrad: dw f32 [C, 1, K, K] (torch layout) and dbias f32 [C] (or None) from x, dy [B*H*W, C] 16-bit; `workspace`:
+    f32, at least dwconv_wgrad_workspace_elems(...) elements (allocated when None)."""
+    _chk(x, BF16, "x"), _chk(dy, BF16, "dy"), _chk(dw, F32, "dw")
+    C = x.shape[-1]
+    if x.dtype != dy.dtype or x.numel() != B * H * W * C or dy.numel() != x.numel() or dw.numel() != C * K * K:
+        raise ValueError("dwconv_wgrad: x / dy / dw do not have the sizes B, H, W, C, K imply")
+    if dbias is not None and (_chk(dbias, F32, "dbias").numel() != C):
+        raise ValueError("dwconv_wgrad: dbias must hold C elements")
+    need = dwconv_wgrad_workspace_elems(B, H, W, C, K)
+    if need <= 0:
+        raise _lib.MemehipError(f"mh_dwconv_nhwc_wgrad: unsupported shape B={B} H={H} W={W} C={C} K={K}")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=F32, device=x.device)
+    elif _chk(workspace, F32, "workspace").numel() < need:
+        raise ValueError(f"dwconv_wgrad: workspace holds {workspace.numel()} elements, {need} needed")
+    check(_L(x).mh_dwconv_nhwc_wgrad(_p(x), _p(dy), _p(dw), _p(dbias), _p(workspace), B, H, W, C, K, float(scale), int(accum), _stream()),
+          "mh_dwconv_nhwc_wgrad")
+    return dw
+
+
+def layer_scale_bwd(W, b, gamma, dWp, dbp, dgamma, dW=None, db=None, accum: bool = False):
+    """mh_layer_scale_bwd over a second Linear with layer_scale folded in: dWp [C, K] / dbp [C] (f32) are the folded layer's gradients;
+    dgamma[c] = sum_k W dWp + b dbp, dW = gamma dWp, db = gamma dbp.  dW / db default to dWp / dbp (in place); accum adds into dW, db, dgamma."""
+    dW, db = dWp if dW is None else dW, dbp if db is None else db
+    for nm, t in (("W", W), ("b", b), ("gamma", gamma), ("dWp", dWp), ("dbp", dbp), ("dW", dW), ("db", db), ("dgamma", dgamma)):
+        _chk(t, F32, nm)
+    C, K = W.shape
+    if any(t.numel() != C * K for t in (dWp, dW)) or any(t.numel() != C for t in (b, gamma, dbp, db, dgamma)):
+        raise ValueError("layer_scale_bwd: operand sizes do not match W [C, K]")
+    if accum and (dW.data_ptr() == dWp.data_ptr() or db.data_ptr() == dbp.data_ptr()):
+        raise ValueError("layer_scale_bwd: accum needs dW / db buffers of their own")
+    check(_lib.load().mh_layer_scale_bwd(_p(W), _p(b), _p(gamma), _p(dWp), _p(dbp), _p(dW), _p(db), _p(dgamma), C, K, int(accum), _stream()),
+          "mh_layer_scale_bwd")
+    return dW, db, dgamma
+
+
 def vit_assemble_fwd(proj, cls, pos, x, B, Np, D):
     _chk(proj, BF16, "proj"), _chk(cls, F32, "cls"), _chk(pos, F32, "pos"), _chk(x, BF16, "x")
     assert proj.numel() >= B * Np * D and cls.numel() >= D and pos.numel() >= (Np + 1) * D and x.numel() >= B * (Np + 1) * D
