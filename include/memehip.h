@@ -102,6 +102,12 @@ int mh_gemm_bf16_grouped(const MhGemmProblem* problems /*host*/, int n_problems,
                          int b_kmajor, mh_stream_t stream);
 /* a split count <= want for which every chunk of ceil(K/ksplit) rounded up to 64 is non-empty (1 when K is short) */
 int mh_gemm_ksplit_for(int K, int want);
+/* Host-only, launches nothing: 1 when mh_gemm_bf16_grouped runs this group on the skinny-M kernel (gemm_skinny_kernel: one wave per
+ * 16 output columns, weights streamed to registers several K tiles ahead), 0 when on the 128x128 tile kernel.  The rule, a pure
+ * function of the arguments (a captured graph replays the same kernel): a_kmajor == 0; every problem has M <= 64, no rows_dev,
+ * ksplit <= 1 and no drop_rng; and the group is narrower than 128 column tiles of 128 in all (sum of ceil(N / 128) < 128: wider
+ * launches fill the chip on the tile kernel).  Both kernels give the same bits; the launcher calls this very function. */
+int mh_gemm_skinny_eligible(const MhGemmProblem* problems /*host*/, int n_problems, int a_kmajor, int b_kmajor);
 /* (The GEMM variants that lost the measurements of rounds 1-4 -- register staging, 4 / 16 waves, 256x128 rings, four-slot ring,
  * double-buffered fragments, K-split waves, persistent workgroups, stream-K, the 128x256 tile, the direct-from-accumulator epilogue
  * -- are not in this library: `make -C csrc LAB=1` builds libmemehip_lab*.so with them behind mh_gemm_set_variant /

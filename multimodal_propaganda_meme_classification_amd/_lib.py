@@ -130,6 +130,7 @@ _PROTOS = {
     "mh_gemm_bf16_grouped": [C.POINTER(MhGemmProblem), c_int, c_int, c_int, c_void_p],
     "mh_gemm_set_trace": [c_void_p],
     "mh_gemm_ksplit_for": [c_int, c_int],
+    "mh_gemm_skinny_eligible": [C.POINTER(MhGemmProblem), c_int, c_int, c_int],
     "mh_layernorm_fwd": [c_void_p] * 7 + [c_int, c_int, c_float, c_void_p],
     "mh_layernorm_bwd": [c_void_p] * 8 + [c_int, c_int, c_int, c_void_p, c_void_p, c_float, C.c_uint32, c_void_p],
     "mh_layernorm_fwd_grouped": [C.POINTER(MhLnFwdJob), c_int, c_int, c_void_p],

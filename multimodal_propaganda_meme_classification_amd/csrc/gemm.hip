@@ -1,6 +1,7 @@
-// Grouped h16 MFMA GEMM with fused epilogue for gfx950 (see include/memehip.h): the ONE kernel the product dispatches
-// (gemm_kernel below: 128x128x64 tile, 8 waves, two workgroups per CU) in its three layouts -- forward (K-contiguous x
-// K-contiguous), dgrad (x K-strided) and wgrad (K-strided x K-strided, f32 output + bias-gradient row sums).
+// Grouped h16 MFMA GEMM with fused epilogue for gfx950 (see include/memehip.h): gemm_kernel below (128x128x64 tile, 8 waves, two
+// workgroups per CU) in its three layouts -- forward (K-contiguous x K-contiguous), dgrad (x K-strided) and wgrad (K-strided x
+// K-strided, f32 output + bias-gradient row sums) -- and gemm_skinny_kernel for forward / dgrad groups whose problems all have
+// M <= 64 rows (one wave per 16 output columns, weights streamed to registers; same bits).  What follows describes gemm_kernel.
 // Operands are staged by LDS-DMA (buffer_load ... lds: rows past the end of an operand read as zero, so M / the wgrad contraction
 // need no padding), swizzle applied to the per-lane SOURCE address (gemm_tile.h):
 //   K-contiguous operand tile  [128 rows][64 k]  (128-B rows): 16-B chunk c of row r lives at chunk c ^ (r & 7)
@@ -64,22 +65,137 @@ MH_DEV void epilogue_prefetch(const MhGemmProblem& P, int m0, int n0, int tid, i
     }
 }
 
-// (Everything the loop needs from the problem descriptor is copied to locals first, and the bias -- a function of the thread's column
-//  only -- is loaded once: the descriptor lives in kernel-argument memory, which the compiler must assume the stores alias, so it
-//  re-read every field after every store (a chain of dependent scalar loads per iteration), and the per-iteration bias load sat behind
-//  the previous iteration's store on the in-order vmcnt counter -- each iteration waited for a store to COMPLETE.)
+// ---- the per-element epilogue arithmetic: ONE pair of functions for gemm_kernel and gemm_skinny_kernel ----------
+// Eight consecutive columns of one output row: v = alpha * acc + bias (epilogue_acc8) -> [dropout, in epilogue_rows] -> aux / activation
+// (with the stored derivative) -> stored-derivative or gelu' multiply -> residual -> f32 (+=) or 16-bit store (epilogue_elem8).  Both
+// kernels call them on the same f32 accumulator values, so a row computed by either is the same bits (tests/test_gemm_skinny_gpu.py);
+// a copy would drift.  (The dropout step stays in epilogue_rows between the two: inside the shared function it cost gemm_kernel's
+// dropout variant 8 spilled VGPRs.)
+// (Everything it needs from the problem descriptor is copied to an EpiCtx of locals first: the descriptor lives in kernel-argument
+//  memory, which the compiler must assume the stores alias, so it re-read every field after every store -- a chain of dependent
+//  scalar loads per iteration.)
+struct EpiCtx {
+    int flags, ldc, N;
+    float alpha;
+    const h16* p_mul;
+    const h16* p_res;
+    h16* p_aux;
+    void* p_c;
+};
+MH_DEV EpiCtx epi_ctx(const MhGemmProblem& P) {
+    EpiCtx E;
+    E.flags = P.flags;
+    E.ldc = P.ldc;
+    E.N = P.N;
+    E.alpha = P.alpha == 0.f ? 1.0f : P.alpha;
+    E.p_mul = (const h16*)P.mul;
+    E.p_res = (const h16*)P.residual;
+    E.p_aux = (h16*)P.aux;
+    E.p_c = P.C;
+    return E;
+}
+// epilogue_acc8: v = alpha * acc + bias for the eight accumulators x0 / x1 (b0 / b1: their bias, zeros without one).
+MH_DEV void epilogue_acc8(const EpiCtx& E, const f32x4 x0, const f32x4 x1, const f32x4 b0, const f32x4 b1, float (&v)[8]) {
+    const float alpha = E.alpha;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v[e] = x0[e] * alpha + b0[e]; v[4 + e] = x1[e] * alpha + b1[e]; }
+}
+// epilogue_elem8: everything behind the dropout site (gemm_kernel's dropout variant applies its mask between the two; the skinny
+// kernel never runs a problem with dropout).  (gm, gn): row and first column in the problem; pf_mul / pf_res: the 16-bit operands
+// fetched ahead (PREF == 1: both; PREF == 2: one slot, the residual's or else the multiplier's; 0: loaded here).
+template <int PREF>
+MH_DEV void epilogue_elem8(const EpiCtx& E, float (&v)[8], int gm, int gn, const i32x4 pf_mul, const i32x4 pf_res) {
+    const int flags = E.flags;
+    const h16* const p_mul = E.p_mul;
+    const h16* const p_res = E.p_res;
+    h16* const p_aux = E.p_aux;
+    const size_t o = (size_t)gm * E.ldc + gn;
+    if ((flags & MH_GEMM_GELU) && (flags & MH_GEMM_DERIV_AUX) && p_aux) {
+        // activation and its derivative from the same exponential: aux receives act'(v), which the dgrad launch multiplies
+        // by as it is (no transcendental math in the backward epilogue)
+        Pack8 u;
+        if (flags & MH_GEMM_QUICK_GELU) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float sg = qgelu_sig(v[e]);
+                u.e[e] = mh_f2bf(sg * (1.0f + 1.702f * v[e] * (1.0f - sg)));
+                v[e] *= sg;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const GeluParts gp = gelu_parts(v[e]);
+                u.e[e] = mh_f2bf(gp.cdf + v[e] * gp.pdf);
+                v[e] *= gp.cdf;
+            }
+        }
+        *(i32x4*)(p_aux + o) = u.v;
+    } else {
+        if (p_aux) {
+            Pack8 u;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) u.e[e] = mh_f2bf(v[e]);
+            *(i32x4*)(p_aux + o) = u.v;
+        }
+        if (flags & MH_GEMM_GELU) {
+            if (flags & MH_GEMM_QUICK_GELU) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = qgelu_f(v[e]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = gelu_f(v[e]);
+            }
+        }
+    }
+    if (p_mul) {
+        Pack8 u;
+        if (PREF == 1) u.v = pf_mul;
+        else if (PREF == 2 && !p_res) u.v = pf_res;
+        else u.v = *(const i32x4*)(p_mul + o);
+        if (flags & MH_GEMM_DERIV_AUX) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] *= mh_bf2f(u.e[e]);
+        } else if (flags & MH_GEMM_QUICK_GELU) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] *= dqgelu_f(mh_bf2f(u.e[e]));
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] *= dgelu_f(mh_bf2f(u.e[e]));
+        }
+    }
+    if (p_res) {
+        Pack8 u;
+        if (PREF) u.v = pf_res;
+        else u.v = *(const i32x4*)(p_res + o);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += mh_bf2f(u.e[e]);
+    }
+    if (flags & MH_GEMM_OUT_F32) {
+        float* c = (float*)E.p_c + o;
+        if (flags & MH_GEMM_ACCUM) {
+            const f32x4 c0 = *(const f32x4*)c, c1 = *(const f32x4*)(c + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { v[e] += c0[e]; v[4 + e] += c1[e]; }
+        }
+        *(f32x4*)c = f32x4{v[0], v[1], v[2], v[3]};
+        *(f32x4*)(c + 4) = f32x4{v[4], v[5], v[6], v[7]};
+    } else {
+        Pack8 u;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) u.e[e] = mh_f2bf(v[e]);
+        *(i32x4*)((h16*)E.p_c + o) = u.v;
+    }
+}
+
+// (the bias -- a function of the thread's column only -- is loaded once: a per-iteration bias load sat behind the previous
+//  iteration's store on the in-order vmcnt counter -- each iteration waited for a store to COMPLETE.)
 template <int TM, int NTHR = TM * 2, bool DROP = true, int PREF = 0>
 MH_DEV void epilogue_rows(const MhGemmProblem& P, const float* cs, int m0, int n0, int tid, int M,
                           const EpiPrefetch<TM, NTHR>* pf = nullptr, const f32x4* bias_pre = nullptr) {
-    const int flags = P.flags;
-    const int ldc = P.ldc, N = P.N;
-    const float alpha = P.alpha == 0.f ? 1.0f : P.alpha;
-    const h16* const p_mul = (const h16*)P.mul;
-    const h16* const p_res = (const h16*)P.residual;
-    h16* const p_aux = (h16*)P.aux;
-    void* const p_c = P.C;
+    const EpiCtx E = epi_ctx(P);
     const int* const drop_rows = P.drop_rows;
     const DropCtx drop = mh_drop_ctx(DROP ? P.drop_rng : nullptr, P.drop_p, P.drop_stream);
+    const int N = E.N;
     constexpr int nthreads = NTHR;
     constexpr int iters = TM * 16 / NTHR;
     static_assert(NTHR % 16 == 0, "a thread keeps its column block across iterations");
@@ -105,94 +221,17 @@ MH_DEV void epilogue_rows(const MhGemmProblem& P, const float* cs, int m0, int n
         const int row = (it * nthreads + tid) >> 4;
         const int gm = m0 + row;
         if (gm >= M || gn >= N) continue;      // ragged M; N need not fill the last 128-column tile (conv layers with 64 filters)
+        const f32x4 x0 = *(const f32x4*)(cs + cs_index(row, cc * 8));
+        const f32x4 x1 = *(const f32x4*)(cs + cs_index(row, cc * 8 + 4));
         float v[8];
-        {
-            const f32x4 x0 = *(const f32x4*)(cs + cs_index(row, cc * 8));
-            const f32x4 x1 = *(const f32x4*)(cs + cs_index(row, cc * 8 + 4));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { v[e] = x0[e] * alpha + b0[e]; v[4 + e] = x1[e] * alpha + b1[e]; }
-        }
-        const size_t o = (size_t)gm * ldc + gn;
+        epilogue_acc8(E, x0, x1, b0, b1, v);
         if (DROP && drop.on) {     // nn.Dropout on the Linear output (BertSelfOutput / BertOutput), before the residual add
             const uint64_t dr = drop_rows ? (uint64_t)drop_rows[gm] : (uint64_t)gm;   // row in the unpacked tensor
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] *= mh_drop_mul(drop, dr * (uint64_t)N + (uint64_t)(gn + e));
         }
-        if ((flags & MH_GEMM_GELU) && (flags & MH_GEMM_DERIV_AUX) && p_aux) {
-            // activation and its derivative from the same exponential: aux receives act'(v), which the dgrad launch multiplies
-            // by as it is (no transcendental math in the backward epilogue)
-            Pack8 u;
-            if (flags & MH_GEMM_QUICK_GELU) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float sg = qgelu_sig(v[e]);
-                    u.e[e] = mh_f2bf(sg * (1.0f + 1.702f * v[e] * (1.0f - sg)));
-                    v[e] *= sg;
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const GeluParts gp = gelu_parts(v[e]);
-                    u.e[e] = mh_f2bf(gp.cdf + v[e] * gp.pdf);
-                    v[e] *= gp.cdf;
-                }
-            }
-            *(i32x4*)(p_aux + o) = u.v;
-        } else {
-            if (p_aux) {
-                Pack8 u;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) u.e[e] = mh_f2bf(v[e]);
-                *(i32x4*)(p_aux + o) = u.v;
-            }
-            if (flags & MH_GEMM_GELU) {
-                if (flags & MH_GEMM_QUICK_GELU) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = qgelu_f(v[e]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = gelu_f(v[e]);
-                }
-            }
-        }
-        if (p_mul) {
-            Pack8 u;
-            if (PREF == 1) u.v = pf->mul[it];
-            else if (PREF == 2 && !p_res) u.v = pf->res[it];
-            else u.v = *(const i32x4*)(p_mul + o);
-            if (flags & MH_GEMM_DERIV_AUX) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] *= mh_bf2f(u.e[e]);
-            } else if (flags & MH_GEMM_QUICK_GELU) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] *= dqgelu_f(mh_bf2f(u.e[e]));
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] *= dgelu_f(mh_bf2f(u.e[e]));
-            }
-        }
-        if (p_res) {
-            Pack8 u;
-            if (PREF) u.v = pf->res[it];
-            else u.v = *(const i32x4*)(p_res + o);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += mh_bf2f(u.e[e]);
-        }
-        if (flags & MH_GEMM_OUT_F32) {
-            float* c = (float*)p_c + o;
-            if (flags & MH_GEMM_ACCUM) {
-                const f32x4 c0 = *(const f32x4*)c, c1 = *(const f32x4*)(c + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { v[e] += c0[e]; v[4 + e] += c1[e]; }
-            }
-            *(f32x4*)c = f32x4{v[0], v[1], v[2], v[3]};
-            *(f32x4*)(c + 4) = f32x4{v[4], v[5], v[6], v[7]};
-        } else {
-            Pack8 u;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) u.e[e] = mh_f2bf(v[e]);
-            *(i32x4*)((h16*)p_c + o) = u.v;
-        }
+        const i32x4 z = i32x4{0, 0, 0, 0};
+        epilogue_elem8<PREF>(E, v, gm, gn, PREF == 1 ? pf->mul[it] : z, PREF ? pf->res[it] : z);
     }
 }
 
@@ -364,6 +403,212 @@ __global__ __launch_bounds__(512, 4) void gemm_kernel(const GemmGroup g) {
     trace_stamp(g, 3);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// gemm_skinny_kernel: grouped launches whose problems ALL have M <= 64 rows (the compact last encoder layer: [B, D] panels; the
+// caption decoder's step), layouts forward (0,0) and dgrad (0,1).  gemm_kernel gives such a launch N / 128 workgroups -- 6 to 48
+// of them on 256 CUs -- each walking its K tiles one memory round trip at a time.  Here ONE WAVE is a workgroup and owns SKN_BN = 16
+// output columns and all the rows: N / 16 workgroups per problem, and the weight fragment of v_mfma_f32_16x16x32 -- 16 contiguous
+// bytes per lane in the forward layout -- goes straight from memory to VGPRs, D K tiles ahead: a register ring the compiler waits on
+// with counted vmcnt (the ring's turns hold no branch, and every load is unconditional; past the last K tile its offset is outside
+// the buffer, which reads as zero without a memory access).  No LDS, no barrier in the forward K loop.  The K-strided weights of the
+// dgrad layout come as 32-byte row pieces through the same ring, are written to a wave-private [64 k][16] LDS image when their tile
+// is due and read back with ds_read_b64_tr_b16 (the addressing of gemm_tile.h: read_frag<1>); LDS operations of one wave execute in
+// order, so no barrier there either.
+// The [M, K] activation panel is read by every workgroup (L2-resident): both 32-deep halves of a row's K tile = one 128-byte line.
+// Same bits as gemm_kernel: the same MFMA with A rows / B columns in the same lanes and the same k in the same fragment element, one
+// f32 accumulator per output element, K tiles ascending with their two halves in order, and epilogue_acc8 / epilogue_elem8 on it.
+// MI = 16-row blocks (2: M <= 32, 4: M <= 64); D = K tiles in flight (skn_depth: 8 / 4, i.e. ~48 / ~40 KB per wave).
+// Widths and depths that were measured against these: profiles/r16_skinny_gemm.txt.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int SKN_NJ = 1;                 // 16-column blocks per wave
+constexpr int SKN_BN = 16 * SKN_NJ;
+constexpr int SKN_MAX_M = 64;
+constexpr int SKN_CS_LD = SKN_BN + 4;     // f32 staging rows + 4 pad: the four 16-lane groups of an accumulator store hit four bank quarters
+constexpr uint32_t SKN_PAST_END = 0x80000000u;      // a byte offset beyond every buffer this kernel binds (operands are < 2 GiB)
+constexpr int skn_depth(int mi) { return mi <= 2 ? 8 : 4; }
+
+template <int MI>
+struct SknFrag {
+    i32x4 a[MI][2], b[SKN_NJ * 2];      // forward: b[j * 2 + kk]; dgrad: piece p = k rows p * (32 / NJ) ..
+};
+
+template <int LB, int MI>
+__global__ __launch_bounds__(64) void gemm_skinny_kernel(const GemmGroup g) {
+    constexpr int D = skn_depth(MI), NJ = SKN_NJ, CPR = 2 * NJ;      // CPR: 16-byte chunks per row of BN columns
+    constexpr int CS_FLOATS = MI * 16 * SKN_CS_LD, IMG_FLOATS = BK * SKN_BN * 2 / 4;      // dgrad: the [64 k][BN] weight image first
+    __shared__ __attribute__((aligned(16))) float cs[CS_FLOATS > IMG_FLOATS ? CS_FLOATS : IMG_FLOATS];
+    int t;
+    {      // XCD-aware as in gemm_kernel: each XCD gets a contiguous run of column tiles (neighbours share weight lines in its L2)
+        const int nwg = g.total_tiles, b = blockIdx.x;
+        const int q = nwg >> 3, r = nwg & 7, x = b & 7, j = b >> 3;
+        if (j >= q + (x < r ? 1 : 0)) return;
+        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
+    }
+    int pi = 0;
+#pragma unroll
+    for (int i = 1; i < MH_GEMM_MAX_GROUP; ++i)
+        if (i < g.n && t >= g.d[i].tile_start) pi = i;
+    const MhGemmProblem& P = g.d[pi].p;
+    const int n0 = (t - g.d[pi].tile_start) * SKN_BN;
+    const int M = P.M, N = P.N, K = P.K, lda = P.lda, ldb = P.ldb;
+    const int lane = threadIdx.x, r16 = lane & 15, g4 = lane >> 4;
+    const __amdgpu_buffer_rsrc_t ra = mh_rsrc(P.A, (uint32_t)((M - 1) * lda + K) * 2u);
+    const __amdgpu_buffer_rsrc_t rb = mh_rsrc(P.B, LB == 0 ? (uint32_t)((N - 1) * ldb + K) * 2u : (uint32_t)((K - 1) * ldb + N) * 2u);
+    const int nk = K / BK;
+
+    // per-lane byte offsets of K tile 0.  A block i: row i * 16 + r16, k = kk * 32 + g4 * 8 (rows >= M lie past the buffer: zeros).
+    // B forward: column n0 + j * 16 + r16 at the same k; B dgrad: piece p = k rows p * (64 / CPR) + lane / CPR, columns
+    // n0 + (lane % CPR) * 8 .. + 7 (columns >= N: zeros or a neighbour's values, feeding only output columns that are never stored).
+    const uint32_t a_off = (uint32_t)(r16 * lda + g4 * 8) * 2u, a_blk = (uint32_t)(16 * lda) * 2u;
+    const uint32_t b_off = LB == 0 ? (uint32_t)((n0 + r16) * ldb + g4 * 8) * 2u : (uint32_t)((lane / CPR) * ldb + n0 + (lane % CPR) * 8) * 2u;
+    const uint32_t b_blk = (uint32_t)(16 * ldb) * 2u;                 // forward: the next 16 columns
+    const uint32_t b_piece = (uint32_t)((64 / CPR) * ldb) * 2u;       // dgrad: the next 64 / CPR k rows
+    const uint32_t b_tile = LB == 0 ? (uint32_t)BK * 2u : (uint32_t)(BK * ldb) * 2u;
+    auto load = [&](SknFrag<MI>& f, int kt) {
+        const bool in = kt < nk;
+        const uint32_t ao = in ? a_off + (uint32_t)kt * (BK * 2u) : SKN_PAST_END;
+        const uint32_t bo = in ? b_off + (uint32_t)kt * b_tile : SKN_PAST_END;
+#pragma unroll
+        for (int p = 0; p < CPR; ++p) f.b[p] = mh_buf_load16(rb, LB == 0 ? bo + (p >> 1) * b_blk + (p & 1) * 64u : bo + p * b_piece);
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) f.a[i][h] = mh_buf_load16(ra, ao + i * a_blk + h * 64u);
+    };
+
+    f32x4 acc[MI][NJ];
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    SknFrag<MI> ring[D];
+#pragma unroll
+    for (int s = 0; s < D; ++s) load(ring[s], s);
+    char* const wimg = (char*)cs;
+    auto consume = [&](const SknFrag<MI>& f) {
+        Pack8 fb[NJ][2];
+        if (LB == 0) {
+#pragma unroll
+            for (int p = 0; p < CPR; ++p) fb[p >> 1][p & 1].v = f.b[p];
+        } else {
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int p = 0; p < CPR; ++p) *(i32x4*)(wimg + p * 1024 + lane * 16) = f.b[p];      // rows of BN * 2 bytes, linear
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) {
+                    const int k0 = kk * 32 + g4 * 8 + (r16 >> 2);      // lanes 4q..4q+3 supply k row k0 (and k0 + 4), 8 bytes each
+                    const int at = k0 * (SKN_BN * 2) + j * 32 + (r16 & 3) * 8;
+                    union {
+                        struct { s16x4 lo, hi; } s;
+                        h16x8 h;
+                    } cv;
+                    cv.s.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, wimg + at));
+                    cv.s.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, wimg + at + 4 * (SKN_BN * 2)));
+                    fb[j][kk].h = cv.h;
+                }
+            asm volatile("" ::: "memory");
+        }
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int i = 0; i < MI; ++i) {
+                Pack8 fa;
+                fa.v = f.a[i][kk];
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) acc[i][j] = MH_MFMA_16x16x32(fa.h, fb[j][kk].h, acc[i][j], 0, 0, 0);
+            }
+    };
+    // whole turns of the ring: no branch between the loads, so every wait is a counted one ((D - 1) tiles stay in flight) ...
+    int kt0 = 0;
+    for (; kt0 + D <= nk; kt0 += D) {
+#pragma unroll
+        for (int s = 0; s < D; ++s) {
+            consume(ring[s]);
+            load(ring[s], kt0 + s + D);
+        }
+    }
+    // ... and the last nk % D tiles, already in the ring
+    const int rem = nk - kt0;
+#pragma unroll
+    for (int s = 0; s < D - 1; ++s)
+        if (s < rem) consume(ring[s]);      // (uniform)
+
+    // ---- epilogue: accumulators -> wave-private f32 image -> 8 columns of a row per lane -> the shared epilogue arithmetic ----
+    const EpiCtx E = epi_ctx(P);
+    constexpr int iters = MI * 16 * CPR / 64, RPI = 64 / CPR;      // rows per iteration
+    const int cc = lane % CPR, gn = n0 + cc * 8;
+    f32x4 b0 = f32x4{0.f, 0.f, 0.f, 0.f}, b1 = b0;
+    if (P.bias && gn < N) {
+        b0 = *(const f32x4*)(P.bias + gn);
+        b1 = *(const f32x4*)(P.bias + gn + 4);
+    }
+    i32x4 pf_mul[iters], pf_res[iters];
+#pragma unroll
+    for (int it = 0; it < iters; ++it) {      // (clamped: rows past M / columns past N are never stored)
+        const size_t o = (size_t)min(it * RPI + lane / CPR, M - 1) * E.ldc + min(gn, N - 8);
+        pf_mul[it] = pf_res[it] = i32x4{0, 0, 0, 0};
+        if (E.p_res) pf_res[it] = *(const i32x4*)(E.p_res + o);
+        if (E.p_mul) pf_mul[it] = *(const i32x4*)(E.p_mul + o);
+    }
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) cs[(i * 16 + g4 * 4 + r) * SKN_CS_LD + j * 16 + r16] = acc[i][j][r];
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int it = 0; it < iters; ++it) {
+        const int gm = it * RPI + lane / CPR;
+        if (gm >= M || gn >= N) continue;
+        const f32x4 x0 = *(const f32x4*)(cs + gm * SKN_CS_LD + cc * 8);
+        const f32x4 x1 = *(const f32x4*)(cs + gm * SKN_CS_LD + cc * 8 + 4);
+        float v[8];
+        epilogue_acc8(E, x0, x1, b0, b1, v);
+        epilogue_elem8<1>(E, v, gm, gn, pf_mul[it], pf_res[it]);
+    }
+}
+
+// The dispatch rule of mh_gemm_bf16_grouped, from the problem list alone (mh_gemm_skinny_eligible exports it)
+// Width bound: a launch that gives gemm_kernel 128 or more column tiles (half the CUs and up) streams its weights as fast there, and
+// every 16-column wave here re-reads the whole activation panel: at M = 64, K = 768 the skinny kernel wins x2.1 at N = 4096, x1.2 at
+// 12288, ties at 16384 (128 tiles) and loses x0.75 at 24576 and x0.67 on the decoder's logits, N = 30528 (profiles/r16_skinny_gemm.txt).
+constexpr int SKN_WIDE_TILES = 128;
+bool skinny_eligible(const MhGemmProblem* problems, int n, int a_kmajor, int b_kmajor) {
+    if (!problems || n < 1 || n > MH_GEMM_MAX_GROUP || a_kmajor) return false;
+    int wide_tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        const MhGemmProblem& p = problems[i];
+        if (p.M < 1 || p.M > SKN_MAX_M || p.rows_dev || p.ksplit > 1 || p.drop_rng) return false;
+        wide_tiles += (p.N + BN - 1) / BN;
+    }
+    return wide_tiles < SKN_WIDE_TILES;
+}
+
+template <int LB, int MI>
+int launch_skinny2(const GemmGroup& g, hipStream_t s) {
+    hipLaunchKernelGGL((gemm_skinny_kernel<LB, MI>), dim3(g.total_tiles), dim3(64), 0, s, g);
+    return mh_launch_status();
+}
+// (the problems were validated by the caller)
+int launch_skinny(GemmGroup& g, int b_kmajor, hipStream_t s) {
+    int total = 0, max_m = 0;
+    for (int i = 0; i < g.n; ++i) {
+        g.d[i].tiles_n = (g.d[i].p.N + SKN_BN - 1) / SKN_BN;
+        g.d[i].tiles_m = 1;
+        g.d[i].tile_start = total;
+        total += g.d[i].tiles_n;
+        max_m = g.d[i].p.M > max_m ? g.d[i].p.M : max_m;
+    }
+    g.total_tiles = total;
+    if (max_m <= 32) return b_kmajor ? launch_skinny2<1, 2>(g, s) : launch_skinny2<0, 2>(g, s);
+    return b_kmajor ? launch_skinny2<1, 4>(g, s) : launch_skinny2<0, 4>(g, s);
+}
+
 unsigned long long* g_trace = nullptr;      // mh_gemm_set_trace
 
 #ifdef MH_LAB
@@ -445,6 +690,7 @@ extern "C" int mh_gemm_bf16_grouped(const MhGemmProblem* problems, int n_problem
     for (int i = 0; i < n_problems; ++i)
         if (problems[i].rows_dev && !g.rows_any) g.rows_any = problems[i].rows_dev;
     hipStream_t s = (hipStream_t)stream;
+    if (skinny_eligible(problems, n_problems, a_kmajor, b_kmajor)) return launch_skinny(g, b_kmajor, s);
     if (!a_kmajor && !b_kmajor) return launch<0, 0>(g, s);
     if (!a_kmajor && b_kmajor) return launch<0, 1>(g, s);
     if (a_kmajor && b_kmajor) return launch<1, 1>(g, s);
@@ -452,6 +698,10 @@ extern "C" int mh_gemm_bf16_grouped(const MhGemmProblem* problems, int n_problem
 }
 
 extern "C" int mh_gemm_ksplit_for(int K, int want) { return ksplit_fit(K, want); }
+
+extern "C" int mh_gemm_skinny_eligible(const MhGemmProblem* problems, int n_problems, int a_kmajor, int b_kmajor) {
+    return skinny_eligible(problems, n_problems, a_kmajor, b_kmajor) ? 1 : 0;
+}
 
 // profiling knob: with a device buffer of 4 x 8 bytes per workgroup of the largest launch, the kernel records 100-MHz stamps per
 // workgroup {entry, first K stage landed, main loop done, epilogue stores issued}; NULL switches it off (tools/gemm_timeline.py)
