@@ -108,11 +108,10 @@ int mh_gemm_ksplit_for(int K, int want);
  * ksplit <= 1 and no drop_rng; and the group is narrower than 128 column tiles of 128 in all (sum of ceil(N / 128) < 128: wider
  * launches fill the chip on the tile kernel).  Both kernels give the same bits; the launcher calls this very function. */
 int mh_gemm_skinny_eligible(const MhGemmProblem* problems /*host*/, int n_problems, int a_kmajor, int b_kmajor);
-/* (The GEMM variants that lost the measurements of rounds 1-4 -- register staging, 4 / 16 waves, 256x128 rings, four-slot ring,
- * double-buffered fragments, K-split waves, persistent workgroups, stream-K, the 128x256 tile, the direct-from-accumulator epilogue
- * -- are not in this library: `make -C csrc LAB=1` builds libmemehip_lab*.so with them behind mh_gemm_set_variant /
- * mh_gemm_set_streamk, declared in csrc/lab/memehip_lab.h, for tools/ only.) */
-/* profiling knob: device buffer of 4 x uint64 per workgroup of the largest launch; the default kernel records 100-MHz stamps per
+/* (These two kernels are the library's only GEMMs.  What was measured against them and lost -- register staging, 4 / 16 waves,
+ * 256x128 rings, four-slot ring, double-buffered fragments, K-split waves, persistent workgroups, stream-K, the 128x256 tile, the
+ * direct-from-accumulator epilogue -- is recorded with its numbers in DESIGN.md section 5 and tools/lab/RESULTS.md.) */
+/* profiling knob: device buffer of 4 x uint64 per workgroup of the largest launch; the 128x128 tile kernel records 100-MHz stamps per
  * workgroup {entry, first K stage landed, main loop done, epilogue stores issued}; NULL = off (tools/gemm_timeline.py) */
 int mh_gemm_set_trace(void* device_buffer);
 

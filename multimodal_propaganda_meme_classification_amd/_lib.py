@@ -238,9 +238,6 @@ _PROTOS = {
 }
 _RESTYPES = {"mh_version": C.c_char_p, "mh_status_str": C.c_char_p, "mh_bn2d_workspace_elems": c_int64,
              "mh_dwconv_wgrad_workspace_elems": c_int64}
-# extra entry points of the LAB build (csrc/lab/memehip_lab.h; `make LAB=1`), bound only when the loaded library has them
-_LAB_PROTOS = {"mh_gemm_set_variant": ([c_int], c_int), "mh_gemm_streamk_workspace_bytes": ([], c_int64),
-               "mh_gemm_set_streamk": ([c_void_p, c_int], c_int)}
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -273,10 +270,6 @@ def load(kind: str = "bf16") -> C.CDLL:
         fn = getattr(lib, name)          # AttributeError here = header/library drift
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, c_int)
-    for name, (argtypes, restype) in _LAB_PROTOS.items():      # tools/ with MEMEHIP_LIB=libmemehip_lab*.so
-        if hasattr(lib, name):
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = argtypes, restype
     _libs[kind] = lib
     return lib
 

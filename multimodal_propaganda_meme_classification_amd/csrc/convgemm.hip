@@ -16,7 +16,6 @@
 // will read) -> part[2][Cout][tiles_m]: train-mode BatchNorm2d needs no statistics pass over the activation.
 #include "common.h"
 #include "gemm_tile.h"
-#include <stdlib.h>
 
 namespace {
 using namespace mh_tile;
@@ -221,7 +220,7 @@ MH_DEV void conv_tile(const ConvGroup& grp, const ConvPair& pr) {
         char* lb = st + BM * BK * 2;
         const int k0 = kbeg + kt * BK;
         if (MODE == MODE_WGRAD) {
-            dma_tile<1, 2>(rr, a.ldreg, m0, k0, wave, lane, la);          // dY [pixel][cout], K-strided
+            dma_tile<1>(rr, a.ldreg, m0, k0, wave, lane, la);          // dY [pixel][cout], K-strided
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int piece = wave * 2 + i;
@@ -241,7 +240,7 @@ MH_DEV void conv_tile(const ConvGroup& grp, const ConvPair& pr) {
         }
         if (PAIR && kt >= nk1) {      // second segment (wave-uniform): rows co2 = c0.. of the 1x1 weight, the same pixel's channels c0.. of dy2
             const int c0 = (kt - nk1) * BK;
-            dma_tile<1, 2>(rr2, pr.ldreg, n0, c0, wave, lane, lb);
+            dma_tile<1>(rr2, pr.ldreg, n0, c0, wave, lane, lb);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs2, LDS_PTR(void, la + (wave * 2 + i) * 1024), 16, p_off2[i] + (uint32_t)c0 * 2u, 0, 0, 0);
@@ -249,12 +248,12 @@ MH_DEV void conv_tile(const ConvGroup& grp, const ConvPair& pr) {
         }
         // regular B first (it needs the tap BEFORE the walk advances)
         if (MODE == MODE_FWD) {
-            dma_tile<0, 2>(rr, a.ldreg, n0, k0, wave, lane, lb);          // Wk [cout][(tap,ci)], K-contiguous
+            dma_tile<0>(rr, a.ldreg, n0, k0, wave, lane, lb);          // Wk [cout][(tap,ci)], K-contiguous
         } else {
             // the weight tap behind window tap (kh', kw'): the flipped tap, or (parity class of a strided convolution) every second one
             const int wtap = a.wstep > 1 ? (a.wkh0 + a.wstep * (a.KH - 1 - u_kh)) * a.wkwfull + a.wkw0 + a.wstep * (a.KW - 1 - u_kw)
                                          : taps - 1 - (u_kh * a.KW + u_kw);
-            dma_tile<1, 2>(rr, a.ldreg, wtap * a.Cw + n0, u_c0, wave, lane, lb);   // rows co = u_c0.., columns = the tap's ci
+            dma_tile<1>(rr, a.ldreg, wtap * a.Cw + n0, u_c0, wave, lane, lb);   // rows co = u_c0.., columns = the tap's ci
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -657,7 +656,7 @@ extern "C" int mh_conv_fwd(const void* x, const void* wk, void* y, float* bn_par
     a.ldreg = g->ldk; a.ldc = g->Cout; a.Cw = g->C;
     a.tiles_m = (a.M + BM - 1) / BM; a.tiles_n = (a.N + BN - 1) / BN;
     a.total_tiles = a.tiles_m * a.tiles_n;
-    a.group_m = group_m_setting();
+    a.group_m = GROUP_M;
     a.kchunk = 0; a.nsplit = 1;
     a.alpha = 1.f;
     a.inv_wo = 1.0f / (float)Wo; a.inv_howo = 1.0f / (float)(Ho * Wo);
@@ -706,7 +705,7 @@ int parity_group(const void* dy, const void* wk, void* dx, const MhConvGeom* g, 
             a.ldreg = g->ldk; a.ldc = g->C; a.Cw = g->C;
             a.tiles_m = (a.M + BM - 1) / BM; a.tiles_n = (a.N + BN - 1) / BN;
             a.total_tiles = a.tiles_m * a.tiles_n;
-            a.group_m = group_m_setting();
+            a.group_m = GROUP_M;
             a.kchunk = 0; a.nsplit = 1; a.alpha = 1.f;
             a.inv_wo = 1.0f / (float)a.Wo; a.inv_howo = 1.0f / (float)(a.Ho * a.Wo);
             a.wstep = 2; a.wkh0 = kh0; a.wkw0 = kw0; a.wkwfull = g->KW;
@@ -760,7 +759,7 @@ extern "C" int mh_conv_dgrad(const void* dy, const void* wk, void* dx, float* wo
     a.ldreg = g->ldk; a.ldc = g->C; a.Cw = g->C;
     a.tiles_m = (a.M + BM - 1) / BM; a.tiles_n = (a.N + BN - 1) / BN;
     a.total_tiles = a.tiles_m * a.tiles_n;
-    a.group_m = group_m_setting();
+    a.group_m = GROUP_M;
     a.kchunk = 0; a.nsplit = 1;
     a.alpha = 1.f;
     a.inv_wo = 1.0f / (float)a.Wo; a.inv_howo = 1.0f / (float)(a.Ho * a.Wo);
@@ -847,7 +846,7 @@ int wgrad_args(const void* dy, const void* x, float* slabs, int ksplit, float al
     if ((a.K + kc - 1) / kc != ksplit) return MH_ESHAPE;          // an empty split: use mh_gemm_ksplit_for(B*Ho*Wo, want)
     a.kchunk = kc; a.nsplit = ksplit;
     a.total_tiles = a.tiles_m * a.tiles_n * ksplit;
-    a.group_m = group_m_setting();
+    a.group_m = GROUP_M;
     a.alpha = alpha == 0.f ? 1.f : alpha;
     a.inv_wo = 1.0f / (float)Wo; a.inv_howo = 1.0f / (float)(Ho * Wo);
     return MH_OK;

@@ -10,14 +10,11 @@
 //                                                              -> ds_read_b64_tr_b16 fragments conflict-free.
 // Epilogue: accumulators -> LDS as f32 [128][128] -> 16-B coalesced global stores with bias / GELU / gelu' / residual in f32.
 // blockIdx -> tile: XCD-aware (blocks b, b+8 share an L2): each XCD gets a contiguous run of tiles, blocked for L2 (tile_coords).
-// The variants that lost the A/B measurements of rounds 1-3 live in lab/gemm_lab.inc (`make LAB=1`), not in the product library.
 #include "common.h"
 #include "gemm_tile.h"
-#include <stdlib.h>
 
 namespace {
 using namespace mh_tile;
-
 
 struct DevProblem {
     MhGemmProblem p;
@@ -31,8 +28,6 @@ struct GemmGroup {
     int total_tiles;
     int group_m;      // L2 blocking of the tile order: GROUP_M row panels are swept column by column (0/1: n-fastest)
     int pad_;
-    float* sk_partial;           // stream-K (gemm_sk_kernel): one accumulator image (512 threads x 32 f32) per workgroup
-    unsigned* sk_flags;          //   [0..grid): "workgroup b's partial is stored"; [grid]: spin time-out marker
     unsigned long long* trace;   // debug (mh_gemm_set_trace): per workgroup 4 x 100-MHz stamps {entry, first stage landed, main loop done, stores issued}
     const int* rows_any;         // one of the problems' rows_dev pointers (NULL when no problem has one): a valid address for the unconditional loads of the live counts
     DevProblem d[MH_GEMM_MAX_GROUP];
@@ -45,16 +40,15 @@ MH_DEV void trace_stamp(const GemmGroup& g, int k) {
 // The 16-bit epilogue operands (residual, gelu' pre-activation) are fetched BEFORE the accumulators go through
 // LDS (epilogue_prefetch), so their HBM latency hides behind the LDS transpose + barrier instead of stalling
 // every store iteration.
-template <int TM, int NTHR>
+constexpr int EPI_THREADS = NW * 64;                  // the whole workgroup stores the BM x BN tile, 16 threads to a row
+constexpr int EPI_ITERS = BM * 16 / EPI_THREADS;
 struct EpiPrefetch {
-    static constexpr int iters = TM * 16 / NTHR;
-    i32x4 res[iters], mul[iters];
+    i32x4 res[EPI_ITERS], mul[EPI_ITERS];
 };
-template <int TM, int NTHR>
-MH_DEV void epilogue_prefetch(const MhGemmProblem& P, int m0, int n0, int tid, int M, EpiPrefetch<TM, NTHR>& pf) {
+MH_DEV void epilogue_prefetch(const MhGemmProblem& P, int m0, int n0, int tid, int M, EpiPrefetch& pf) {
 #pragma unroll
-    for (int it = 0; it < EpiPrefetch<TM, NTHR>::iters; ++it) {
-        const int q = it * NTHR + tid;
+    for (int it = 0; it < EPI_ITERS; ++it) {
+        const int q = it * EPI_THREADS + tid;
         const int row = q >> 4, cc = q & 15;
         const int gm = min(m0 + row, M - 1), gn = min(n0 + cc * 8, P.N - 8);   // clamped: rows past M / columns past N are never stored
         const size_t o = (size_t)gm * P.ldc + gn;
@@ -102,8 +96,7 @@ MH_DEV void epilogue_acc8(const EpiCtx& E, const f32x4 x0, const f32x4 x1, const
 }
 // epilogue_elem8: everything behind the dropout site (gemm_kernel's dropout variant applies its mask between the two; the skinny
 // kernel never runs a problem with dropout).  (gm, gn): row and first column in the problem; pf_mul / pf_res: the 16-bit operands
-// fetched ahead (PREF == 1: both; PREF == 2: one slot, the residual's or else the multiplier's; 0: loaded here).
-template <int PREF>
+// fetched ahead by the caller (zeros where the problem has none).
 MH_DEV void epilogue_elem8(const EpiCtx& E, float (&v)[8], int gm, int gn, const i32x4 pf_mul, const i32x4 pf_res) {
     const int flags = E.flags;
     const h16* const p_mul = E.p_mul;
@@ -149,9 +142,7 @@ MH_DEV void epilogue_elem8(const EpiCtx& E, float (&v)[8], int gm, int gn, const
     }
     if (p_mul) {
         Pack8 u;
-        if (PREF == 1) u.v = pf_mul;
-        else if (PREF == 2 && !p_res) u.v = pf_res;
-        else u.v = *(const i32x4*)(p_mul + o);
+        u.v = pf_mul;
         if (flags & MH_GEMM_DERIV_AUX) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] *= mh_bf2f(u.e[e]);
@@ -165,8 +156,7 @@ MH_DEV void epilogue_elem8(const EpiCtx& E, float (&v)[8], int gm, int gn, const
     }
     if (p_res) {
         Pack8 u;
-        if (PREF) u.v = pf_res;
-        else u.v = *(const i32x4*)(p_res + o);
+        u.v = pf_res;
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += mh_bf2f(u.e[e]);
     }
@@ -189,22 +179,16 @@ MH_DEV void epilogue_elem8(const EpiCtx& E, float (&v)[8], int gm, int gn, const
 
 // (the bias -- a function of the thread's column only -- is loaded once: a per-iteration bias load sat behind the previous
 //  iteration's store on the in-order vmcnt counter -- each iteration waited for a store to COMPLETE.)
-template <int TM, int NTHR = TM * 2, bool DROP = true, int PREF = 0>
-MH_DEV void epilogue_rows(const MhGemmProblem& P, const float* cs, int m0, int n0, int tid, int M,
-                          const EpiPrefetch<TM, NTHR>* pf = nullptr, const f32x4* bias_pre = nullptr) {
+template <bool DROP>
+MH_DEV void epilogue_rows(const MhGemmProblem& P, const float* cs, int m0, int n0, int tid, int M, const EpiPrefetch& pf) {
     const EpiCtx E = epi_ctx(P);
     const int* const drop_rows = P.drop_rows;
     const DropCtx drop = mh_drop_ctx(DROP ? P.drop_rng : nullptr, P.drop_p, P.drop_stream);
     const int N = E.N;
-    constexpr int nthreads = NTHR;
-    constexpr int iters = TM * 16 / NTHR;
-    static_assert(NTHR % 16 == 0, "a thread keeps its column block across iterations");
+    static_assert(EPI_THREADS % 16 == 0, "a thread keeps its column block across iterations");
     const int cc = tid & 15, gn = n0 + cc * 8;
     f32x4 b0 = f32x4{0.f, 0.f, 0.f, 0.f}, b1 = b0;
-    if (bias_pre) {
-        b0 = bias_pre[0];
-        b1 = bias_pre[1];
-    } else if (P.bias && gn < N) {
+    if (P.bias && gn < N) {
         b0 = *(const f32x4*)(P.bias + gn);
         b1 = *(const f32x4*)(P.bias + gn + 4);
     }
@@ -217,8 +201,8 @@ MH_DEV void epilogue_rows(const MhGemmProblem& P, const float* cs, int m0, int n
     // after; round 4, second session).
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0), expcnt / lgkmcnt untouched
 #pragma unroll
-    for (int it = 0; it < iters; ++it) {
-        const int row = (it * nthreads + tid) >> 4;
+    for (int it = 0; it < EPI_ITERS; ++it) {
+        const int row = (it * EPI_THREADS + tid) >> 4;
         const int gm = m0 + row;
         if (gm >= M || gn >= N) continue;      // ragged M; N need not fill the last 128-column tile (conv layers with 64 filters)
         const f32x4 x0 = *(const f32x4*)(cs + cs_index(row, cc * 8));
@@ -230,14 +214,12 @@ MH_DEV void epilogue_rows(const MhGemmProblem& P, const float* cs, int m0, int n
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] *= mh_drop_mul(drop, dr * (uint64_t)N + (uint64_t)(gn + e));
         }
-        const i32x4 z = i32x4{0, 0, 0, 0};
-        epilogue_elem8<PREF>(E, v, gm, gn, PREF == 1 ? pf->mul[it] : z, PREF ? pf->res[it] : z);
+        epilogue_elem8(E, v, gm, gn, pf.mul[it], pf.res[it]);
     }
 }
 
-
 // ---------------------------------------------------------------------------------------------------------------------
-// gemm_kernel: the kernel every grouped launch of the product runs.  128x128x64 tile per 512-thread workgroup: eight waves as
+// gemm_kernel: the kernel of every grouped launch that gemm_skinny_kernel does not take.  128x128x64 tile per 512-thread workgroup: eight waves as
 // 2 (M) x 4 (N), 64x32 each = 4x2 tiles of v_mfma_f32_16x16x32 (4 waves per SIMD cover barrier + LDS latency best on this path's
 // shapes; 4 waves of 64x64 and 16 of 32x32 measured slower), two LDS-DMA stages, ONE barrier per K step, the next stage issued
 // before the MFMAs of the current one.  Epilogue: accumulators -> f32 staging tile in LDS (swizzled: cs_index) -> bias / GELU /
@@ -247,12 +229,12 @@ MH_DEV void epilogue_rows(const MhGemmProblem& P, const float* cs, int m0, int n
 // (~1 280: 96 KB of fragment reads + 32 KB of LDS-DMA writes per workgroup) and the L2 -> LDS stream (1 024) are within 25 % of
 // each other, and every launch pays ~4 us of fill + epilogue per round of 512 workgroups -- a burst of 16 MB of loads / stores
 // that all workgroups issue at the same moment.
-// Round 4 built the alternatives the last review asked for and measured them in the step against this kernel on one box
-// (tools/lab/RESULTS.md (r4c) .. exp_r4g.sh; profiles/r04_gemm_shapes.csv; all in lab/gemm_lab.inc now): the epilogue stored STRAIGHT from
+// Alternatives measured in the step against this kernel on one box (tools/lab/RESULTS.md (r4c) .. exp_r4g.sh;
+// profiles/r04_gemm_shapes.csv; their source is in the history): the epilogue stored STRAIGHT from
 // transposed accumulators (weights in the MFMA's A slot, v_permlane16_swap pairing, no staging tile) is 1-4 us faster on the
 // store-only launches standalone and 3-5 us slower where a 16-bit operand is read back (64-byte row segments per wave instead of
 // 256-byte ones) -- in the step: 9.75-9.84 ms against 9.66-9.72; the same kernel with 4 x 2 waves of 32x64 wins the weight-gradient
-// launches by 5 % standalone and nothing in the step; the 128x256x32 tile loses 0.25 ms per step.  This kernel stays.
+// launches by 5 % standalone and nothing in the step; the 128x256x32 tile loses 0.25 ms per step.
 // ---------------------------------------------------------------------------------------------------------------------
 template <int LA, int LB, bool DROP>
 __global__ __launch_bounds__(512, 4) void gemm_kernel(const GemmGroup g) {
@@ -362,8 +344,8 @@ __global__ __launch_bounds__(512, 4) void gemm_kernel(const GemmGroup g) {
     k_loop<LA, LB>(
         acc, smem, nk, wave, lane,
         [&](int kt, char* st) {
-            dma_tile<LA, 16 / NW>(ra, P.lda, m0, kbeg + kt * BK, wave, lane, st);
-            dma_tile<LB, 16 / NW>(rb, P.ldb, n0, kbeg + kt * BK, wave, lane, st + BM * BK * 2);
+            dma_tile<LA>(ra, P.lda, m0, kbeg + kt * BK, wave, lane, st);
+            dma_tile<LB>(rb, P.ldb, n0, kbeg + kt * BK, wave, lane, st + BM * BK * 2);
         },
         [&](const h16x8 (&fa)[NI]) {
             if (do_rowsum) {
@@ -395,11 +377,11 @@ __global__ __launch_bounds__(512, 4) void gemm_kernel(const GemmGroup g) {
     }
     // (issuing these loads under the last K tile's MFMAs instead was measured 20 % slower: the extra live registers
     //  across the main loop cost more than the remaining exposed latency)
-    EpiPrefetch<BM, NW * 64> pf;
-    epilogue_prefetch<BM, NW * 64>(P, m0, n0, tid, M, pf);
+    EpiPrefetch pf;
+    epilogue_prefetch(P, m0, n0, tid, M, pf);
     stage_acc(cs, acc, wave, lane);
     __syncthreads();
-    epilogue_rows<BM, NW * 64, DROP, 1>(P, cs, m0, n0, tid, M, &pf);
+    epilogue_rows<DROP>(P, cs, m0, n0, tid, M, pf);
     trace_stamp(g, 3);
 }
 
@@ -569,7 +551,7 @@ __global__ __launch_bounds__(64) void gemm_skinny_kernel(const GemmGroup g) {
         const f32x4 x1 = *(const f32x4*)(cs + gm * SKN_CS_LD + cc * 8 + 4);
         float v[8];
         epilogue_acc8(E, x0, x1, b0, b1, v);
-        epilogue_elem8<1>(E, v, gm, gn, pf_mul[it], pf_res[it]);
+        epilogue_elem8(E, v, gm, gn, pf_mul[it], pf_res[it]);
     }
 }
 
@@ -611,10 +593,6 @@ int launch_skinny(GemmGroup& g, int b_kmajor, hipStream_t s) {
 
 unsigned long long* g_trace = nullptr;      // mh_gemm_set_trace
 
-#ifdef MH_LAB
-#include "lab/gemm_lab.inc"
-#endif
-
 template <int LA, int LB, bool DROP>
 int launch2(const GemmGroup& g, hipStream_t s) {
     static bool attr_set = false;
@@ -627,9 +605,11 @@ int launch2(const GemmGroup& g, hipStream_t s) {
 }
 template <int LA, int LB>
 int launch(const GemmGroup& g, hipStream_t s) {
-    bool any_drop = false;     // the dropout epilogue is compiled only into the variant that needs it
-    for (int i = 0; i < g.n; ++i) any_drop |= (g.d[i].p.drop_rng != nullptr && g.d[i].p.drop_p > 0.f);
-    if (LA == 0 && LB == 0 && any_drop) return launch2<LA, LB, true>(g, s);
+    if constexpr (LA == 0 && LB == 0) {     // the dropout epilogue is compiled only for the layout that runs it (forward), in a kernel of its own
+        bool any_drop = false;
+        for (int i = 0; i < g.n; ++i) any_drop |= (g.d[i].p.drop_rng != nullptr && g.d[i].p.drop_p > 0.f);
+        if (any_drop) return launch2<LA, LB, true>(g, s);
+    }
     return launch2<LA, LB, false>(g, s);
 }
 
@@ -638,17 +618,6 @@ int launch(const GemmGroup& g, hipStream_t s) {
 extern "C" int mh_gemm_bf16_grouped(const MhGemmProblem* problems, int n_problems, int a_kmajor,
                                     int b_kmajor, mh_stream_t stream) {
     if (!problems || n_problems < 1 || n_problems > MH_GEMM_MAX_GROUP) return MH_EINVAL;
-#ifdef MH_LAB
-    if (g_variant < 0) {
-        const char* e = getenv("MEMEHIP_GEMM_VARIANT");
-        g_variant = e ? atoi(e) : -2;
-        if (g_variant < 0 || g_variant > 13) g_variant = -2;
-    }
-    if (g_variant >= 0) {      // -2: the product's kernel
-        const int rc = lab_gemm_grouped(problems, n_problems, a_kmajor, b_kmajor, stream);
-        if (rc != LAB_NOT_MINE) return rc;
-    }
-#endif
     GemmGroup g;
     g.n = n_problems;
     int total = 0;
@@ -681,11 +650,9 @@ extern "C" int mh_gemm_bf16_grouped(const MhGemmProblem* problems, int n_problem
         total += g.d[i].tiles_m * g.d[i].tiles_n * splits;
     }
     g.total_tiles = total;
-    g.group_m = group_m_setting();
+    g.group_m = GROUP_M;
     g.pad_ = 0;
     g.trace = g_trace;
-    g.sk_partial = nullptr;
-    g.sk_flags = nullptr;
     g.rows_any = nullptr;
     for (int i = 0; i < n_problems; ++i)
         if (problems[i].rows_dev && !g.rows_any) g.rows_any = problems[i].rows_dev;
@@ -709,21 +676,3 @@ extern "C" int mh_gemm_set_trace(void* device_buffer) {
     g_trace = (unsigned long long*)device_buffer;
     return MH_OK;
 }
-
-#ifdef MH_LAB
-extern "C" int64_t mh_gemm_streamk_workspace_bytes(void) { return (int64_t)(SK_GRID * SK_PARTIAL_FLOATS * 4 + (SK_GRID + 16) * 4); }
-extern "C" int mh_gemm_set_streamk(void* workspace, int mode) {
-    if (mode < 0 || mode > 2 || (mode > 0 && !workspace)) return MH_EINVAL;
-    g_sk_partial = (float*)workspace;
-    g_sk_flags = workspace ? (unsigned*)((char*)workspace + SK_GRID * SK_PARTIAL_FLOATS * 4) : nullptr;
-    g_sk_mode = workspace ? mode : 0;
-    g_sk_force = mode == 2;
-    return MH_OK;
-}
-// -2 = the product's kernel (default); 0-13 = the lab kernels (csrc/lab/memehip_lab.h)
-extern "C" int mh_gemm_set_variant(int v) {
-    if (v != -2 && (v < 0 || v > 13)) return MH_EINVAL;
-    g_variant = v;
-    return MH_OK;
-}
-#endif

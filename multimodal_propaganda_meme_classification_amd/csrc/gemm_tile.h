@@ -5,7 +5,6 @@
 // its XCD distribution of the tiles, how a K stage is issued, and its epilogue.
 #pragma once
 #include "common.h"
-#include <stdlib.h>
 
 namespace mh_tile {
 
@@ -21,12 +20,13 @@ MH_DEV int swz_kstrided(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
 
 // ---- global -> LDS directly (LDS-DMA, buffer_load ... lds): no VGPR staging, no ds_write pass ---
 // One wave-instruction writes 1 KiB of LDS linearly (base + lane*16), so the swizzle is applied to
-// the per-lane SOURCE address (same involution as store_tile).  Wave w moves pieces 4w..4w+3.
-template <int KMAJOR, int PPW = 4>
+// the per-lane SOURCE address (an involution: read_frag applies the same one).  A tile is 16 such pieces: wave w moves 2w and 2w+1.
+constexpr int DMA_PPW = 16 / NW;
+template <int KMAJOR>
 MH_DEV void dma_tile(__amdgpu_buffer_rsrc_t r, int ld, int r0, int k0, int wave, int lane, char* lds) {
 #pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-        const int piece = wave * PPW + i;
+    for (int i = 0; i < DMA_PPW; ++i) {
+        const int piece = wave * DMA_PPW + i;
         uint32_t off;
         if (KMAJOR == 0) {
             const int row = piece * 8 + (lane >> 3);
@@ -97,15 +97,9 @@ MH_DEV void tile_coords(int tiles_n, int tiles_m, int group_m, int lt, int& tm, 
     tm = g * group_m + (r - tn * rows);
 }
 
-// GROUP_M of the tile order (0 / 1: n-fastest): MEMEHIP_GEMM_GROUP_M, default 8, read once for both kernels
-inline int group_m_setting() {
-    static const int group_m = [] {
-        const char* e = getenv("MEMEHIP_GEMM_GROUP_M");
-        const int v = e ? atoi(e) : 8;
-        return (v < 0 || v > 64) ? 8 : v;
-    }();
-    return group_m;
-}
+// GROUP_M of the tile order (0 / 1: n-fastest) for both kernels: 8 (measured in the step with the live-tile order: 8 -> 9.70-9.73 ms,
+// 4 -> 9.90-9.91, 16 -> 9.78, 6 -> 9.92; tools/lab/RESULTS.md)
+constexpr int GROUP_M = 8;
 
 // ---- split-K: K cut into `splits` chunks of whole K tiles -----------------------------------
 inline int ksplit_chunk(int K, int splits) { return ((K + splits - 1) / splits + BK - 1) / BK * BK; }

@@ -31,25 +31,6 @@ def _kind(t: torch.Tensor) -> str:
     return "fp16" if t.dtype == F16 else "bf16"
 
 
-_STREAMK_WS = {}      # (library kind, device index) -> workspace tensor, kept for the life of the process
-
-
-def ensure_streamk(lib, kind: str, device, mode=None) -> None:
-    """LAB builds only (libmemehip_lab*.so through MEMEHIP_LIB; tools/gemm_sk_check.py): the stream-K GEMM is not in the product
-    library -- it measured slower on this path's shapes (csrc/lab/gemm_lab.inc).  ``mode`` 1 / 2 allocates the workspace on this
-    device (accumulator images of 512 workgroups + zeroed flags, kept for the life of the process) and switches it on; 0 off."""
-    if not hasattr(lib, "mh_gemm_set_streamk"):
-        raise _lib.MemehipError("stream-K is a lab kernel: build `make -C csrc LAB=1` and load it through MEMEHIP_LIB / MEMEHIP_LIB_F16")
-    if mode == 0:
-        check(lib.mh_gemm_set_streamk(None, 0), "mh_gemm_set_streamk")
-        return
-    dev = torch.device(device)
-    key = (kind, dev.index if dev.index is not None else torch.cuda.current_device())
-    if key not in _STREAMK_WS:
-        _STREAMK_WS[key] = torch.zeros(int(lib.mh_gemm_streamk_workspace_bytes()), dtype=torch.uint8, device=dev)
-    check(lib.mh_gemm_set_streamk(_STREAMK_WS[key].data_ptr(), int(mode)), "mh_gemm_set_streamk")
-
-
 def _L(t: torch.Tensor):
     kind = _kind(t)
     return _lib.load(kind)

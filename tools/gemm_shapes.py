@@ -3,11 +3,9 @@ the benchmark's row counts (text: 2 096 live rows of a 4 096-row packed operand,
 with the step's epilogues, timed the same way for every candidate: N interleaved rounds in ONE process, HIP events around 10
 back-to-back launches, median over rounds.
 
-    python tools/gemm_shapes.py [--cands product,v10,v12,v3,torch] [--csv profiles/r04_gemm_shapes.csv]
+    python tools/gemm_shapes.py [--cands product,torch] [--csv profiles/r04_gemm_shapes.csv]
 
-candidates: `product` = the kernel the product library dispatches; `vN` = lab variant N (csrc/lab/memehip_lab.h; needs the lab build
-loaded: MEMEHIP_LIB_F16=.../libmemehip_lab_f16.so after `make -C csrc LAB=1`): v10 = epilogue straight from transposed accumulators,
-v12 = v10 + the 128x256x32 tile wherever legal ("wide"), v3 = 256x128 ping-pong ring ("pp"), v9 = persistent;
+candidates: `product` = the kernel the library dispatches (MEMEHIP_LIB / MEMEHIP_LIB_F16 select another build of it);
 
 `torch` = torch.matmul (hipBLASLt / rocBLAS) on the same operands: the two towers' problems as two calls (a library has no grouped
 launch) WITHOUT the fused epilogue (bias / GELU / residual would be further launches) -- an upper bound for what the library gives.
@@ -18,7 +16,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
-from multimodal_propaganda_meme_classification_amd import ops, _lib  # noqa: E402
+from multimodal_propaganda_meme_classification_amd import ops  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--cands", default="product,torch")
@@ -112,8 +110,6 @@ cases = {
     "wgrad_image 4 problems": wgrad(Ti, False),
 }
 
-kind = "fp16" if T16 == torch.float16 else "bf16"
-lib = _lib.load(kind)
 cands = args.cands.split(",")
 
 
@@ -121,12 +117,10 @@ def run(name, cand):
     ps, ak, bk, fl, mms = cases[name]
     if cand == "torch":
         fn = lambda: [m() for m in mms]
-    else:
-        if hasattr(lib, "mh_gemm_set_variant"):
-            lib.mh_gemm_set_variant(int(cand[1:]) if cand.startswith("v") else -2)
-        elif cand.startswith("v"):
-            raise SystemExit("lab variants need the lab build: MEMEHIP_LIB_F16=<repo>/multimodal_propaganda_meme_classification_amd/libmemehip_lab_f16.so")
+    elif cand == "product":
         fn = lambda: ops.gemm_grouped(ps, ak, bk)
+    else:
+        raise SystemExit(f"unknown candidate {cand!r}: product or torch")
     for _ in range(2):
         fn()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -143,8 +137,6 @@ for r in range(args.rounds):
     for name in cases:
         for c in cands:
             res.setdefault((name, c), []).append(run(name, c))
-if hasattr(lib, "mh_gemm_set_variant"):
-    lib.mh_gemm_set_variant(-2)
 
 rows = ["shape,candidate,us_median,us_min,TFLOPs_median"]
 tot = {c: 0.0 for c in cands}

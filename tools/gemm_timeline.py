@@ -1,20 +1,38 @@
-"""Where a grouped GEMM launch of config 3 spends its time, per workgroup: the default kernel's 100-MHz stamps (mh_gemm_set_trace)
+"""Where a grouped GEMM launch of config 3 spends its time, per workgroup: gemm_kernel's 100-MHz stamps (mh_gemm_set_trace)
 {entry, first K stage landed, main loop done, epilogue stores issued} for the four forward shapes and two dgrad shapes at the
 benchmark's row counts (2096 live text rows + 6304 image rows)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
-os.environ.setdefault("TT", "2096")
-import tools.gemm_ab as ab          # noqa: E402  (defines the cases; exits before timing when imported)
 from multimodal_propaganda_meme_classification_amd import ops, _lib  # noqa: E402
 
+dev = torch.device("cuda")
+BF16 = torch.bfloat16
+Tt, Ti, D, I = int(os.environ.get("TT", "2096")), 6304, 768, 3072
+
+
+def rnd(*s):
+    return (torch.randn(*s, device=dev) * 0.5).to(BF16)
+
+
+def fwd_group(N, K):
+    ps = [ops.Gemm(rnd(T, K), rnd(N, K), torch.empty((T, N), dtype=BF16, device=dev), T, N, K, K, K, N, bias=torch.zeros(N, device=dev))
+          for T in (Tt, Ti)]
+    return ps, False, False
+
+
+def dgrad_group(Nout, Kin):
+    ps = [ops.Gemm(rnd(T, Nout), rnd(Nout, Kin), torch.empty((T, Kin), dtype=BF16, device=dev), T, Kin, Nout, Nout, Kin, Kin) for T in (Tt, Ti)]
+    return ps, False, True
+
+
+cases = {"fwd qkv": fwd_group(3 * D, D), "fwd out": fwd_group(D, D), "fwd ffn1": fwd_group(I, D), "fwd ffn2": fwd_group(D, I),
+         "dgrad ffn2": dgrad_group(D, I), "dgrad qkv": dgrad_group(3 * D, D)}
+
 lib = _lib.load()
-if hasattr(lib, "mh_gemm_set_variant"):
-    lib.mh_gemm_set_variant(int(os.environ.get("GEMM_VARIANT", "-2")))
 buf = torch.zeros(4 * 4096, dtype=torch.int64, device="cuda")
-for name in ("fwd qkv", "fwd out", "fwd ffn1", "fwd ffn2", "dgrad ffn2", "dgrad qkv"):
-    ps, ak, bk, fl = ab.cases[name]
+for name, (ps, ak, bk) in cases.items():
     for _ in range(3):
         ops.gemm_grouped(ps, ak, bk)
     torch.cuda.synchronize()
