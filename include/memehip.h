@@ -786,10 +786,48 @@ int mh_sum_shards_16(const void* in /*[W][shard]*/, void* out /*[shard]*/, int W
  *   state int32[4] = {t, arrival counter (0), rows finished, output length once all rows finished (0 before)}.
  *   Column c = t + 1 of out_ids int64 [B][ld_out] receives the prompt token (c < prompt_len, read from out_ids itself), pad_id
  *   (row finished before), or the argmax, which marks the row finished when it is eos_id.  next_ids[b] = that token; t += 1.
+ *
+ * Beam search (rows are [image][beam], K beams per image, 2 <= K <= 8):
+ * mh_attn_decode_beams: mh_attn_decode with two more arguments (mh_attn_decode is this call with kv_group 1 and src NULL).
+ *   kv_group: row b reads the k / v of row b / kv_group (cross-attention: one copy of the image's k / v for its K beams).
+ *             B % kv_group == 0; the self form (t_dev) needs kv_group 1.
+ *   src     : self form only.  int32 [B][ld_src], ld_src >= T: key j < t of row b is read from cache row src[b][j] (entries
+ *             are clamped to [0, B)); this step's k / v still go to slot t of row b itself.  mh_beam_step keeps the table.
+ * mh_beam_step: two launches per step over f32 logits [B*K][ldl]: transformers' GenerationMixin._beam_search with one eos token.
+ *   Per row the f32 log-softmax ((x - max) - log(sum)) plus the beam's running score and the row's top 2K; per image the
+ *   ordered top 2K of the K*V candidates, the K running beams (the best that neither are eos nor reach cap, the maximum
+ *   length), the finished beams (candidates among the first K that stop, scored logp / (c + 1 - prompt_len) ** length_penalty,
+ *   merged with the K kept so far) and the early-stop heuristic.  early_stopping: 0 False, 1 True, 2 "never".
+ *   Ties: the larger f32 value first, then the lower flat index beam * V + token; in the later selections the lower position.
+ *   state int32[4] = {t, arrival counter (0), images closed this step (0), 1 once no image's finished beams can change}.
+ *   Column c = t + 1: inside the prompt (c < prompt_len) every beam takes run_seq's token and is its own parent.  t += 1.
+ *   The sequences (int32 [B*K][cap]) and src are permuted by parent in place; src[row][t] becomes the parent's row.
+ *   Start: run_scores {0, -1e9, ...} per image, fin_scores -1e9, fin_flags 0, fin_len 0, heur 1, state 0, run_seq = fin_seq =
+ *   the prompt padded with pad_id, next_ids the prompt's first token.  V >= 2K; logits must be finite or -inf.
  * ------------------------------------------------------------------------------------------ */
+typedef struct MhBeamState {
+    int64_t* next_ids;   /* [B*K] the running beams' new tokens: the next step's input ids */
+    int32_t* parents;    /* [B*K] the beam (0..K-1 of its image) each running beam continues */
+    float* run_scores;   /* [B*K] */
+    int32_t* run_seq;    /* [B*K][cap] */
+    int32_t* src;        /* [B*K][cap] cache ancestry table of mh_attn_decode_beams, or NULL */
+    int32_t* fin_seq;    /* [B*K][cap] finished beams, best first */
+    float* fin_scores;   /* [B*K] */
+    int32_t* fin_flags;  /* [B*K] 1: the slot holds a finished beam */
+    int32_t* fin_len;    /* [B*K] its generated length */
+    int32_t* heur;       /* [B] 1 while a running beam may still beat the worst finished one */
+    int32_t* state;      /* [4] */
+    float* cand_val;     /* [B*K][2K] workspace: each row's top 2K */
+    int32_t* cand_idx;   /* [B*K][2K] */
+} MhBeamState;
 int mh_attn_decode(const void* q, int ldq, void* k, void* v, int64_t ld_b, int ld_t, const void* kv_new, int ld_new,
                    const int32_t* t_dev, int T, void* out, int ldo, float* workspace, int nsplit, int B, int H,
                    mh_stream_t stream);
+int mh_attn_decode_beams(const void* q, int ldq, void* k, void* v, int64_t ld_b, int ld_t, const void* kv_new, int ld_new,
+                         const int32_t* t_dev, int T, void* out, int ldo, float* workspace, int nsplit, int B, int H,
+                         int kv_group, const int32_t* src, int ld_src, mh_stream_t stream);
+int mh_beam_step(const float* logits, int ldl, int V, int B, int K, const MhBeamState* st, int cap, int prompt_len,
+                 float length_penalty, int early_stopping, int64_t eos_id, mh_stream_t stream);
 int mh_decode_embed(const int64_t* ids /*[B]*/, const int32_t* t_dev, const float* word, const float* pos, const float* gamma,
                     const float* beta, void* y, int B, int D, int V, int P, float eps, mh_stream_t stream);
 int mh_greedy_step(const float* logits, int ldl, int V, int B, int64_t* out_ids, int ld_out, int64_t* next_ids,

@@ -37,6 +37,11 @@ class MhGemmProblem(C.Structure):
                 ("rows_dev", c_void_p), ("drop_rows", c_void_p), ("ksplit", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class MhBeamState(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("next_ids", "parents", "run_scores", "run_seq", "src", "fin_seq", "fin_scores", "fin_flags",
+                                        "fin_len", "heur", "state", "cand_val", "cand_idx")]
+
+
 class MhColsumJob(C.Structure):
     _fields_ = [("part", c_void_p), ("out0", c_void_p), ("out1", c_void_p)]
 
@@ -231,6 +236,9 @@ _PROTOS = {
     "mh_sum_shards_16": [c_void_p, c_void_p, c_int, c_int64, c_void_p],
     "mh_attn_decode": [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                        c_void_p, c_int, c_int, c_int, c_void_p],
+    "mh_attn_decode_beams": [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                             c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
+    "mh_beam_step": [c_void_p, c_int, c_int, c_int, c_int, C.POINTER(MhBeamState), c_int, c_int, c_float, c_int, c_int64, c_void_p],
     "mh_decode_embed": [c_void_p] * 7 + [c_int] * 4 + [c_float, c_void_p],
     "mh_greedy_step": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p],
     "mh_version": [],

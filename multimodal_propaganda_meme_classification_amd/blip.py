@@ -1,4 +1,4 @@
-"""BLIP image captioning (``BlipForConditionalGeneration.generate``, greedy) on the HIP kernels: the caption tower of Kevin's model.
+"""BLIP image captioning (``BlipForConditionalGeneration.generate``, greedy or beam search) on the HIP kernels: the caption tower of Kevin's model.
 
 The reference captions every image of every split inside ``MultimodalDataset.__init__`` (``Multimodal_example_task2C.py:195-256``):
 ``Salesforce/blip-image-captioning-large`` in fp16, the prompt ``"a meme of"``, batches of 64, ``generate(..., max_new_tokens=128)``.
@@ -18,6 +18,11 @@ Launch plan (activations are 16-bit row matrices, ``compute_dtype`` selects the 
   rows) and ``mh_greedy_step``.  The prompt goes through the same step one token at a time (causal: the same result as a prefill).
 * The step reads t, the input ids and the finished flags on the device, so it is captured once as a single-stream hipGraph and
   replayed per token; the host reads the "all rows finished" word every ``poll_every`` steps.
+* Beam search (``num_beams = K > 1``) runs the same step on B * K rows, [image][beam]: ``mh_beam_step`` replaces ``mh_greedy_step``
+  (transformers' ``_beam_search``: top 2K of the K * V accumulated log-probabilities, running and finished beams, the early-stop
+  heuristic, all on the device), cross-attention reads one k / v copy per image (``kv_group = K``), and the self-attention cache
+  stays in place: an int32 ancestry table [B * K][cap], permuted by ``mh_beam_step``, tells ``mh_attn_decode`` which physical row
+  holds each earlier position of a beam.
 """
 from __future__ import annotations
 
@@ -88,7 +93,8 @@ class _TextLayer(nn.Module):
 
 
 class BlipCaptioner(nn.Module):
-    """``BlipForConditionalGeneration`` (vision tower + text decoder + LM head) for greedy captioning on the HIP kernels."""
+    """``BlipForConditionalGeneration`` (vision tower + text decoder + LM head) for greedy and beam-search captioning on the HIP
+    kernels."""
 
     def __init__(self, text: dict, vision: dict, compute_dtype: str = "fp16"):
         super().__init__()
@@ -237,8 +243,9 @@ class BlipCaptioner(nn.Module):
         return y
 
     # ---- decoder state and one step -------------------------------------------------------------------------------------------
-    def _state(self, B: int, cap: int, device):
-        key = (B, cap, str(device))
+    def _state(self, B: int, cap: int, device, K: int = 1):
+        """buffers of the decode step for B images of K beams: R = B * K rows, cross k / v one copy per image"""
+        key = (B, cap, str(device), K)
         if key in self._states:
             return self._states[key]
         tc, T16 = self.text_cfg, self._T16()
@@ -246,35 +253,39 @@ class BlipCaptioner(nn.Module):
         Ni = (self.vision_cfg["image_size"] // self.vision_cfg["patch_size"]) ** 2 + 1
         Vp = self._pack["head"][3].shape[0]
         e = lambda *s, dt=T16: torch.empty(s, dtype=dt, device=device)
-        ns_self, ns_cross = ops.decode_splits(B, H, cap), ops.decode_splits(B, H, Ni)
-        st = dict(B=B, cap=cap, Ni=Ni, ns_self=ns_self, ns_cross=ns_cross,
-                  cache=[torch.zeros((B, cap, 2 * D), dtype=T16, device=device) for _ in range(nl)],
+        R = B * K
+        ns_self, ns_cross = ops.decode_splits(R, H, cap), ops.decode_splits(R, H, Ni)
+        st = dict(B=B, K=K, R=R, cap=cap, Ni=Ni, ns_self=ns_self, ns_cross=ns_cross,
+                  cache=[torch.zeros((R, cap, 2 * D), dtype=T16, device=device) for _ in range(nl)],
                   ckv=[e(B * Ni, 2 * D) for _ in range(nl)],
-                  x=e(B, D), x1=e(B, D), s=e(B, D), ctx=e(B, D), q=e(B, D), qkv=e(B, 3 * D), ffn=e(B, I), h=e(B, D),
-                  mean=e(B, dt=F32), rstd=e(B, dt=F32), logits=e(B, Vp, dt=F32),
-                  ws=e(B * H * max(ns_self, ns_cross, 1) * 66, dt=F32),
-                  out_ids=e(B, cap, dt=I64), next_ids=e(B, dt=I64), finished=e(B, dt=I32), sv=e(4, dt=I32), graph=None)
+                  x=e(R, D), x1=e(R, D), s=e(R, D), ctx=e(R, D), q=e(R, D), qkv=e(R, 3 * D), ffn=e(R, I), h=e(R, D),
+                  mean=e(R, dt=F32), rstd=e(R, dt=F32), logits=e(R, Vp, dt=F32),
+                  ws=e(R * H * max(ns_self, ns_cross, 1) * 66, dt=F32),
+                  out_ids=e(B, cap, dt=I64), next_ids=e(R, dt=I64), finished=e(B, dt=I32), sv=e(4, dt=I32), graph=None, beam=None)
         self._states = {key: st}          # one live batch shape at a time (the caches are large)
         return st
 
     def _step(self, st):
         pk, tc = self._pack, self.text_cfg
-        B, cap, Ni = st["B"], st["cap"], st["Ni"]
+        B, cap, Ni, K = st["R"], st["cap"], st["Ni"], st["K"]       # B: rows of the step ([image][beam] under beam search)
         D, H, eps = tc["hidden_size"], tc["num_attention_heads"], tc["layer_norm_eps"]
-        t = st["sv"][0:1]
+        beam = st["beam"]
+        t = st["sv"][0:1] if beam is None else beam["state"][0:1]
+        next_ids = st["next_ids"] if beam is None else beam["next_ids"]
+        src = None if beam is None else beam["src"]
         x, x1, s, ctx, q, qkv, ffn, h = (st[k] for k in ("x", "x1", "s", "ctx", "q", "qkv", "ffn", "h"))
         mean, rstd, ws = st["mean"], st["rstd"], st["ws"]
-        ops.decode_embed(st["next_ids"], t, pk["word"], pk["tpos"], *pk["emb_ln"], eps, x)
+        ops.decode_embed(next_ids, t, pk["word"], pk["tpos"], *pk["emb_ln"], eps, x)
         qkv_flat = qkv.view(-1)
         for lw, cache, ckv in zip(pk["txt"], st["cache"], st["ckv"]):
             cf, kf = cache.view(-1), ckv.view(-1)
             ops.linear_fwd(x, lw["wqkv"], bias=lw["bqkv"], out=qkv)
             ops.attn_decode(qkv, cf, cf[D:], ctx, B, H, cap, 3 * D, cap * 2 * D, 2 * D, D, t_dev=t, kv_new=qkv_flat[D:], ld_new=3 * D,
-                            nsplit=st["ns_self"], workspace=ws)
+                            nsplit=st["ns_self"], workspace=ws, src=src)
             ops.linear_fwd(ctx, lw["wo"], bias=lw["bo"], residual=x, out=s)
             ops.layernorm_fwd(s, *lw["ln1"], eps, y=x1, mean=mean, rstd=rstd)
             ops.linear_fwd(x1, lw["wcq"], bias=lw["bcq"], out=q)
-            ops.attn_decode(q, kf, kf[D:], ctx, B, H, Ni, D, Ni * 2 * D, 2 * D, D, nsplit=st["ns_cross"], workspace=ws)
+            ops.attn_decode(q, kf, kf[D:], ctx, B, H, Ni, D, Ni * 2 * D, 2 * D, D, nsplit=st["ns_cross"], workspace=ws, kv_group=K)
             ops.linear_fwd(ctx, lw["wco"], bias=lw["bco"], residual=x1, out=s)
             ops.layernorm_fwd(s, *lw["ln2"], eps, y=x1, mean=mean, rstd=rstd)
             ops.linear_fwd(x1, lw["wi"], bias=lw["bi"], gelu=True, out=ffn)
@@ -285,20 +296,35 @@ class BlipCaptioner(nn.Module):
         ops.layernorm_fwd(h, *lnh, eps, y=x1, mean=mean, rstd=rstd)
         Vp = wdec.shape[0]
         ops.gemm_grouped([ops.Gemm(x1, wdec, st["logits"], B, Vp, D, D, D, Vp, bias=bdec)], False, False)
-        ops.greedy_step(st["logits"], tc["vocab_size"], st["out_ids"], st["next_ids"], st["finished"], st["sv"], st["P"],
-                        tc["sep_token_id"], tc["pad_token_id"])
+        if beam is None:
+            ops.greedy_step(st["logits"], tc["vocab_size"], st["out_ids"], st["next_ids"], st["finished"], st["sv"], st["P"],
+                            tc["sep_token_id"], tc["pad_token_id"])
+        else:
+            ops.beam_step(st["logits"], tc["vocab_size"], beam, st["P"], st["length_penalty"], st["early_stopping"], tc["sep_token_id"])
 
-    def _prepare(self, pixel_values, prompt, cap):
+    def _prepare(self, pixel_values, prompt, cap, num_beams=1, length_penalty=1.0, early_stopping=False):
         """vision tower, cross k / v of every layer, and the step's state for this prompt (int64 [B, P] on the device)."""
         img = self.vision_forward(pixel_values)
         B, P = prompt.shape
-        st = self._state(B, cap, pixel_values.device)
-        st["P"] = P
+        st = self._state(B, cap, pixel_values.device, num_beams)
+        st["P"], st["length_penalty"], st["early_stopping"] = P, float(length_penalty), early_stopping
+        st["key"] = (P, num_beams, float(length_penalty), early_stopping)      # what a captured step has baked in
         D = self.text_cfg["hidden_size"]
         gs = [ops.Gemm(img, lw["wckv"], ckv, img.shape[0], 2 * D, img.shape[1], img.shape[1], img.shape[1], 2 * D, bias=lw["bckv"])
               for lw, ckv in zip(self._pack["txt"], st["ckv"])]
         for i in range(0, len(gs), _lib.MH_GEMM_MAX_GROUP):
             ops.gemm_grouped(gs[i:i + _lib.MH_GEMM_MAX_GROUP], False, False)
+        if num_beams > 1:
+            # transformers fills beam sequences with `pad_token_id or eos_token_id`: a pad id of 0 (BLIP's) counts as unset there
+            fill = self.text_cfg["pad_token_id"] or self.text_cfg["sep_token_id"]
+            if st["beam"] is None:
+                st["beam"] = ops.beam_state(B, num_beams, cap, prompt, fill, pixel_values.device)
+            else:                      # same tensors (a captured step points at them), start values
+                fresh = ops.beam_state(B, num_beams, cap, prompt, fill, pixel_values.device)
+                for n, v in fresh.items():
+                    if isinstance(v, torch.Tensor):
+                        st["beam"][n].copy_(v)
+            return st
         st["out_ids"].fill_(self.text_cfg["pad_token_id"])
         st["out_ids"][:, :P] = prompt
         st["next_ids"].copy_(prompt[:, 0])
@@ -306,21 +332,28 @@ class BlipCaptioner(nn.Module):
         st["sv"].zero_()
         return st
 
-    def _run(self, st, steps: int, graph: bool, poll_every: int, record=None):
-        """``steps`` decode steps (stops early once every row has finished, checked every ``poll_every`` steps)."""
+    def _run(self, st, steps: int, graph: bool, poll_every: int, record=None, trace=None):
+        """``steps`` decode steps (stops early once every row has finished, checked every ``poll_every`` steps).  ``record``: a
+        list that receives each step's logits; ``trace`` (beam search): a list that receives, per step, a dict of copies of the
+        logits the step used and of the beam state after it (``ops.beam_state``'s tensors)."""
+        done = st["sv"] if st["beam"] is None else st["beam"]["state"]
         for i in range(steps):
             if i == 0 or not graph:
                 self._step(st)
             else:
-                if st["graph"] is None or st["graph_P"] != st["P"]:
+                if st["graph"] is None or st["graph_key"] != st["key"]:
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g):
                         self._step(st)
-                    st["graph"], st["graph_P"] = g, st["P"]
+                    st["graph"], st["graph_key"] = g, st["key"]
                 st["graph"].replay()
             if record is not None:
                 record.append(st["logits"][:, :self.text_cfg["vocab_size"]].clone())
-            if i + 1 < steps and (i + 1) % poll_every == 0 and int(st["sv"][3]) != 0:
+            if trace is not None:
+                snap = {n: v.clone() for n, v in st["beam"].items() if isinstance(v, torch.Tensor) and not n.startswith("cand_")}
+                snap["logits"] = st["logits"][:, :self.text_cfg["vocab_size"]].clone()
+                trace.append(snap)
+            if i + 1 < steps and (i + 1) % poll_every == 0 and int(done[3]) != 0:
                 break
 
     # ---- public surface -------------------------------------------------------------------------------------------------------
@@ -340,17 +373,38 @@ class BlipCaptioner(nn.Module):
 
     @torch.no_grad()
     def generate(self, pixel_values: torch.Tensor, input_ids: Optional[torch.Tensor] = None, attention_mask=None,
-                 max_new_tokens: int = 20, *, graph: bool = True, poll_every: int = 8, num_beams: int = 1, do_sample: bool = False,
+                 max_new_tokens: int = 20, *, graph: bool = True, poll_every: int = 8, num_beams: int = 1, length_penalty: float = 1.0,
+                 early_stopping=False, num_return_sequences: int = 1, do_sample: bool = False,
                  repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_length: int = 0, min_new_tokens: int = 0,
-                 interpolate_pos_encoding: bool = False) -> torch.LongTensor:
-        """``BlipForConditionalGeneration.generate(pixel_values, input_ids, attention_mask, max_new_tokens=...)`` under greedy
-        decoding: ``input_ids[:, 0]`` becomes ``bos_token_id``, the last prompt token is dropped, rows that emitted eos
-        (``sep_token_id``) continue with ``pad_token_id``, and the output ends at the step where the last row finished (or after
-        ``max_new_tokens``).  ``graph=False`` runs the same launches without the hipGraph."""
-        if num_beams != 1:
-            raise ValueError("beam search (num_beams > 1) is not implemented")
+                 interpolate_pos_encoding: bool = False, _trace=None) -> torch.LongTensor:
+        """``BlipForConditionalGeneration.generate(pixel_values, input_ids, attention_mask, max_new_tokens=...)``:
+        ``input_ids[:, 0]`` becomes ``bos_token_id``, the last prompt token is dropped, eos is ``sep_token_id``.
+
+        Greedy (``num_beams=1``, the default): rows that emitted eos continue with ``pad_token_id``, and the output ends at the step
+        where the last row finished (or after ``max_new_tokens``).
+
+        Beam search (``2 <= num_beams <= 8``, with ``length_penalty`` and ``early_stopping`` False, True or ``"never"``):
+        transformers' ``_beam_search`` on the device.  The best finished beam of every image is returned, cut to the prompt plus
+        the longest generated length among the returned beams and padded as transformers pads it: with ``pad_token_id or
+        eos_token_id``, i.e. with eos where the pad id is 0, as BLIP's is.  Where torch.topk leaves
+        a tie open, the lower flat index ``beam * vocab_size + token`` wins (the lower position in the later selections).  The loop
+        ends once no image's finished beams can change any more (transformers may run further steps; the result is the same).
+
+        ``graph=False`` runs the same launches without the hipGraph.  Refused with ``ValueError``: ``num_beams`` outside 1..8,
+        ``num_return_sequences != 1``, sampling, ``repetition_penalty != 1``, ``no_repeat_ngram_size``, ``min_length`` /
+        ``min_new_tokens``, ``interpolate_pos_encoding``, prompt attention masks with zeros, and ``num_beams > 1`` for a model or
+        batch that is not on the HIP device (greedy calls there raise ``MemehipError``: there is no CPU path at all)."""
+        if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= 8:
+            raise ValueError("num_beams must be an integer from 1 (greedy) to 8")
+        if num_return_sequences != 1:
+            raise ValueError("num_return_sequences != 1 is not implemented (the best beam of every image is returned)")
+        if not isinstance(early_stopping, bool) and early_stopping != "never":
+            raise ValueError("early_stopping must be False, True or 'never'")
         if do_sample:
-            raise ValueError("sampling is not implemented (greedy decoding only)")
+            raise ValueError("sampling is not implemented (greedy decoding and beam search only)")
+        if num_beams > 1 and not (isinstance(pixel_values, torch.Tensor) and pixel_values.is_cuda and next(self.parameters()).is_cuda):
+            # (the argument is refused, as before beam search existed: the search lives in the device step and nowhere else)
+            raise ValueError("beam search (num_beams > 1) exists only in the HIP decode step: move the model and batch with .to(device)")
         if repetition_penalty != 1.0:
             raise ValueError("repetition_penalty != 1 is not implemented")
         if no_repeat_ngram_size:
@@ -373,6 +427,14 @@ class BlipCaptioner(nn.Module):
         if cap > self.text_cfg["max_position_embeddings"]:
             raise ValueError("prompt + max_new_tokens exceeds max_position_embeddings")
         self._packed()
+        if num_beams > 1:
+            if self.text_cfg["vocab_size"] < 2 * num_beams:
+                raise ValueError("beam search needs vocab_size >= 2 * num_beams")
+            st = self._prepare(pixel_values, prompt, cap, num_beams, length_penalty, early_stopping)
+            self._run(st, P - 1 + int(max_new_tokens), graph, int(poll_every), trace=_trace)
+            bs = st["beam"]
+            best_len = bs["fin_len"].view(-1, num_beams)[:, 0]
+            return bs["fin_seq"].view(-1, num_beams, cap)[:, 0, :P + int(best_len.max())].to(I64)
         st = self._prepare(pixel_values, prompt, cap)
         self._run(st, P - 1 + int(max_new_tokens), graph, int(poll_every))
         sv = st["sv"].cpu()

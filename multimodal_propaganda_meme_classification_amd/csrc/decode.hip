@@ -4,6 +4,12 @@
 //                    the self-attention form first stores this step's k / v into cache slot t (t read on the device)
 //   mh_decode_embed  LayerNorm(word[id] + pos[t]) for one token per row (id and t read on the device)
 //   mh_greedy_step   row argmax of the LM head's f32 logits + the greedy bookkeeping of transformers' generate
+//   mh_beam_step     beam search over the same logits (2 <= K <= 8 beams per image): log-softmax + the row's top 2K, then per image
+//                    the ordered top 2K of K*V candidates and the running / finished bookkeeping of transformers' _beam_search
+//
+// Beams: the rows are [image][beam].  Cross-attention k / v stay one copy per image (kv_group rows share it).  The self-attention
+// cache does not move when beams are re-ordered: an ancestry table src[row][position] names the physical cache row that holds the
+// k / v of that position for the beam now living in `row`; mh_beam_step permutes the table, mh_attn_decode reads keys through it.
 //
 // Every state that changes from step to step (t, the input ids, the finished flags) lives in device memory, so one step is
 // captured once as a hipGraph and replayed per token.  Every sum runs in a fixed order: results are bit-identical run to run.
@@ -29,8 +35,9 @@ struct DecodeArgs {
     const int32_t* t_dev;  // self form: the slot of this step (keys 0..t attend; t >= T: no store, keys 0..T-1); NULL: T keys
     h16* out;              // out of (b, h) at out + b*ldo + h*64
     float* ws;             // nsplit > 1: [B*H][nsplit][DEC_WS]
+    const int32_t* src;    // beams: key j < t of row b lives in cache row src[b*ld_src + j] (NULL: in row b itself)
     int64_t ld_b;
-    int ldq, ld_t, ld_new, ldo, T, H, nsplit, chunk;
+    int ldq, ld_t, ld_new, ldo, T, H, nsplit, chunk, ld_src, kv_group;
 };
 
 MH_DEV float sum8(float x, unsigned lane) {      // sum over the 8 lanes of a group (lanes 8g .. 8g+7)
@@ -55,7 +62,9 @@ __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(DecodeArgs a) 
     const int t = a.t_dev ? a.t_dev[0] : -1;
     const int T = a.t_dev ? min(t + 1, a.T) : a.T;          // keys this step attends
     const h16* newk = a.kv_new ? a.kv_new + (int64_t)b * a.ld_new + h * 64 : nullptr;
-    const int64_t base = (int64_t)b * a.ld_b + h * 64;
+    const int64_t base = (int64_t)(b / a.kv_group) * a.ld_b + h * 64;      // kv_group rows read one image's k / v
+    const int32_t* srow = a.src ? a.src + (int64_t)b * a.ld_src : nullptr;
+    const int last_row = (int)gridDim.z - 1;
 
     // self form: the split that owns slot t stores this step's k / v row there (the step itself reads them from kv_new)
     if (a.t_dev && t >= 0 && t < a.T && split == 0 && tid < 16) {
@@ -76,11 +85,20 @@ __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(DecodeArgs a) 
         // two keys per group and pass: their four 16-byte loads are issued together
         const int jj[2] = {jb, jb + DEC_GROUPS};
         float kf[2][8], vf[2][8], s[2];
+        int64_t rb[2] = {base, base};
+        if (srow) {                                          // both table entries of the trip are loaded before its keys
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int j = jj[u] < j1 ? jj[u] : jb;
+                const int r = j == t ? b : srow[j];          // (slot t is this step's own: its entry is written by mh_beam_step)
+                rb[u] = (int64_t)min(max(r, 0), last_row) * a.ld_b + h * 64;
+            }
+        }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int j = jj[u] < j1 ? jj[u] : jb;           // (a missing second key re-reads the first and is dropped below)
-            const h16* kp = (j == t) ? newk : a.k + base + (int64_t)j * a.ld_t;
-            const h16* vp = (j == t) ? newk + a.H * 64 : a.v + base + (int64_t)j * a.ld_t;
+            const h16* kp = (j == t) ? newk : a.k + rb[u] + (int64_t)j * a.ld_t;
+            const h16* vp = (j == t) ? newk + a.H * 64 : a.v + rb[u] + (int64_t)j * a.ld_t;
             load8(kp + l8 * 8, kf[u]);
             load8(vp + l8 * 8, vf[u]);
         }
@@ -280,14 +298,302 @@ __global__ void __launch_bounds__(256) greedy_step_kernel(const float* logits, i
     }
 }
 
+// ---- beam search ------------------------------------------------------------------------------------------------------------------
+// One order everywhere: the larger f32 value first, then the lower index (the flat candidate index beam * V + token in the image's
+// top 2K, the position in the later selections).  torch.topk leaves ties open; this is the rule they get here.
+constexpr int BEAM_MAX = 8;
+constexpr float BEAM_NEG = -1.0e9f;
+
+MH_DEV bool beam_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+MH_DEV void lse_merge(float& m, float& s, float om, float os) {
+    const float M = fmaxf(m, om);
+    s = s * (m == M ? 1.f : expf(m - M)) + os * (om == M ? 1.f : expf(om - M));
+    m = M;
+}
+
+// One workgroup per beam row: the row's log-sum-exp (f32, fixed order) and its own top N = 2K accumulated log-probabilities
+// ((x - max) - log(sum)) + score, the oracle's f32 operations in its order.  The image's top 2K is a subset of the union of these.
+// The second pass re-reads the row (122 KB at V = 30524, from L2) because the order is taken on the rounded accumulated value: two
+// logits that round to one value tie, and the tie goes to the lower index.
+template <int N>
+__global__ void __launch_bounds__(256) beam_row_kernel(const float* logits, int ldl, int V, const float* run_scores, const int32_t* state,
+                                                       int prompt_len, int cap, float* cand_val, int32_t* cand_idx) {
+    __shared__ float shm[4], shs[4];
+    __shared__ int shi[4];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const int col = state[0] + 1;
+    if (col < prompt_len || col >= cap) return;           // inside the prompt, or past the end: no candidates are needed
+    const float* row = logits + (int64_t)r * ldl;
+    float m = -INFINITY, s = 0.f;
+    for (int c = tid * 4; c < V; c += 256 * 4) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(row + c);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (c + i < V && x[i] != -INFINITY) {
+                if (x[i] > m) {
+                    s = s * expf(m - x[i]) + 1.f;
+                    m = x[i];
+                } else {
+                    s += expf(x[i] - m);
+                }
+            }
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+        lse_merge(m, s, om, os);
+    }
+    if ((tid & 63) == 0) {
+        shm[tid >> 6] = m;
+        shs[tid >> 6] = s;
+    }
+    __syncthreads();
+    m = shm[0], s = shs[0];
+    for (int w = 1; w < 4; ++w) lse_merge(m, s, shm[w], shs[w]);
+    const float lse = logf(s), score = run_scores[r];
+
+    float lv[N];
+    int li[N];
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        lv[n] = -INFINITY;
+        li[n] = 0x7fffffff;
+    }
+    for (int c = tid * 4; c < V; c += 256 * 4) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(row + c);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float f = ((x[i] - m) - lse) + score;
+            if (c + i < V && beam_better(f, c + i, lv[N - 1], li[N - 1])) {
+                lv[N - 1] = f;
+                li[N - 1] = c + i;
+#pragma unroll
+                for (int n = N - 1; n > 0; --n)
+                    if (beam_better(lv[n], li[n], lv[n - 1], li[n - 1])) {
+                        const float tv = lv[n];
+                        const int ti = li[n];
+                        lv[n] = lv[n - 1], li[n] = li[n - 1];
+                        lv[n - 1] = tv, li[n - 1] = ti;
+                    }
+            }
+        }
+    }
+    // N rounds: the best entry of the workgroup that ranks after the previous round's winner
+    float pv = INFINITY;
+    int pi = -1;
+    for (int round = 0; round < N; ++round) {
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int n = N - 1; n >= 0; --n)
+            if (beam_better(pv, pi, lv[n], li[n])) {      // the list is sorted: the last hit from the back is the first from the front
+                bv = lv[n];
+                bi = li[n];
+            }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (beam_better(ov, oi, bv, bi)) {
+                bv = ov;
+                bi = oi;
+            }
+        }
+        __syncthreads();
+        if ((tid & 63) == 0) {
+            shm[tid >> 6] = bv;
+            shi[tid >> 6] = bi;
+        }
+        __syncthreads();
+        bv = shm[0], bi = shi[0];
+        for (int w = 1; w < 4; ++w)
+            if (beam_better(shm[w], shi[w], bv, bi)) {
+                bv = shm[w];
+                bi = shi[w];
+            }
+        if (tid == 0) {
+            cand_val[(int64_t)r * N + round] = bv;
+            cand_idx[(int64_t)r * N + round] = bi;
+        }
+        pv = bv, pi = bi;
+    }
+}
+
+MH_DEV int pick8(const int (&a)[BEAM_MAX], int p) {
+    int v = a[0];
+#pragma unroll
+    for (int k = 1; k < BEAM_MAX; ++k) v = p == k ? a[k] : v;
+    return v;
+}
+
+struct BeamArgs {
+    MhBeamState s;
+    int V, K, cap, prompt_len, early_stopping, eos;
+    float length_penalty;
+};
+
+// One workgroup per image.  state words: [0] t, [1] arrival counter (0 between launches), [2] images closed in this step (0
+// between launches), [3] 1 once no image can change its finished beams any more.
+__global__ void __launch_bounds__(256) beam_image_kernel(BeamArgs a) {
+    __shared__ float cv[2 * BEAM_MAX * BEAM_MAX], ov[2 * BEAM_MAX], ms[3 * BEAM_MAX], nrs[BEAM_MAX], nfs[BEAM_MAX];
+    __shared__ int ci[2 * BEAM_MAX * BEAM_MAX], oi[2 * BEAM_MAX], cpar[2 * BEAM_MAX], ctok[2 * BEAM_MAX], hit[2 * BEAM_MAX], taken[3 * BEAM_MAX];
+    __shared__ int rpar[BEAM_MAX], rtok[BEAM_MAX], ffrom[BEAM_MAX], mflag[3 * BEAM_MAX], mlen[3 * BEAM_MAX], nflag[BEAM_MAX], nlen[BEAM_MAX];
+    const MhBeamState& S = a.s;
+    const int b = blockIdx.x, tid = threadIdx.x, K = a.K, N = 2 * a.K, cap = a.cap, P = a.prompt_len;
+    const int t = S.state[0], col = t + 1;
+    const int r0 = b * K;
+    bool closed = false;
+    if (col < cap && col < P) {
+        // inside the prompt: every beam takes the prompt's next token and stays where it is
+        if (tid < K) {
+            const int r = r0 + tid;
+            S.next_ids[r] = S.run_seq[(int64_t)r * cap + col];
+            S.parents[r] = tid;
+            if (S.src && t >= 0) S.src[(int64_t)r * cap + t] = r;
+        }
+    } else if (col < cap) {
+        const int n = K * N;
+        if (tid < n) {
+            const int beam = tid / N;
+            cv[tid] = S.cand_val[(int64_t)r0 * N + tid];
+            ci[tid] = beam * a.V + S.cand_idx[(int64_t)r0 * N + tid];
+        }
+        __syncthreads();
+        if (tid < n) {                                    // rank by counting: the flat indices are distinct, so the ranks are too
+            const float v = cv[tid];
+            const int i = ci[tid];
+            int rank = 0;
+            for (int o = 0; o < n; ++o) rank += beam_better(cv[o], ci[o], v, i) ? 1 : 0;
+            if (rank < N) {
+                ov[rank] = v;
+                oi[rank] = i;
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            bool allhit = true;
+            for (int j = 0; j < N; ++j) {
+                cpar[j] = min(max(oi[j] / a.V, 0), K - 1);      // (in range whatever a row of NaNs left in the candidates)
+                ctok[j] = min(max(oi[j] % a.V, 0), a.V - 1);
+                hit[j] = (ctok[j] == a.eos || col + 1 >= cap) ? 1 : 0;
+                allhit = allhit && hit[j];
+            }
+            // running beams: the best K of the 2K that do not stop
+            for (int j = 0; j < N; ++j) {
+                ms[j] = hit[j] ? ov[j] + BEAM_NEG : ov[j];
+                taken[j] = 0;
+            }
+            for (int k = 0; k < K; ++k) {
+                int best = -1;
+                for (int j = 0; j < N; ++j)
+                    if (!taken[j] && (best < 0 || ms[j] > ms[best])) best = j;
+                taken[best] = 1;
+                nrs[k] = ms[best];
+                rpar[k] = cpar[best];
+                rtok[k] = ctok[best];
+            }
+            // finished beams: the old K and the 2K candidates, merged; the best K stay
+            const int glen = col + 1 - P;
+            const float pen = (float)pow((double)glen, (double)a.length_penalty);
+            bool allfin = true;
+            for (int k = 0; k < K; ++k) allfin = allfin && S.fin_flags[r0 + k] != 0;
+            const bool full = allfin && a.early_stopping == 1;
+            bool heur = S.heur[b] != 0;
+            for (int k = 0; k < K; ++k) {
+                ms[k] = S.fin_scores[r0 + k];
+                mflag[k] = S.fin_flags[r0 + k];
+                mlen[k] = S.fin_len[r0 + k];
+                taken[k] = 0;
+            }
+            for (int j = 0; j < N; ++j) {
+                const bool did = hit[j] && j < K;
+                float f = ov[j] / pen;
+                if (full) f += BEAM_NEG;
+                if (!heur) f += BEAM_NEG;
+                if (!did) f += BEAM_NEG;
+                ms[K + j] = f;
+                mflag[K + j] = did ? 1 : 0;
+                mlen[K + j] = glen;
+                taken[K + j] = 0;
+            }
+            for (int k = 0; k < K; ++k) {
+                int best = -1;
+                for (int j = 0; j < K + N; ++j)
+                    if (!taken[j] && (best < 0 || ms[j] > ms[best])) best = j;
+                taken[best] = 1;
+                ffrom[k] = best;
+                nfs[k] = ms[best];
+                nflag[k] = mflag[best];
+                nlen[k] = mlen[best];
+            }
+            // can a running beam still beat the worst finished one?
+            const int hyp = (a.early_stopping == 2 && a.length_penalty > 0.f) ? cap - P : glen;
+            const float best_running = nrs[0] / (float)pow((double)hyp, (double)a.length_penalty);
+            float worst = nfs[0];
+            bool newall = true, any = false;
+            for (int k = 0; k < K; ++k) {
+                worst = fminf(worst, nfs[k]);
+                newall = newall && nflag[k];
+            }
+            for (int k = 0; k < K; ++k) any = any || best_running > (nflag[k] ? worst : BEAM_NEG);
+            heur = heur && any;
+            for (int k = 0; k < K; ++k) {
+                S.next_ids[r0 + k] = rtok[k];
+                S.parents[r0 + k] = rpar[k];
+                S.run_scores[r0 + k] = nrs[k];
+                S.fin_scores[r0 + k] = nfs[k];
+                S.fin_flags[r0 + k] = nflag[k];
+                S.fin_len[r0 + k] = nlen[k];
+            }
+            S.heur[b] = heur ? 1 : 0;
+            closed = !heur || (a.early_stopping == 1 && newall) || allhit;
+        }
+        __syncthreads();
+        // the sequences and the cache's ancestry table follow the beams: one column per thread and pass, K values in registers
+        for (int c = tid; c <= col; c += 256) {
+            int orun[BEAM_MAX], ofin[BEAM_MAX], osrc[BEAM_MAX];
+#pragma unroll
+            for (int k = 0; k < BEAM_MAX; ++k) {
+                const int64_t at = (int64_t)(r0 + (k < K ? k : 0)) * cap + c;
+                orun[k] = S.run_seq[at];
+                ofin[k] = S.fin_seq[at];
+                osrc[k] = (S.src && c < t) ? S.src[at] : 0;
+            }
+#pragma unroll
+            for (int k = 0; k < BEAM_MAX; ++k) {
+                if (k >= K) break;
+                const int64_t at = (int64_t)(r0 + k) * cap + c;
+                S.run_seq[at] = c == col ? rtok[k] : pick8(orun, rpar[k]);
+                const int from = ffrom[k];
+                S.fin_seq[at] = from < K ? pick8(ofin, from) : (c == col ? ctok[from - K] : pick8(orun, cpar[from - K]));
+                if (S.src && c <= t) S.src[at] = c == t ? r0 + rpar[k] : pick8(osrc, rpar[k]);
+            }
+        }
+    }
+    if (tid == 0) {
+        if (closed) __hip_atomic_fetch_add(&S.state[2], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // every workgroup has read t and counted itself before it arrives; the last one to arrive advances t and re-arms the counters
+        const int arrived = __hip_atomic_fetch_add(&S.state[1], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (arrived == (int)gridDim.x - 1) {
+            const int nclosed = __hip_atomic_load(&S.state[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (nclosed == (int)gridDim.x) __hip_atomic_store(&S.state[3], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&S.state[2], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&S.state[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&S.state[0], t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
 }  // namespace
 
-extern "C" int mh_attn_decode(const void* q, int ldq, void* k, void* v, int64_t ld_b, int ld_t, const void* kv_new, int ld_new,
-                              const int32_t* t_dev, int T, void* out, int ldo, float* workspace, int nsplit, int B, int H,
-                              mh_stream_t stream) {
-    if (!q || !k || !v || !out || (t_dev && !kv_new) || (nsplit > 1 && !workspace)) return MH_EINVAL;
+extern "C" int mh_attn_decode_beams(const void* q, int ldq, void* k, void* v, int64_t ld_b, int ld_t, const void* kv_new, int ld_new,
+                                    const int32_t* t_dev, int T, void* out, int ldo, float* workspace, int nsplit, int B, int H,
+                                    int kv_group, const int32_t* src, int ld_src, mh_stream_t stream) {
+    if (!q || !k || !v || !out || (t_dev && !kv_new) || (nsplit > 1 && !workspace) || (src && !t_dev)) return MH_EINVAL;
     if (B < 1 || H < 1 || T < 1 || nsplit < 1 || nsplit > 64 || ldq % 8 || ld_t % 8 || ld_b % 8 || ld_new % 8 || ldo < H * 64)
         return MH_ESHAPE;
+    if (kv_group < 1 || B % kv_group || (t_dev && kv_group != 1) || (src && ld_src < T)) return MH_ESHAPE;
     DecodeArgs a;
     a.q = (const h16*)q;
     a.k = (h16*)k;
@@ -296,6 +602,9 @@ extern "C" int mh_attn_decode(const void* q, int ldq, void* k, void* v, int64_t 
     a.t_dev = t_dev;
     a.out = (h16*)out;
     a.ws = workspace;
+    a.src = src;
+    a.ld_src = ld_src;
+    a.kv_group = kv_group;
     a.ld_b = ld_b;
     a.ldq = ldq; a.ld_t = ld_t; a.ld_new = ld_new; a.ldo = ldo;
     a.T = T; a.H = H; a.nsplit = nsplit;
@@ -304,6 +613,12 @@ extern "C" int mh_attn_decode(const void* q, int ldq, void* k, void* v, int64_t 
     hipLaunchKernelGGL(attn_decode_kernel, dim3(nsplit, H, B), dim3(DEC_THREADS), 0, s, a);
     if (nsplit > 1) hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(H, B), dim3(64), 0, s, (const float*)workspace, (h16*)out, ldo, H, nsplit);
     return mh_launch_status();
+}
+
+extern "C" int mh_attn_decode(const void* q, int ldq, void* k, void* v, int64_t ld_b, int ld_t, const void* kv_new, int ld_new,
+                              const int32_t* t_dev, int T, void* out, int ldo, float* workspace, int nsplit, int B, int H,
+                              mh_stream_t stream) {
+    return mh_attn_decode_beams(q, ldq, k, v, ld_b, ld_t, kv_new, ld_new, t_dev, T, out, ldo, workspace, nsplit, B, H, 1, nullptr, 0, stream);
 }
 
 extern "C" int mh_decode_embed(const int64_t* ids, const int32_t* t_dev, const float* word, const float* pos, const float* gamma,
@@ -320,5 +635,32 @@ extern "C" int mh_greedy_step(const float* logits, int ldl, int V, int B, int64_
     if (B < 1 || V < 1 || ldl < V || ldl % 4 || prompt_len < 1 || ld_out <= prompt_len) return MH_ESHAPE;
     hipLaunchKernelGGL(greedy_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ldl, V, out_ids, ld_out, next_ids, finished,
                        state, prompt_len, eos_id, pad_id);
+    return mh_launch_status();
+}
+
+extern "C" int mh_beam_step(const float* logits, int ldl, int V, int B, int K, const MhBeamState* st, int cap, int prompt_len,
+                            float length_penalty, int early_stopping, int64_t eos_id, mh_stream_t stream) {
+    if (!logits || !st || !st->next_ids || !st->parents || !st->run_scores || !st->run_seq || !st->fin_seq || !st->fin_scores ||
+        !st->fin_flags || !st->fin_len || !st->heur || !st->state || !st->cand_val || !st->cand_idx)
+        return MH_EINVAL;
+    if (B < 1 || K < 2 || K > BEAM_MAX || V < 2 * K || (int64_t)K * V > 0x7fffffff || ldl < V || ldl % 4 || prompt_len < 1 ||
+        cap <= prompt_len || early_stopping < 0 || early_stopping > 2 || (int64_t)B * K * cap > 0x7fffffff)
+        return MH_ESHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    const int R = B * K;
+#define MH_BEAM_ROW(KK)                                                                                                               \
+    case KK:                                                                                                                          \
+        hipLaunchKernelGGL(beam_row_kernel<2 * KK>, dim3(R), dim3(256), 0, s, logits, ldl, V, (const float*)st->run_scores,           \
+                           (const int32_t*)st->state, prompt_len, cap, st->cand_val, st->cand_idx);                                   \
+        break;
+    switch (K) {
+        MH_BEAM_ROW(2) MH_BEAM_ROW(3) MH_BEAM_ROW(4) MH_BEAM_ROW(5) MH_BEAM_ROW(6) MH_BEAM_ROW(7) MH_BEAM_ROW(8)
+    }
+#undef MH_BEAM_ROW
+    BeamArgs a;
+    a.s = *st;
+    a.V = V; a.K = K; a.cap = cap; a.prompt_len = prompt_len; a.early_stopping = early_stopping; a.eos = (int)eos_id;
+    a.length_penalty = length_penalty;
+    hipLaunchKernelGGL(beam_image_kernel, dim3(B), dim3(256), 0, s, a);
     return mh_launch_status();
 }

@@ -727,10 +727,13 @@ def _i32(t, name):
     return t
 
 
-def attn_decode(q, k, v, out, B, H, T, ldq, ld_b, ld_t, ldo, t_dev=None, kv_new=None, ld_new=0, nsplit=None, workspace=None):
+def attn_decode(q, k, v, out, B, H, T, ldq, ld_b, ld_t, ldo, t_dev=None, kv_new=None, ld_new=0, nsplit=None, workspace=None,
+                kv_group=1, src=None):
     """mh_attn_decode: out[b, h] = softmax(q[b, h] . k[b, h, :T]^T / 8) v[b, h, :T] (16-bit views with element strides; see the
     header).  t_dev (device int32 [1]) selects the self-attention form: kv_new's k / v rows are stored into slot t first and keys
-    0..t attend (T = the cache capacity).  nsplit None: decode_splits(B, H, T); a workspace is allocated when it is > 1."""
+    0..t attend (T = the cache capacity).  nsplit None: decode_splits(B, H, T); a workspace is allocated when it is > 1.
+    Beams (mh_attn_decode_beams): kv_group rows share the k / v of row b // kv_group; src (device int32 [B, >= T], self form) names
+    the cache row that holds key j < t of row b."""
     for nm, t in (("q", q), ("k", k), ("v", v), ("out", out)):
         _chk(t, BF16, nm, False)
     if len({q.dtype, k.dtype, v.dtype, out.dtype}) != 1:
@@ -742,7 +745,14 @@ def attn_decode(q, k, v, out, B, H, T, ldq, ld_b, ld_t, ldo, t_dev=None, kv_new=
             raise ValueError("attn_decode: kv_new smaller than B / ld_new / H imply")
     if q.numel() < (B - 1) * ldq + H * 64 or out.numel() < (B - 1) * ldo + H * 64:
         raise ValueError("attn_decode: q / out smaller than B / ld / H imply")
-    need = (B - 1) * ld_b + (T - 1) * ld_t + H * 64
+    kv_group = int(kv_group)
+    if kv_group < 1 or B % kv_group or (t_dev is not None and kv_group != 1):
+        raise ValueError("attn_decode: kv_group must divide B, and be 1 in the self form")
+    if src is not None:
+        _i32(src, "src")
+        if t_dev is None or src.dim() != 2 or src.shape[0] != B or src.shape[1] < T or not src.is_contiguous():
+            raise ValueError("attn_decode: src is a contiguous int32 [B, >= T] table of the self form")
+    need = (B // kv_group - 1) * ld_b + (T - 1) * ld_t + H * 64
     if k.numel() < need or v.numel() < need:
         raise ValueError("attn_decode: k / v smaller than B / T / strides imply")
     nsplit = decode_splits(B, H, T) if nsplit is None else int(nsplit)
@@ -752,8 +762,13 @@ def attn_decode(q, k, v, out, B, H, T, ldq, ld_b, ld_t, ldo, t_dev=None, kv_new=
         _chk(workspace, F32, "workspace")
         if workspace.numel() < B * H * nsplit * 66:
             raise ValueError("attn_decode: workspace smaller than B * H * nsplit * 66")
-    check(_L(q).mh_attn_decode(_p(q), int(ldq), _p(k), _p(v), int(ld_b), int(ld_t), _p(kv_new), int(ld_new), _p(t_dev), int(T), _p(out),
-                               int(ldo), _p(workspace) if nsplit > 1 else None, nsplit, int(B), int(H), _stream()), "mh_attn_decode")
+    if kv_group == 1 and src is None:
+        check(_L(q).mh_attn_decode(_p(q), int(ldq), _p(k), _p(v), int(ld_b), int(ld_t), _p(kv_new), int(ld_new), _p(t_dev), int(T), _p(out),
+                                   int(ldo), _p(workspace) if nsplit > 1 else None, nsplit, int(B), int(H), _stream()), "mh_attn_decode")
+    else:
+        check(_L(q).mh_attn_decode_beams(_p(q), int(ldq), _p(k), _p(v), int(ld_b), int(ld_t), _p(kv_new), int(ld_new), _p(t_dev), int(T),
+                                         _p(out), int(ldo), _p(workspace) if nsplit > 1 else None, nsplit, int(B), int(H), kv_group,
+                                         _p(src), src.shape[1] if src is not None else 0, _stream()), "mh_attn_decode_beams")
     return out
 
 
@@ -779,3 +794,45 @@ def greedy_step(logits, V, out_ids, next_ids, finished, state, prompt_len, eos_i
         raise ValueError("greedy_step: shapes disagree")
     check(_lib.load().mh_greedy_step(_p(logits), ldl, int(V), B, _p(out_ids), out_ids.shape[1], _p(next_ids), _p(finished), _p(state),
                                      int(prompt_len), int(eos_id), int(pad_id), _stream()), "mh_greedy_step")
+
+
+BEAM_NEG = -1.0e9
+
+
+def beam_state(B, K, cap, prompt, pad_id, device, src=True):
+    """The device state of mh_beam_step for B images of K beams, at its start values (include/memehip.h): a dict of tensors, rows
+    [image][beam].  prompt: int [B, P] (every beam of an image starts from it); src: also the cache ancestry table."""
+    B, K, cap = int(B), int(K), int(cap)
+    prompt = torch.as_tensor(prompt).to(device=device, dtype=torch.int32)
+    if prompt.dim() != 2 or prompt.shape[0] != B or not 1 <= prompt.shape[1] < cap:
+        raise ValueError("beam_state: prompt must be [B, P] with 1 <= P < cap")
+    if not 2 <= K <= 8:
+        raise ValueError("beam_state: 2 <= K <= 8")
+    R = B * K
+    z = lambda *s, dt=torch.int32: torch.zeros(s, dtype=dt, device=device)
+    run_seq = torch.full((R, cap), int(pad_id), dtype=torch.int32, device=device)
+    run_seq[:, :prompt.shape[1]] = prompt.repeat_interleave(K, 0)
+    run_scores = torch.full((B, K), BEAM_NEG, dtype=F32, device=device)
+    run_scores[:, 0] = 0.0
+    st = dict(B=B, K=K, cap=cap, next_ids=run_seq[:, 0].to(I64).contiguous(), parents=z(R), run_scores=run_scores.view(R), run_seq=run_seq,
+              src=torch.arange(R, dtype=torch.int32, device=device).view(R, 1).repeat(1, cap) if src else None,
+              fin_seq=run_seq.clone(), fin_scores=torch.full((R,), BEAM_NEG, dtype=F32, device=device), fin_flags=z(R), fin_len=z(R),
+              heur=torch.ones(B, dtype=torch.int32, device=device), state=z(4), cand_val=z(R, 2 * K, dt=F32), cand_idx=z(R, 2 * K))
+    st["_c"] = _lib.MhBeamState(**{n: _p(st[n]) for n, _ in _lib.MhBeamState._fields_})
+    return st
+
+
+def beam_step(logits, V, st, prompt_len, length_penalty, early_stopping, eos_id):
+    """mh_beam_step over f32 logits [B * K, ldl] (ldl >= V) on a beam_state: see include/memehip.h."""
+    _chk(logits, F32, "logits")
+    if not isinstance(early_stopping, bool) and early_stopping != "never":
+        raise ValueError("beam_step: early_stopping is False, True or 'never'")
+    B, K, cap = st["B"], st["K"], st["cap"]
+    if logits.dim() != 2 or logits.shape[0] != B * K or not logits.is_contiguous() or V > logits.shape[1]:
+        raise ValueError("beam_step: logits must be a contiguous [B * K, ldl >= V]")
+    for n, _ in _lib.MhBeamState._fields_:
+        if st[n] is not None and getattr(st["_c"], n) != st[n].data_ptr():
+            raise ValueError(f"beam_step: state tensor {n!r} was replaced after beam_state()")
+    es = 1 if early_stopping is True else (2 if early_stopping == "never" else 0)
+    check(_lib.load().mh_beam_step(_p(logits), logits.shape[1], int(V), B, K, C.byref(st["_c"]), cap, int(prompt_len), float(length_penalty),
+                                   es, int(eos_id), _stream()), "mh_beam_step")

@@ -61,6 +61,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dtype", choices=("fp16", "bf16"), default="fp16")
     ap.add_argument("--no-hf", action="store_true", help="skip transformers' generate (e.g. under a profiler)")
+    ap.add_argument("--num-beams", type=int, default=1, help="beam search with this many beams on both sides (1: greedy)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
@@ -69,7 +70,7 @@ def main():
     from multimodal_propaganda_meme_classification_amd import BlipCaptioner, ops
     dev = torch.device("cuda:0")
     cfg = large_config()
-    B, N = args.batch, args.max_new_tokens
+    B, N, K = args.batch, args.max_new_tokens, args.num_beams
     ours = BlipCaptioner.from_config(cfg, compute_dtype=args.dtype, device=dev)
     random_state(ours, args.seed)
     hf = None
@@ -89,9 +90,9 @@ def main():
             if name == "hf_fp16" and hf is None:
                 continue
             if name == "hf_fp16":
-                dt, out = timed(lambda: hf.generate(pixel_values=pix.half(), input_ids=prompt.clone().to(dev), max_new_tokens=N))
+                dt, out = timed(lambda: hf.generate(pixel_values=pix.half(), input_ids=prompt.clone().to(dev), max_new_tokens=N, num_beams=K))
             else:
-                dt, out = timed(lambda: ours.generate(pix, prompt.clone(), max_new_tokens=N, graph=(name == "ours_graph")))
+                dt, out = timed(lambda: ours.generate(pix, prompt.clone(), max_new_tokens=N, graph=(name == "ours_graph"), num_beams=K))
             steps[name] = int(out.shape[1]) - (prompt.shape[1] - 1)          # new tokens in the output
             if r > 0:
                 runs[name].append(dt)
@@ -100,6 +101,12 @@ def main():
     vis = [timed(lambda: ours.vision_forward(pix))[0] for _ in range(3)]
     st = ours._states[next(iter(ours._states))]
     n_rep = 50
+    t_dev = st["sv"] if st["beam"] is None else st["beam"]["state"]
+
+    def rewind():          # beam search: time steps inside the caption (past max_length the beam step has nothing to select)
+        if st["beam"] is not None:
+            t_dev[0] = prompt.shape[1] - 1
+    rewind()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -108,6 +115,7 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     step_graph_ms = e0.elapsed_time(e1) / n_rep
+    rewind()
     e0.record()
     for _ in range(10):
         ours._step(st)
@@ -115,6 +123,7 @@ def main():
     torch.cuda.synchronize()
     step_eager_ms = e0.elapsed_time(e1) / 10
     # launches per token: one per library call of the step, plus the combine launch of every split attention
+    rewind()
     calls = []
     orig = ops.check
     ops.check = lambda status, what: (calls.append(what), orig(status, what))[1]
@@ -124,17 +133,19 @@ def main():
         ops.check = orig
     torch.cuda.synchronize()
     H = cfg.text_config.num_attention_heads
-    splits = sum(1 for c in calls if c == "mh_attn_decode") // 2 * ((ops.decode_splits(B, H, st["cap"]) > 1) + (ops.decode_splits(B, H, st["Ni"]) > 1))
-    launches = len(calls) + splits
+    attn = sum(1 for c in calls if c.startswith("mh_attn_decode"))
+    splits = attn // 2 * ((ops.decode_splits(B * K, H, st["cap"]) > 1) + (ops.decode_splits(B * K, H, st["Ni"]) > 1))
+    launches = len(calls) + splits + (1 if K > 1 else 0)          # mh_beam_step is two launches
 
     def stat(v):
         return {"median_s": sorted(v)[len(v) // 2], "runs_s": [round(x, 4) for x in v]} if v else None
 
-    res = {"metric": "BLIP-large captioning images/s (greedy, fp16 reference)", "batch": B, "max_new_tokens": N, "dtype": args.dtype,
+    res = {"metric": f"BLIP-large captioning images/s ({'greedy' if K == 1 else f'beam search, {K} beams'}, fp16 reference)", "batch": B, "max_new_tokens": N, "dtype": args.dtype,
            "weights": f"random, seed {args.seed}", "gpu": torch.cuda.get_device_name(0)}
     for name, v in runs.items():
         if v:
-            res[name] = dict(stat(v), images_per_s=round(B / stat(v)["median_s"], 2), new_tokens=steps[name])
+            res[name] = dict(stat(v), images_per_s=round(B / stat(v)["median_s"], 2), new_tokens=steps[name],
+                             ms_per_new_token=round(1000 * stat(v)["median_s"] / max(1, steps[name]), 3))
     res["vision_tower_ms"] = round(1000 * sorted(vis)[1], 3)
     res["decode_step_ms_graph"] = round(step_graph_ms, 4)
     res["decode_step_ms_eager"] = round(step_eager_ms, 4)
