@@ -1,4 +1,8 @@
-"""ctypes binding of libmemehip.so (the C ABI declared in include/memehip.h).
+"""ctypes binding of libmemehip.so, read from the C ABI's one declaration: include/memehip.h.
+
+At import a small reader turns the header into this module's attributes -- every ``MH_*`` constant, a ctypes class per
+struct and the argument and return types of every ``mh_*`` entry point -- so a prototype is written once, in C.  The reader
+never skips: a declaration it cannot read stops the import, it does not become a function with ctypes' default int arguments.
 
 The library is built in-tree by ``__graft_entry__.build()`` /
 ``make -C multimodal_propaganda_meme_classification_amd/csrc``.  There is no
@@ -8,252 +12,114 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmemehip.so")            # bf16 storage
 LIB_PATH_F16 = os.path.join(_HERE, "libmemehip_f16.so")    # fp16 storage (same kernels, -DMH_FP16)
 LIB_PATHS = {"bf16": LIB_PATH, "fp16": LIB_PATH_F16}
-
-MH_GEMM_MAX_GROUP = 8
-MH_GEMM_GELU = 1
-MH_GEMM_OUT_F32 = 2
-MH_GEMM_ACCUM = 4
-MH_GEMM_QUICK_GELU = 8
-MH_GEMM_DERIV_AUX = 16
-MH_COLSUM_MAX_JOBS = 64
-MH_LN_MAX_JOBS = 4
-MH_ATTN_MAX_GROUP = 2
-
-c_void_p, c_int, c_int64, c_float = C.c_void_p, C.c_int, C.c_int64, C.c_float
-
-
-class MhGemmProblem(C.Structure):
-    _fields_ = [("A", c_void_p), ("B", c_void_p), ("C", c_void_p), ("bias", c_void_p),
-                ("residual", c_void_p), ("aux", c_void_p), ("mul", c_void_p), ("rowsum", c_void_p),
-                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
-                ("lda", C.c_int32), ("ldb", C.c_int32), ("ldc", C.c_int32),
-                ("flags", C.c_int32), ("alpha", C.c_float),
-                ("drop_rng", c_void_p), ("drop_p", C.c_float), ("drop_stream", C.c_uint32),
-                ("rows_dev", c_void_p), ("drop_rows", c_void_p), ("ksplit", C.c_int32), ("reserved_", C.c_int32)]
-
-
-class MhBeamState(C.Structure):
-    _fields_ = [(n, c_void_p) for n in ("next_ids", "parents", "run_scores", "run_seq", "src", "fin_seq", "fin_scores", "fin_flags",
-                                        "fin_len", "heur", "state", "cand_val", "cand_idx")]
-
-
-class MhColsumJob(C.Structure):
-    _fields_ = [("part", c_void_p), ("out0", c_void_p), ("out1", c_void_p)]
-
-
-class MhConvPackJob(C.Structure):
-    _fields_ = [("w", c_void_p), ("out", c_void_p)] + [(n, C.c_int32) for n in ("Cout", "Cin", "KH", "KW", "Cp", "ldk", "block_start", "reserved_")]
-
-
-class MhConvWgradJob(C.Structure):
-    _fields_ = [("slabs", c_void_p), ("g", c_void_p)] + [(n, C.c_int32) for n in ("Cout", "Cin", "KH", "KW", "Cp", "ldk", "nsplit", "accumulate")] + \
-               [("scale", C.c_float), ("block_start", C.c_int32)]
-
-
-class MhConvGeom(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("B", "H", "W", "C", "KH", "KW", "stride", "pad", "Cout", "ldk")]
-
-
-class MhConvBnBwd(C.Structure):
-    _fields_ = [(n, c_void_p) for n in ("z", "mean", "rstd", "gamma", "beta", "part")] + [("relu", C.c_int32), ("reserved_", C.c_int32),
-                                                                                          ("addend", c_void_p), ("y_mask", c_void_p)]
-
-
-class MhConvWgradProblem(C.Structure):
-    _fields_ = [("dy", c_void_p), ("x", c_void_p), ("slabs", c_void_p), ("ksplit", C.c_int32), ("alpha", C.c_float), ("geom", MhConvGeom)]
-
-
-MH_CONV_MAX_GROUP = 6
-MH_CONV_MAX_JOBS = 64
-MH_BN_RELU, MH_BN_ACCUM_PARAM_GRADS = 1, 2
-
-
-MH_ADAM_MAX_GROUPS = 8
-
-
-class MhAdamSkipGroups(C.Structure):
-    _fields_ = [("hyper", c_void_p * MH_ADAM_MAX_GROUPS), ("beta1", C.c_double * MH_ADAM_MAX_GROUPS), ("beta2", C.c_double * MH_ADAM_MAX_GROUPS),
-                ("n", C.c_int32), ("reserved_", C.c_int32)]
-
-
-class MhLossScale(C.Structure):
-    _fields_ = [("scale", c_void_p), ("growth", c_void_p), ("overflow", c_void_p), ("growth_factor", C.c_float), ("backoff_factor", C.c_float),
-                ("min_scale", C.c_float), ("max_scale", C.c_float), ("growth_interval", C.c_int32), ("base_grad_scale", C.c_float)]
-
-
-class MhLnFwdJob(C.Structure):
-    _fields_ = [(n, c_void_p) for n in ("x", "gamma", "beta", "y", "y_f32", "mean", "rstd")] + \
-               [("rows", C.c_int32), ("eps", C.c_float), ("rows_dev", c_void_p)]
-
-
-class MhLnBwdJob(C.Structure):
-    _fields_ = [(n, c_void_p) for n in ("dy", "x", "gamma", "mean", "rstd", "dx_add", "dx", "part", "dx_drop", "rng")] + \
-               [("n_part", C.c_int32), ("rows", C.c_int32), ("drop_p", C.c_float), ("drop_stream", C.c_uint32),
-                ("rows_dev", c_void_p), ("drop_rows", c_void_p)]
-
-
-class MhAttnProblem(C.Structure):
-    _fields_ = [(n, c_void_p) for n in ("qkv", "key_mask", "out", "lse", "dout", "delta", "dqkv", "cu", "row_map", "rng")] + \
-               [("drop_p", C.c_float), ("drop_stream", C.c_uint32), ("B", C.c_int32), ("S", C.c_int32), ("H", C.c_int32),
-                ("reserved", C.c_int32)]
-
-
-MH_ROWS_MAX_JOBS = 8
-
-
-class MhRowsJob(C.Structure):
-    _fields_ = [(n, c_void_p) for n in ("src", "dst", "idx", "rows_dev")] + \
-               [(n, C.c_int32) for n in ("n", "rows", "D", "stride", "offset", "reserved_")]
-
-
-class MhGemmF32(C.Structure):
-    _fields_ = [("A", c_void_p), ("B", c_void_p), ("C", c_void_p), ("bias", c_void_p)] + \
-               [(n, C.c_int32) for n in ("M", "N", "K", "lda", "ldb", "ldc", "flags")] + \
-               [(n, c_void_p) for n in ("bn_gamma", "bn_beta", "bn_running_mean", "bn_running_var", "bn_save_mean",
-                                        "bn_save_rstd", "bn_z")] + \
-               [("bn_ldz", C.c_int32), ("bn_eps", C.c_float), ("bn_momentum", C.c_float), ("bn_training", C.c_int32)]
-
-
-MH_F32_ACCUM, MH_F32_TANH, MH_F32_RELU, MH_F32_BN = 1, 2, 4, 8
-
-
-class MhHeadParams(C.Structure):
-    _fields_ = [(n, c_void_p) for n in ("Wt", "bt", "Wi", "bi", "Wf", "bf_", "Wo", "bo")]
-
-
-class MhHeadGrads(C.Structure):
-    _fields_ = [(n, c_void_p) for n in ("Wt", "bt", "Wi", "bi", "Wf", "bf_", "Wo", "bo")]
-
-
-# name -> argtypes; every function returns int (MhStatus) unless listed in _RESTYPES
-_PROTOS = {
-    "mh_gemm_bf16_grouped": [C.POINTER(MhGemmProblem), c_int, c_int, c_int, c_void_p],
-    "mh_gemm_set_trace": [c_void_p],
-    "mh_gemm_ksplit_for": [c_int, c_int],
-    "mh_gemm_skinny_eligible": [C.POINTER(MhGemmProblem), c_int, c_int, c_int],
-    "mh_layernorm_fwd": [c_void_p] * 7 + [c_int, c_int, c_float, c_void_p],
-    "mh_layernorm_bwd": [c_void_p] * 8 + [c_int, c_int, c_int, c_void_p, c_void_p, c_float, C.c_uint32, c_void_p],
-    "mh_layernorm_fwd_grouped": [C.POINTER(MhLnFwdJob), c_int, c_int, c_void_p],
-    "mh_layernorm_bwd_grouped": [C.POINTER(MhLnBwdJob), c_int, c_int, c_void_p],
-    "mh_colsum_partials_f32": [C.POINTER(MhColsumJob), c_int, c_int, c_int, c_float, c_void_p],
-    "mh_attn_fwd": [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p, c_float, C.c_uint32, c_void_p],
-    "mh_attn_bwd": [c_void_p] * 7 + [c_int, c_int, c_int, c_void_p, c_float, C.c_uint32, c_void_p],
-    "mh_attn_fwd_grouped": [C.POINTER(MhAttnProblem), c_int, c_void_p],
-    "mh_attn_bwd_grouped": [C.POINTER(MhAttnProblem), c_int, c_void_p],
-    "mh_attn_set_onepass": [c_int],
-    "mh_attn_fwd_packed": [c_void_p] * 6 + [c_int, c_int, c_int, c_void_p, c_float, C.c_uint32, c_void_p],
-    "mh_attn_bwd_packed": [c_void_p] * 9 + [c_int, c_int, c_int, c_void_p, c_float, C.c_uint32, c_void_p],
-    "mh_pack_plan": [c_void_p, c_int, c_int, c_int] + [c_void_p] * 6 + [c_void_p],
-    "mh_pack_rows": [c_void_p] * 4 + [c_int, c_int, c_void_p],
-    "mh_unpack_rows": [c_void_p] * 3 + [c_int, c_int, c_void_p],
-    "mh_rows_gather": [C.POINTER(MhRowsJob), c_int, c_void_p],
-    "mh_rows_scatter_zero": [C.POINTER(MhRowsJob), c_int, c_void_p],
-    "mh_bert_embed_fwd": [c_void_p] * 10 + [c_int, c_int, c_int, c_int, c_float, c_void_p, c_float, C.c_uint32, c_void_p],
-    "mh_image_normalize_u8": [c_void_p, c_void_p, c_int, c_int, c_int, C.POINTER(c_float), C.POINTER(c_float), c_void_p],
-    "mh_image_resample_u8": [c_void_p] * 5 + [c_int] + [c_void_p] * 2 + [c_int] + [c_void_p] * 4 + [c_int] * 5 + [c_void_p],
-    "mh_image_luma_sum_u8": [c_void_p, c_void_p, c_int, c_int, c_void_p],
-    "mh_image_jitter_rotate_u8": [c_void_p] * 5 + [c_int] * 3 + [c_void_p],
-    "mh_dropout_apply": [c_void_p, c_int64, c_void_p, c_float, C.c_uint32, c_void_p],
-    "mh_dropout_mask_u8": [c_void_p, c_int64, c_void_p, c_float, C.c_uint32, c_void_p],
-    "mh_bert_embed_bwd": [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
-    "mh_position_ids_from_input_ids": [c_void_p] * 3 + [c_int] * 4 + [c_void_p],
-    "mh_bert_embed_fwd_pos": [c_void_p] * 10 + [c_int, c_int, c_int, c_int, c_float, c_void_p, c_float, C.c_uint32, c_void_p, c_int,
-                              c_void_p],
-    "mh_embed_pos_bwd": [c_void_p] * 5 + [c_int] * 4 + [c_float, c_void_p],
-    "mh_zero_rows_f32": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mh_patchify": [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
-    "mh_patchify_ld": [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p],
-    "mh_copy2d_u32": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
-    "mh_vit_assemble_fwd": [c_void_p] * 4 + [c_int] * 3 + [c_void_p],
-    "mh_vit_assemble_bwd": [c_void_p] * 4 + [c_int] * 3 + [c_float, c_void_p],
-    "mh_head_fwd": [C.POINTER(MhHeadParams), c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 7 + [c_void_p, c_float, C.c_uint32, c_void_p, c_void_p],
-    "mh_head_bwd": [C.POINTER(MhHeadParams), C.POINTER(MhHeadGrads)] + [c_void_p] * 8 + [c_int] * 8 + [c_float, c_void_p, c_float, C.c_uint32, c_void_p, c_void_p],
-    "mh_pool_fwd": [c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p],
-    "mh_pool_bwd": [c_void_p, c_void_p, c_void_p, c_int] + [c_int] * 5 + [c_float, c_void_p, c_void_p],
-    "mh_bn1d_fwd": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
-                    c_float, c_float, c_int, c_int, c_void_p],
-    "mh_bn1d_bwd": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                    c_void_p, c_int, c_int, c_int, c_void_p],
-    "mh_gemm_f32": [C.POINTER(MhGemmF32), c_int, c_int, c_void_p],
-    "mh_colsum_f32": [c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_void_p],
-    "mh_pool_max_fwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mh_pool_max_bwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mh_pool_mean_fwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mh_pool_mean_bwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mh_pool_attn_fwd": [c_void_p] * 7 + [c_int] * 4 + [c_void_p],
-    "mh_pool_attn_bwd": [c_void_p] * 9 + [c_int] * 4 + [c_void_p],
-    "mh_pad_seq_f32": [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
-    "mh_relu_max_fwd": [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p],
-    "mh_relu_max_bwd": [c_void_p, c_void_p, c_void_p] + [c_int] * 3 + [c_void_p],
-    "mh_conv_fold_f32": [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p],
-    "mh_mca3_fwd": [c_void_p] * 9 + [c_int, c_int, c_void_p],
-    "mh_mca3_bwd": [c_void_p] * 15 + [c_int, c_int, c_void_p],
-    "mh_softmax_gate_fwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
-    "mh_softmax_gate_bwd": [c_void_p] * 5 + [c_int, c_int, c_void_p],
-    "mh_nchw_to_nhwc": [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
-    "mh_im2col_nhwc": [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p],
-    "mh_col2im_nhwc": [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p],
-    "mh_conv_weight_pack": [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p],
-    "mh_conv_weight_unpack": [c_void_p, c_void_p] + [c_int] * 6 + [c_float, c_void_p],
-    "mh_conv_weight_pack_batched": [C.POINTER(MhConvPackJob), c_int, c_void_p],
-    "mh_conv_wgrad_finish_batched": [C.POINTER(MhConvWgradJob), c_int, c_void_p],
-    "mh_conv_splitk": [C.POINTER(MhConvGeom), c_int],
-    "mh_conv_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.POINTER(MhConvGeom), c_void_p],
-    "mh_conv_dgrad": [c_void_p, c_void_p, c_void_p, c_void_p, C.POINTER(MhConvGeom), C.POINTER(MhConvBnBwd), c_void_p],
-    "mh_conv_dgrad_pair": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, C.POINTER(MhConvGeom), C.POINTER(MhConvBnBwd), c_void_p],
-    "mh_bn2d_bwd_parts": [c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_int, c_int, c_float, c_void_p],
-    "mh_conv_wgrad": [c_void_p, c_void_p, c_void_p, c_int, c_float, C.POINTER(MhConvGeom), c_void_p],
-    "mh_conv_wgrad_grouped": [C.POINTER(MhConvWgradProblem), c_int, c_void_p],
-    "mh_bn2d_fwd_parts": [c_void_p, c_void_p, c_int] + [c_void_p] * 8 + [c_int, c_int, c_float, c_float, c_int, c_void_p],
-    "mh_bn2d_workspace_elems": [c_int, c_int],
-    "mh_bn2d_fwd": [c_void_p] * 10 + [c_int, c_int, c_float, c_float, c_int, c_int, c_void_p],
-    "mh_bn2d_apply": [c_void_p] * 7 + [c_int, c_int, c_int, c_void_p],
-    "mh_bn2d_bwd": [c_void_p] * 12 + [c_int, c_int, c_int, c_float, c_void_p],
-    "mh_maxpool_fwd": [c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p],
-    "mh_maxpool_bwd": [c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p],
-    "mh_avgpool_fwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mh_avgpool_bwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p],
-    "mh_add_h16": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
-    "mh_dwconv_weight_pack": [c_void_p, c_void_p, c_int, c_int, c_void_p],
-    "mh_dwconv_nhwc": [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
-    "mh_dwconv_nhwc_dgrad": [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
-    "mh_dwconv_wgrad_workspace_elems": [c_int] * 5,
-    "mh_dwconv_nhwc_wgrad": [c_void_p] * 5 + [c_int] * 5 + [c_float, c_int, c_void_p],
-    "mh_layer_scale_bwd": [c_void_p] * 8 + [c_int, c_int, c_int, c_void_p],
-    "mh_ce_fwd_bwd": [c_void_p] * 5 + [c_int, c_int, c_float, c_void_p, c_void_p],
-    "mh_focal_fwd_bwd": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_void_p, c_void_p],
-    "mh_adam_skip_account": [C.POINTER(MhAdamSkipGroups), c_void_p, c_void_p, c_void_p, C.POINTER(MhLossScale), c_void_p],
-    "mh_sumsq_f32": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
-    "mh_adam_step": [c_void_p] * 5 + [c_int64, c_int64, c_void_p, c_int, c_void_p, c_float, c_float, c_void_p, c_int, c_void_p],
-    "mh_adam_step_rows": [c_void_p] * 6 + [c_int, c_int, c_void_p, c_int, c_void_p, c_float, c_float, c_void_p, c_int, c_void_p],
-    "mh_cast_f32_bf16": [c_void_p, c_void_p, c_int64, c_void_p],
-    "mh_cast_bf16_f32": [c_void_p, c_void_p, c_int64, c_void_p],
-    "mh_sum_shards_16": [c_void_p, c_void_p, c_int, c_int64, c_void_p],
-    "mh_attn_decode": [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                       c_void_p, c_int, c_int, c_int, c_void_p],
-    "mh_attn_decode_beams": [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                             c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
-    "mh_beam_step": [c_void_p, c_int, c_int, c_int, c_int, C.POINTER(MhBeamState), c_int, c_int, c_float, c_int, c_int64, c_void_p],
-    "mh_decode_embed": [c_void_p] * 7 + [c_int] * 4 + [c_float, c_void_p],
-    "mh_greedy_step": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p],
-    "mh_version": [],
-    "mh_status_str": [c_int],
-}
-_RESTYPES = {"mh_version": C.c_char_p, "mh_status_str": C.c_char_p, "mh_bn2d_workspace_elems": c_int64,
-             "mh_dwconv_wgrad_workspace_elems": c_int64}
-
-EXPORTED_SYMBOLS = tuple(_PROTOS)
-
-_libs = {}
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "memehip.h")
 
 
 class MemehipError(RuntimeError):
     pass
+
+
+# The whole type rule.  A pointer to a header struct is POINTER(thatStruct), a returned char pointer is a c_char_p, every other
+# pointer (and a `typedef void* name`) is a c_void_p; _POINTEES are the further names that may only be pointed to.
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint8_t": C.c_uint8,
+            "float": C.c_float, "double": C.c_double}
+_POINTEES = ("void", "char", "unsigned long long")
+_INT = r"-?(?:0[xX][0-9a-fA-F]+|\d+)"
+_DECLARATOR = r"(\**)\s*\b(\w+)\s*(?:\[\s*(\w+)\s*\])?"               # stars, name, array bound
+_TYPED = re.compile(r"((?:\w+\s+)*\w+)\b\s*" + _DECLARATOR)              # type words, then a declarator
+_STATEMENTS = [(kind, re.compile(rx)) for kind, rx in (
+    ("enum", r"typedef\s+enum\s+\w*\s*\{([^{}]*)\}\s*(\w+)\s*;"),
+    ("struct", r"typedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(\w+)\s*;"),
+    ("handle", r"typedef\s+void\s*\*\s*()(\w+)\s*;"),
+    ("proto", r"([\w\s*]+?)\b(mh_\w+)\s*\(([^(){};]*)\)\s*;"))]
+
+
+def read_header(text: str):
+    """C header text -> (constants {name: int}, structs {name: ctypes class}, prototypes {name: (restype, argtypes)}),
+    each in header order.  Raises MemehipError, naming the text, for anything outside the forms and the type rule above."""
+    def fail(why, what):
+        raise MemehipError(f"memehip.h reader: {why}: {' '.join(what.split())!r}")
+
+    consts, structs, handles, protos = {}, {}, {}, {}
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(MH_\w+)\b[ \t]*(.*)$", text, flags=re.M):
+        if not re.fullmatch(_INT, value.strip()) or consts.setdefault(name, int(value, 0)) != int(value, 0):
+            fail("a constant that is not one integer", f"#define {name} {value}")
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    n_calls = len(re.findall(r"mh_\w+\s*\(", text))
+    text, wrapped = re.subn(r'extern\s+"C"\s*\{', " ", text)
+    text = text.strip()
+    if wrapped:
+        text = text[:-1].rstrip() if text.endswith("}") else fail('extern "C" { is not closed at the end', text[-80:])
+
+    def ctype(words, stars, returned=False):
+        base = " ".join(w for w in words.split() if w != "const")
+        if base in structs:
+            return C.POINTER(structs[base]) if stars else structs[base]
+        if stars:
+            if base not in _SCALARS and base not in _POINTEES and base not in handles:
+                fail("a type name outside the rule", words + stars)
+            return C.c_char_p if returned and base == "char" else C.c_void_p
+        if base not in _SCALARS and base not in handles:
+            fail("a type name outside the rule", words)
+        return _SCALARS.get(base, C.c_void_p)
+
+    def fields(body):
+        out = []
+        for stmt in filter(None, (s.strip() for s in body.split(";"))):
+            first, *more = stmt.split(",")
+            m = _TYPED.fullmatch(first.strip()) or fail("a declarator it cannot split", stmt)
+            rest = [re.fullmatch(_DECLARATOR, d.strip()) or fail("a declarator it cannot split", stmt) for d in more]
+            for stars, name, bound in [m.groups()[1:]] + [d.groups() for d in rest]:
+                t = ctype(m.group(1), stars)
+                if bound is not None:
+                    if bound not in consts and not re.fullmatch(_INT, bound):
+                        fail("an array bound that is neither a known constant nor an integer", stmt)
+                    t = t * (consts[bound] if bound in consts else int(bound, 0))
+                out.append((name, t))
+        return out
+
+    pos = 0
+    while pos < len(text):
+        for kind, rx in _STATEMENTS:
+            m = rx.match(text, pos)
+            if m:
+                break
+        else:
+            fail("a declaration it cannot read", text[pos:].split(";")[0][:200])
+        pos, (body, name) = re.compile(r"\s*").match(text, m.end()).end(), m.groups()[:2]
+        if kind == "enum":
+            for item in body.split(","):
+                e = re.fullmatch(rf"\s*(\w+)\s*=\s*({_INT})\s*", item) or fail("an enumerator without an integer value", item)
+                consts[e.group(1)] = int(e.group(2), 0)
+        elif kind == "struct":
+            structs[name] = type(name, (C.Structure,), {"_fields_": fields(body)})
+        elif kind == "handle":
+            handles[name] = C.c_void_p
+        else:
+            r = re.fullmatch(r"((?:\w+\s+)*\w+)\s*(\**)\s*", body) or fail("a prototype it cannot split", m.group(0))
+            args = [] if m.group(3).strip() == "void" else [_TYPED.fullmatch(a.strip()) for a in m.group(3).split(",")]
+            if not all(args) or any(a.group(4) for a in args):
+                fail("a prototype it cannot split", m.group(0))
+            protos[name] = (ctype(r.group(1), r.group(2), returned=True), [ctype(a.group(1), a.group(2)) for a in args])
+    if len(protos) != n_calls:
+        fail(f"{n_calls} times 'mh_name (' but {len(protos)} prototypes", ", ".join(protos))
+    return consts, structs, protos
+
+
+with open(HEADER_PATH) as _f:
+    _CONSTS, _STRUCTS, _SIGNATURES = read_header(_f.read())
+globals().update(_CONSTS)       # MH_GEMM_MAX_GROUP, ..., MH_OK, ...
+globals().update(_STRUCTS)      # MhGemmProblem, ...
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+
+_libs = {}
 
 
 def load(kind: str = "bf16") -> C.CDLL:
@@ -274,10 +140,9 @@ def load(kind: str = "bf16") -> C.CDLL:
             "(python -c 'import __graft_entry__ as g; g.build()' or make -C "
             "multimodal_propaganda_meme_classification_amd/csrc). There is no CPU/PyTorch fallback.")
     lib = C.CDLL(path)
-    for name, argtypes in _PROTOS.items():
+    for name, (restype, argtypes) in _SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError here = header/library drift
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPES.get(name, c_int)
+        fn.restype, fn.argtypes = restype, argtypes
     _libs[kind] = lib
     return lib
 

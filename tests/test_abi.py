@@ -43,7 +43,8 @@ def test_binding_covers_header(lib):
 
 
 def test_struct_layout_matches_header(lib):
-    # 8 pointers + 7 int32 + float + pointer + float + uint32 + 2 pointers = 128 bytes; a drift here would corrupt every grouped launch
+    # 8 pointers + 7 int32 + float + pointer + float + uint32 + 2 pointers + 2 int32 = 136 bytes; a drift here would corrupt every
+    # grouped launch
     assert ctypes.sizeof(lib.MhGemmProblem) == 136
     assert ctypes.sizeof(lib.MhColsumJob) == 24
     assert ctypes.sizeof(lib.MhAttnProblem) == 104
@@ -72,22 +73,99 @@ def test_product_does_not_import_oracle():
 
 
 def test_ctypes_structs_match_the_c_compiler(tmp_path):
-    """Every struct of include/memehip.h, sized by gcc, against its ctypes mirror: a field added on one side only shifts the
-    second element of a job array and fails far from its cause."""
-    import ctypes
+    """Every struct the binding read from include/memehip.h against gcc: its size and the offset of every field.  A field read with
+    the wrong type, or lost, shifts the second element of a job array and fails far from its cause."""
     import subprocess
     from multimodal_propaganda_meme_classification_amd import _lib as lib
-    names = ["MhGemmProblem", "MhColsumJob", "MhLnFwdJob", "MhLnBwdJob", "MhAttnProblem", "MhHeadParams", "MhHeadGrads", "MhGemmF32", "MhConvPackJob", "MhConvWgradJob", "MhConvGeom", "MhConvWgradProblem", "MhConvBnBwd", "MhAdamSkipGroups", "MhLossScale"]
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    structs = {n: v for n, v in vars(lib).items() if isinstance(v, type) and issubclass(v, ctypes.Structure)}
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "memehip.h")).read(), flags=re.S)
+    assert len(structs) == len(re.findall(r"\btypedef\s+struct\b", header)) >= 17      # counted without the reader: none was lost
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include "memehip.h"\nint main(void){' +
-                   "".join(f'printf("{n} %zu\\n", sizeof({n}));' for n in names) + "return 0;}\n")
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "memehip.h"\nint main(void){' +
+                   "".join(f'printf("{n} %zu\\n", sizeof({n}));' +
+                           "".join(f'printf("{n}.{f} %zu\\n", offsetof({n}, {f}));' for f, _ in t._fields_) for n, t in structs.items()) +
+                   "return 0;}\n")
     exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)], check=True)
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
-    sizes = dict(line.split() for line in out.strip().splitlines())
-    for n in names:
-        assert ctypes.sizeof(getattr(lib, n)) == int(sizes[n]), (n, ctypes.sizeof(getattr(lib, n)), sizes[n])
+    want = {k: int(v) for k, v in (line.split() for line in out.strip().splitlines())}
+    got = {n: ctypes.sizeof(t) for n, t in structs.items()}
+    got.update({f"{n}.{f}": getattr(t, f).offset for n, t in structs.items() for f, _ in t._fields_})
+    assert len(got) > 150 and got == want, {k: (got.get(k), want.get(k)) for k in set(got) | set(want) if got.get(k) != want.get(k)}
+
+
+def test_reader_types_against_hand_spelled_lists(lib):
+    """What the binding read from the header for the declarations that are easiest to get wrong, spelled out by hand here."""
+    P, I, I64, F, U32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32
+    handle = lib.load()
+    want = {
+        "mh_adam_step": (I, [P] * 5 + [I64, I64, P, I, P, F, F, P, I, P]),                      # int64_t among ints
+        "mh_attn_decode_beams": (I, [P, I, P, P, I64, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P]),   # int64_t ld_b; ..., src, ld_src, stream
+        "mh_beam_step": (I, [P, I, I, I, I, ctypes.POINTER(lib.MhBeamState), I, I, F, I, I64, P]),
+        "mh_image_resample_u8": (I, [P] * 5 + [I] + [P] * 2 + [I] + [P] * 4 + [I] * 5 + [P]),
+        "mh_image_normalize_u8": (I, [P, P, I, I, I, P, P, P]),
+        "mh_bert_embed_bwd": (I, [P] * 5 + [I, I, I, I, I64, F, P, P, P, P]),
+        "mh_dropout_apply": (I, [P, I64, P, F, U32, P]),
+        "mh_mca3_bwd": (I, [P] * 15 + [I, I, P]),
+        "mh_rows_gather": (I, [ctypes.POINTER(lib.MhRowsJob), I, P]),
+        "mh_version": (ctypes.c_char_p, []),
+        "mh_status_str": (ctypes.c_char_p, [I]),
+        "mh_bn2d_workspace_elems": (I64, [I, I]),
+        "mh_dwconv_wgrad_workspace_elems": (I64, [I] * 5),
+    }
+    for name, (restype, argtypes) in want.items():
+        fn = getattr(handle, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    assert {n for n in lib.EXPORTED_SYMBOLS if getattr(handle, n).restype is not I} == {n for n, (r, _) in want.items() if r is not I}
+    # arrays sized by a constant
+    assert lib.MH_ADAM_MAX_GROUPS == 8
+    assert lib.MhAdamSkipGroups._fields_ == [("hyper", P * 8), ("beta1", ctypes.c_double * 8), ("beta2", ctypes.c_double * 8),
+                                             ("n", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
+    # a struct by value inside another
+    assert lib.MhConvWgradProblem._fields_ == [("dy", P), ("x", P), ("slabs", P), ("ksplit", ctypes.c_int32), ("alpha", F),
+                                               ("geom", lib.MhConvGeom)]
+    assert lib.MhConvGeom._fields_ == [(n, ctypes.c_int32) for n in ("B", "H", "W", "C", "KH", "KW", "stride", "pad", "Cout", "ldk")]
+    # the anonymous typedef, several declarators per statement and several statements per line
+    assert lib.MhRowsJob._fields_ == [(n, P) for n in ("src", "dst", "idx", "rows_dev")] + \
+        [(n, ctypes.c_int32) for n in ("n", "rows", "D", "stride", "offset", "reserved_")]
+    # `const float *Wt, *bt;`: the star belongs to the declarator
+    assert lib.MhHeadParams._fields_ == [(n, P) for n in ("Wt", "bt", "Wi", "bi", "Wf", "bf_", "Wo", "bo")]
+    assert (lib.MH_OK, lib.MH_EINVAL, lib.MH_ESHAPE, lib.MH_ELAUNCH) == (0, 1, 2, 3)
+    assert (lib.MH_GEMM_MAX_GROUP, lib.MH_GEMM_DERIV_AUX, lib.MH_BN_ACCUM_PARAM_GRADS, lib.MH_F32_BN, lib.MH_CONV_MAX_GROUP) == (8, 16, 2, 8, 6)
+    # ops.py hands (c_float * 3) host arrays to mh_image_normalize_u8's two c_void_p arguments
+    assert ctypes.c_void_p.from_param((ctypes.c_float * 3)()) is not None
+
+
+_SMALL_HEADER = """
+#define MH_N 2 /* a bound */
+typedef void* mh_stream_t;
+typedef struct A { const float *v[MH_N], *w; int32_t n, m; } A;
+int mh_x(const A* a /*host*/, int64_t n,
+         mh_stream_t stream);
+"""
+
+
+@pytest.mark.parametrize("bad, named", [
+    ("int mh_y(size_t n);", "size_t"),                                           # a type name outside the rule
+    ("int mh_y(const struct foo* p);", "struct foo"),                            # ... also behind a pointer
+    ("void mh_y(int n);", "void"),                                               # ... and as a return type
+    ("typedef struct B { long n; } B;", "long"),
+    ("typedef struct B { float v[MH_NOPE]; } B;", "MH_NOPE"),                     # an array bound that is no known constant
+    ("typedef struct B { float v[2 * MH_N]; } B;", "v[2 * MH_N]"),               # a declarator it cannot split
+    ("int mh_y(int, float y);", "mh_y"),                                         # a prototype it cannot split
+    ("int mh_y(int (*f)(int));", "mh_y"),
+    ("int mh_x(int n);", "mh_x"),                                                # declared twice: 3 calls, 2 prototypes
+    ("#define MH_M (1 << 3)", "MH_M"),                                           # a constant that is no integer
+    ("static inline int twice(int a) { return a + a; }", "twice"),               # anything that is no declaration it knows
+])
+def test_reader_is_strict(lib, bad, named):
+    """The reader never skips: text it cannot read raises MemehipError naming that text, so the import stops."""
+    consts, structs, protos = lib.read_header(_SMALL_HEADER)
+    assert consts == {"MH_N": 2} and list(protos) == ["mh_x"]
+    assert protos["mh_x"] == (ctypes.c_int, [ctypes.POINTER(structs["A"]), ctypes.c_int64, ctypes.c_void_p])
+    assert structs["A"]._fields_ == [("v", ctypes.c_void_p * 2), ("w", ctypes.c_void_p), ("n", ctypes.c_int32), ("m", ctypes.c_int32)]
+    with pytest.raises(lib.MemehipError, match=re.escape(named)):
+        lib.read_header(_SMALL_HEADER + bad + "\n")
 
 
 def test_isa_guard_bands_hold(lib):

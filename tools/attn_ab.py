@@ -1,21 +1,15 @@
 """Same-box A/B of two builds of the library on the attention forward (boxes differ by +-1.5 %, more than many kernel changes):
 both .so files are loaded in ONE process and timed interleaved.   usage: attn_ab.py <libA.so> <libB.so>"""
-import ctypes as C
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-paths = sys.argv[1:3]
-libs = []
-for p in paths:
-    lib = C.CDLL(os.path.abspath(p))
-    lib.mh_attn_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_uint32,
-                                C.c_void_p]
-    lib.mh_attn_fwd.restype = C.c_int
-    lib.mh_attn_bwd.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p]
-    lib.mh_attn_bwd.restype = C.c_int
-    libs.append(lib)
+# the two builds take the binding's two library slots (the overrides _lib.load() reads): both get the header's argument types
+os.environ["MEMEHIP_LIB"], os.environ["MEMEHIP_LIB_F16"] = (os.path.abspath(p) for p in sys.argv[1:3])
+from multimodal_propaganda_meme_classification_amd import _lib  # noqa: E402
+
+libs = [_lib.load("bf16"), _lib.load("fp16")]
 dev = torch.device("cuda")
 g = torch.Generator(device="cuda").manual_seed(0)
 for (B, S, H) in ((32, 577, 16), (32, 197, 12), (32, 256, 16)):

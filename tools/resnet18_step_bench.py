@@ -30,7 +30,7 @@ def count_launches(pkg, net, step):
     """libmemehip calls of one step (name -> count), by wrapping every mh_* entry point of the handle the tower uses"""
     lib = pkg._lib.load(net.compute_dtype)
     skip = ("mh_conv_splitk", "mh_bn2d_workspace_elems", "mh_gemm_ksplit_for", "mh_status_str", "mh_version")      # host-only queries
-    names = [n for n in pkg._lib._PROTOS if n not in skip]
+    names = [n for n in pkg._lib.EXPORTED_SYMBOLS if n not in skip]
     counts, real = {}, {}
     for n in names:
         real[n] = getattr(lib, n)
