@@ -13,6 +13,9 @@ the way the reference writes it:
 Towers, poolings, Linear+BatchNorm1d+ReLU projections, ConcatAttention3, the focal loss and Adam all run in libmemehip.
 Synthetic inputs (no dataset or checkpoints offline).   python examples/task2c_kevin.py [--full] [--caption-model {bert,roberta}]
                                                                                           [--image-model {vit,resnet18,convnext_tiny}]
+                                                                                          [--accumulation-steps N]
+--accumulation-steps N: gradient accumulation -- every step runs the batch as N micro-batches with loss / N and one
+optimizer.step() behind them (model.set_grad_accumulation(True)).
 --image-model resnet18: the image tower is the submitted model's ``image_model = "resnet18"`` (:82 default; the only family its
 hard-coded ``Linear(512, 512)`` admits) -- resnet.ResNet18 under FineTuneMLP(512, proj), the text tower a TextEncoder of its own.
 --image-model convnext_tiny: the organizers' own image backbone (baselines/extract_feat.py) under the same head --
@@ -36,6 +39,8 @@ def main():
     ap.add_argument("--full", action="store_true")
     ap.add_argument("--caption-model", choices=("bert", "roberta"), default="bert")
     ap.add_argument("--image-model", choices=("vit", "resnet18", "convnext_tiny"), default="vit")
+    ap.add_argument("--accumulation-steps", type=int, default=1,
+                    help="N > 1: every step accumulates the gradients of N micro-batches (the batch in N parts, loss / N)")
     args = ap.parse_args()
     small, roberta, resnet = not args.full, args.caption_model == "roberta", args.image_model == "resnet18"
     convnext = args.image_model == "convnext_tiny"
@@ -78,11 +83,26 @@ def main():
     optimizer = memehip.Adam(model.get_params(lr), lr=lr, max_grad_norm=1.0)      # clip_grad_norm_(model.parameters(), 1.0), fused
     scheduler = memehip.get_linear_schedule_with_warmup(optimizer, num_warmup_steps=2, num_training_steps=10)
     criterion = memehip.SigmoidFocalLoss()
+    N = args.accumulation_steps
+    if N < 1 or B % N:
+        ap.error(f"--accumulation-steps must divide the batch of {B}")
+    if N > 1:       # the HIP towers then add every backward after the first of a window into .grad, as the rest of the model does
+        model.set_grad_accumulation(True)
     for step in range(5):
         optimizer.zero_grad()
-        output = model(*batch)
-        loss = criterion(output, labels, alpha=0.25, gamma=2.0, reduction="mean")
-        loss.backward()
+        if N == 1:
+            output = model(*batch)
+            loss = criterion(output, labels, alpha=0.25, gamma=2.0, reduction="mean")
+            loss.backward()
+        else:
+            losses = []
+            for k in range(N):
+                part = slice(k * (B // N), (k + 1) * (B // N))
+                output = model(*(x[part] for x in batch))
+                micro = criterion(output, labels[part], alpha=0.25, gamma=2.0, reduction="mean")
+                (micro / N).backward()
+                losses.append(micro.detach())
+            loss = torch.stack(losses).mean()
         grad_norm = optimizer.grad_norm()          # clip_grad_norm_(model.parameters(), float("inf")) of the reference's log line
         optimizer.step()
         scheduler.step()

@@ -275,6 +275,14 @@ int mh_bert_embed_bwd(const int64_t* ids, const void* d_pre /*bf16 [T][D]*/, flo
                       /* both NULL, or a persistent id index (restored to INT32_MAX / 0 on return): makes the duplicate-id
                          sum linear in the token count instead of quadratic -- the gathered batch of 8 ranks has 32 768 ids */,
                       mh_stream_t stream);
+/* Gradient accumulation over micro-batches: mh_bert_embed_bwd with dword[id] += (the row sum, rounded to f32 times scale exactly
+ * as mh_bert_embed_bwd stores it) for every row the call touches -- the same first-occurrence owner, the same order, the same
+ * pad-row rule; rows it does not touch are left alone.  dpos / dtype0 are OVERWRITTEN as mh_bert_embed_bwd writes them (the caller
+ * points them at a scratch and adds that with mh_accum_spans_f32). */
+int mh_bert_embed_bwd_accum(const int64_t* ids, const void* d_pre /*bf16 [T][D]*/, float* dword /*[V][D]*/,
+                            float* dpos /*[P][D]*/, float* dtype0 /*[D] or NULL*/, int B, int S, int D,
+                            int vocab, int64_t pad_id, float scale, uint8_t* row_live, int32_t* first_pos, int32_t* id_count,
+                            mh_stream_t stream);
 /* RoBERTa-family embeddings (transformers RobertaEmbeddings: roberta-base, xlm-roberta-base): the same sum and LayerNorm with
  * the position row taken from the input ids,
  *     position_id = pad_id + (non-pad ids of the sequence up to and including the token)     for a non-pad token,
@@ -762,6 +770,18 @@ int mh_cast_bf16_f32(const void* src, float* dst, int64_t n, mh_stream_t stream)
 /* Data-parallel gradient exchange with 16-bit wire format (ddp.GradientReducer(compress="bf16")): out[i] = 16-bit(sum_w
  * in[w][i]) with the sum in fp32 and a fixed order -- the shards received by the all-to-all, accumulated on receipt. */
 int mh_sum_shards_16(const void* in /*[W][shard]*/, void* out /*[shard]*/, int W, int64_t shard, mh_stream_t stream);
+/* Gradient accumulation over micro-batches: the small gradients of a backward (biases, LayerNorm, head, class token, position
+ * and type tables) are written to a scratch mirror of their run of the flat gradient buffer and added into it here, several
+ * spans per launch: dst[i] = dst[i] + src[i] for i < n, ONE f32 add of two stored f32 values per element (never contracted with
+ * anything), 16-byte loads and stores.  dst and src 16-byte aligned, n >= 1 (any: the last 1..3 elements go one by one); spans
+ * must not overlap. */
+#define MH_SPAN_MAX_JOBS 16
+typedef struct MhSpanJob {
+    float* dst;         /* device */
+    const float* src;   /* device */
+    int64_t n;
+} MhSpanJob;
+int mh_accum_spans_f32(const MhSpanJob* jobs /*host*/, int n_jobs, mh_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Autoregressive decode (decode.hip): BLIP image captioning, one new token per row and step

@@ -103,9 +103,31 @@ __global__ __launch_bounds__(256) void bert_embed_fwd_pos_kernel(
                               eps, drop);
 }
 
+// Eight columns of a word-table gradient row.  ADD (gradient accumulation over micro-batches): the sum times `scale` is rounded to
+// f32 exactly as the overwriting store rounds it, then added to what the row holds -- two roundings, never one fused multiply-add
+// (an empty asm statement keeps the product from being contracted into the add).
+template <bool ADD>
+MH_DEV void word_row_store(float* __restrict__ out, const float (&acc)[8], float scale) {
+    if constexpr (ADD) {
+        const f32x4 o0 = *(const f32x4*)out, o1 = *(const f32x4*)(out + 4);
+        float r[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float mine = acc[e] * scale;
+            asm volatile("" : "+v"(mine));      // the rounded product, opaque to the backend: -ffp-contract=fast would fuse it into the add
+            r[e] = (e < 4 ? o0[e] : o1[e - 4]) + mine;
+        }
+        *(f32x4*)out = f32x4{r[0], r[1], r[2], r[3]};
+        *(f32x4*)(out + 4) = f32x4{r[4], r[5], r[6], r[7]};
+    } else {
+        *(f32x4*)out = f32x4{acc[0], acc[1], acc[2], acc[3]} * scale;
+        *(f32x4*)(out + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]} * scale;
+    }
+}
+
 // ---- word-embedding gradient: the first occurrence of an id owns the row and sums all of its
 // duplicates in position order (bitwise reproducible, no atomics) -----------------------------------
-template <int NCH>
+template <int NCH, bool ADD = false>
 __global__ __launch_bounds__(256) void bert_embed_bwd_word_kernel(const int64_t* __restrict__ ids,
                                                                   const h16* __restrict__ d_pre,
                                                                   float* __restrict__ dword, int T, int D,
@@ -152,10 +174,7 @@ __global__ __launch_bounds__(256) void bert_embed_bwd_word_kernel(const int64_t*
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
         const int c = (lane + 64 * i) * 8;
-        if (c < D) {
-            *(f32x4*)(out + c) = f32x4{acc[i][0], acc[i][1], acc[i][2], acc[i][3]} * scale;
-            *(f32x4*)(out + c + 4) = f32x4{acc[i][4], acc[i][5], acc[i][6], acc[i][7]} * scale;
-        }
+        if (c < D) word_row_store<ADD>(out + c, acc[i], scale);
     }
 }
 
@@ -175,7 +194,7 @@ __global__ __launch_bounds__(256) void bert_embed_index_kernel(const int64_t* __
     atomicAdd(&count[id], 1);
 }
 
-template <int NCH>
+template <int NCH, bool ADD = false>
 __global__ __launch_bounds__(256) void bert_embed_bwd_word_indexed_kernel(const int64_t* __restrict__ ids,
                                                                           const h16* __restrict__ d_pre,
                                                                           float* __restrict__ dword, int T, int D,
@@ -250,10 +269,7 @@ __global__ __launch_bounds__(256) void bert_embed_bwd_word_indexed_kernel(const 
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
         const int c = (lane + 64 * i) * 8;
-        if (c < D) {
-            *(f32x4*)(out + c) = f32x4{acc[i][0], acc[i][1], acc[i][2], acc[i][3]} * scale;
-            *(f32x4*)(out + c + 4) = f32x4{acc[i][4], acc[i][5], acc[i][6], acc[i][7]} * scale;
-        }
+        if (c < D) word_row_store<ADD>(out + c, acc[i], scale);
     }
 }
 
@@ -535,27 +551,53 @@ extern "C" int mh_bert_embed_fwd(const int64_t* ids, const float* word, const fl
     return mh_launch_status();
 }
 
-extern "C" int mh_bert_embed_bwd(const int64_t* ids, const void* d_pre, float* dword, float* dpos, float* dtype0,
-                                 int B, int S, int D, int vocab, int64_t pad_id, float scale, uint8_t* row_live,
-                                 int32_t* first_pos, int32_t* id_count, mh_stream_t stream) {
+namespace {
+template <bool ADD>
+int bert_embed_bwd_launch(const int64_t* ids, const void* d_pre, float* dword, float* dpos, float* dtype0, int B, int S, int D,
+                          int vocab, int64_t pad_id, float scale, uint8_t* row_live, int32_t* first_pos, int32_t* id_count,
+                          mh_stream_t stream) {
     if (!ids || !d_pre || !dword || !dpos) return MH_EINVAL;
     if ((first_pos == nullptr) != (id_count == nullptr)) return MH_EINVAL;
     if (B < 1 || S < 1 || D < 8 || (D % 8) || D > 4096 || vocab < 1) return MH_ESHAPE;
     const int T = B * S;
     hipStream_t s = (hipStream_t)stream;
+#define MH_WORD_DISPATCH(NAME, ...)                                          \
+    do {                                                                     \
+        const int nch = (D / 8 + 63) / 64;                                   \
+        if (nch <= 1) hipLaunchKernelGGL((NAME<1, ADD>), __VA_ARGS__);       \
+        else if (nch <= 2) hipLaunchKernelGGL((NAME<2, ADD>), __VA_ARGS__);  \
+        else if (nch <= 4) hipLaunchKernelGGL((NAME<4, ADD>), __VA_ARGS__);  \
+        else hipLaunchKernelGGL((NAME<8, ADD>), __VA_ARGS__);                \
+    } while (0)
     if (first_pos) {
         hipLaunchKernelGGL(bert_embed_index_kernel, dim3((T + 255) / 256), dim3(256), 0, s, ids, T, vocab, pad_id,
                            first_pos, id_count);
-        NCH_DISPATCH(bert_embed_bwd_word_indexed_kernel, dim3((T + 3) / 4), dim3(256), 0, s, ids, (const h16*)d_pre,
-                     dword, T, D, vocab, pad_id, scale, row_live, first_pos, id_count);
+        MH_WORD_DISPATCH(bert_embed_bwd_word_indexed_kernel, dim3((T + 3) / 4), dim3(256), 0, s, ids, (const h16*)d_pre,
+                         dword, T, D, vocab, pad_id, scale, row_live, first_pos, id_count);
     } else {
-        NCH_DISPATCH(bert_embed_bwd_word_kernel, dim3((T + 3) / 4), dim3(256), 0, s, ids, (const h16*)d_pre, dword, T,
-                     D, vocab, pad_id, scale, row_live);
+        MH_WORD_DISPATCH(bert_embed_bwd_word_kernel, dim3((T + 3) / 4), dim3(256), 0, s, ids, (const h16*)d_pre, dword, T,
+                         D, vocab, pad_id, scale, row_live);
     }
+#undef MH_WORD_DISPATCH
     NCH_DISPATCH(sum_over_batch_kernel, dim3(S), dim3(256), 0, s, (const h16*)d_pre, dpos, B, S, D, scale);
     if (dtype0)
         hipLaunchKernelGGL(colsum_rows_f32_kernel, dim3((D + 63) / 64), dim3(256), 0, s, dpos, dtype0, S, D);
     return mh_launch_status();
+}
+}  // namespace
+
+extern "C" int mh_bert_embed_bwd(const int64_t* ids, const void* d_pre, float* dword, float* dpos, float* dtype0,
+                                 int B, int S, int D, int vocab, int64_t pad_id, float scale, uint8_t* row_live,
+                                 int32_t* first_pos, int32_t* id_count, mh_stream_t stream) {
+    return bert_embed_bwd_launch<false>(ids, d_pre, dword, dpos, dtype0, B, S, D, vocab, pad_id, scale, row_live, first_pos,
+                                        id_count, stream);
+}
+
+extern "C" int mh_bert_embed_bwd_accum(const int64_t* ids, const void* d_pre, float* dword, float* dpos, float* dtype0,
+                                       int B, int S, int D, int vocab, int64_t pad_id, float scale, uint8_t* row_live,
+                                       int32_t* first_pos, int32_t* id_count, mh_stream_t stream) {
+    return bert_embed_bwd_launch<true>(ids, d_pre, dword, dpos, dtype0, B, S, D, vocab, pad_id, scale, row_live, first_pos,
+                                       id_count, stream);
 }
 
 extern "C" int mh_bert_embed_fwd_pos(const int64_t* ids, const float* word, const float* pos, const float* type0,

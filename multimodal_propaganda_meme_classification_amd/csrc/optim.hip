@@ -362,6 +362,70 @@ extern "C" int mh_sum_shards_16(const void* in, void* out, int W, int64_t shard,
     return mh_launch_status();
 }
 
+namespace {
+// Gradient accumulation: dst[i] = dst[i] + src[i] over up to MH_SPAN_MAX_JOBS spans in one launch.  A workgroup owns SPAN_TILE
+// consecutive elements of one span (start[] = the first workgroup of each span); every element is read and written by exactly
+// one thread, so the result does not depend on the grid.  One rounded f32 add per element; there is nothing to contract it with.
+constexpr int SPAN_VECS = 4;                        // 16-byte vectors per thread
+constexpr int SPAN_TILE = 256 * 4 * SPAN_VECS;      // elements per workgroup
+struct SpanJobs {
+    float* dst[MH_SPAN_MAX_JOBS];
+    const float* src[MH_SPAN_MAX_JOBS];
+    int64_t n[MH_SPAN_MAX_JOBS];
+    int start[MH_SPAN_MAX_JOBS + 1];
+    int n_jobs;
+};
+__global__ __launch_bounds__(256) void accum_spans_kernel(const SpanJobs J) {
+    int j = 0;
+#pragma unroll
+    for (int i = 1; i < MH_SPAN_MAX_JOBS; ++i)
+        if (i < J.n_jobs && (int)blockIdx.x >= J.start[i]) j = i;
+    float* __restrict__ dst = J.dst[j];
+    const float* __restrict__ src = J.src[j];
+    const int64_t n = J.n[j];
+    const int64_t base = (int64_t)(blockIdx.x - J.start[j]) * SPAN_TILE;
+    f32x4 a[SPAN_VECS], b[SPAN_VECS];
+#pragma unroll
+    for (int k = 0; k < SPAN_VECS; ++k) {           // the loads of a thread are independent: all in flight before the first add
+        const int64_t i = base + ((int64_t)k * 256 + threadIdx.x) * 4;
+        if (i + 4 <= n) {
+            a[k] = *(const f32x4*)(dst + i);
+            b[k] = *(const f32x4*)(src + i);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < SPAN_VECS; ++k) {
+        const int64_t i = base + ((int64_t)k * 256 + threadIdx.x) * 4;
+        if (i + 4 <= n) {
+            *(f32x4*)(dst + i) = a[k] + b[k];
+        } else if (i < n) {                         // the span's last 1..3 elements
+            for (int64_t e = i; e < n; ++e) dst[e] = dst[e] + src[e];
+        }
+    }
+}
+}  // namespace
+
+extern "C" int mh_accum_spans_f32(const MhSpanJob* jobs, int n_jobs, mh_stream_t stream) {
+    if (!jobs || n_jobs < 1 || n_jobs > MH_SPAN_MAX_JOBS) return MH_EINVAL;
+    SpanJobs J = {};
+    J.n_jobs = n_jobs;
+    int64_t blocks = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        if (!jobs[i].dst || !jobs[i].src) return MH_EINVAL;
+        if (((uintptr_t)jobs[i].dst | (uintptr_t)jobs[i].src) & 15) return MH_EINVAL;
+        if (jobs[i].n < 1) return MH_ESHAPE;
+        J.dst[i] = jobs[i].dst;
+        J.src[i] = jobs[i].src;
+        J.n[i] = jobs[i].n;
+        J.start[i] = (int)blocks;
+        blocks += (jobs[i].n + SPAN_TILE - 1) / SPAN_TILE;
+        if (blocks > 0x7fffffff) return MH_ESHAPE;
+    }
+    for (int i = n_jobs; i <= MH_SPAN_MAX_JOBS; ++i) J.start[i] = (int)blocks;
+    hipLaunchKernelGGL(accum_spans_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, J);
+    return mh_launch_status();
+}
+
 extern "C" int mh_cast_bf16_f32(const void* src, float* dst, int64_t n, mh_stream_t stream) {
     if (!src || !dst) return MH_EINVAL;
     if (n < 1 || (((uintptr_t)src | (uintptr_t)dst) & 15)) return MH_ESHAPE;

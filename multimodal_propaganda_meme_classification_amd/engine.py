@@ -24,8 +24,8 @@ from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import (MH_GEMM_DERIV_AUX, MH_GEMM_GELU, MH_GEMM_OUT_F32, MH_GEMM_QUICK_GELU, MhAttnProblem, MhColsumJob, MhGemmProblem, MhHeadGrads,
-                   MhHeadParams, MhLnBwdJob, MhLnFwdJob, MhRowsJob)
+from ._lib import (MH_GEMM_ACCUM, MH_GEMM_DERIV_AUX, MH_GEMM_GELU, MH_GEMM_OUT_F32, MH_GEMM_QUICK_GELU, MhAttnProblem, MhColsumJob, MhGemmProblem,
+                   MhHeadGrads, MhHeadParams, MhLnBwdJob, MhLnFwdJob, MhRowsJob, MhSpanJob)
 from .config import Layout, ModelConfig, check_sequence_length
 
 BF16, F32, I64 = torch.bfloat16, torch.float32, torch.int64
@@ -145,6 +145,11 @@ class Plan:
         self.fwd = Segment("fwd", lib)
         self.loss = Segment("loss", lib)
         self.bwd: List[Segment] = []          # backward segments in execution order
+        # gradient accumulation: the same backward over the same activations and temporaries, ADDING into the flat gradient buffer
+        # (built on first use by Engine.add_flavour, from the arguments the plan was built with; None until then).  The plan keeps
+        # no reference to its builder: a plan must die with its engine by reference count alone -- it owns the activations.
+        self.bwd_add: Optional[List[Segment]] = None
+        self.build_args: Optional[tuple] = None
         self.bucket_after: Dict[str, Tuple[int, int]] = {}   # segment name -> flat grad range complete after it
         self.n_launches = 0
         self.gemm_flops = 0.0                 # algorithmic GEMM FLOPs of one step (fwd + dgrad + wgrad), no row packed away
@@ -178,6 +183,16 @@ class Engine:
         self.word_count = torch.zeros(cfg.text.vocab_size, dtype=torch.int32, device=self.dev)
         # dynamic loss scale read by the fused loss launch (1 = none; a memehip.GradScaler attached to the model owns it)
         self.loss_scale = torch.ones(1, dtype=F32, device=self.dev)
+        # gradient accumulation over micro-batches (model.set_grad_accumulation): a scratch mirror of the small gradients' run of the
+        # flat buffer (n_shadow .. the word table; allocated on first use) and the token ids of every ADDING backward of the
+        # current window, whose word-table rows the first backward of the next window has to clear
+        self.small0 = layout.n_shadow
+        self.small1 = layout.spec[WORD_TABLE].offset
+        self._mirror: Optional[torch.Tensor] = None
+        self._window_ids: List[torch.Tensor] = []
+        # bert position scheme: a backward writes the first S rows of the position-table gradient only; the leading rows that may
+        # be non-zero.  An accumulation window that opens with a shorter sequence clears the rest (before_backward).
+        self._pos_rows = 0
 
     # ---- parameter / gradient views -----------------------------------------------------------------
     def _slice(self, flat: torch.Tensor, name: str, count: int = 1) -> torch.Tensor:
@@ -195,21 +210,63 @@ class Engine:
         assert s.offset + s.numel * count <= self.layout.n_shadow, name
         return self.SH[s.offset:s.offset + s.numel * count]
 
-    def before_backward(self, plan: Plan):
+    def mirror(self) -> torch.Tensor:
+        """Scratch mirror of G[small0:small1]; an adding backward writes its small gradients here (same offsets) and adds them
+        into G with mh_accum_spans_f32.  Elements no kernel writes (alignment gaps) stay zero."""
+        if self._mirror is None:
+            self._mirror = torch.zeros(self.small1 - self.small0, dtype=F32, device=self.dev)
+        return self._mirror
+
+    def _zero_word_rows(self, ids: torch.Tensor):
+        gword = self.g(WORD_TABLE)
+        st = self.lib.mh_zero_rows_f32(ids.data_ptr(), gword.data_ptr(), ids.numel(), self.cfg.text.hidden,
+                                       self.cfg.text.vocab_size, torch.cuda.current_stream().cuda_stream)
+        _lib.check(st, "mh_zero_rows_f32")
+
+    def before_backward(self, plan: Plan, add: bool = False, accumulating: bool = False):
         """Each plan re-zeroes the word-embedding gradient rows IT touched last time (the table gradient is dense,
         only touched rows are ever non-zero).  When the previous backward ran under a different plan (another
-        batch size / sequence length), clear that plan's rows first so no stale row survives the switch."""
+        batch size / sequence length), clear that plan's rows first so no stale row survives the switch.
+        add = True (an adding backward inside an accumulation window): nothing is cleared, whatever plan ran last -- the rows
+        of every micro-batch stay until the first (overwriting) backward of the next window, which clears them here.
+        accumulating = True (that first backward of a window): the rows of the position-table gradient past this plan's
+        sequence length, which a longer micro-batch of the window before wrote, are cleared as well."""
+        if add:
+            self._pos_rows = max(self._pos_rows, plan.S)
+            return
+        if accumulating and self._pos_rows > plan.S and self.cfg.text.position_scheme != "roberta":
+            D = self.cfg.text.hidden
+            self.g(TXT + "embeddings.position_embeddings.weight")[plan.S * D:self._pos_rows * D].zero_()
+            self._pos_rows = plan.S
+        self._pos_rows = max(self._pos_rows, plan.S)
         last = getattr(self, "_last_bwd_plan", None)
         if last is not None and last is not plan:
-            gword = self.g("bert.embeddings.word_embeddings.weight")
             for key in ("prev_ids_all", "prev_ids"):
                 prev = last.buf.get(key)
                 if prev is not None:
-                    st = self.lib.mh_zero_rows_f32(prev.data_ptr(), gword.data_ptr(), prev.numel(), self.cfg.text.hidden,
-                                                   self.cfg.text.vocab_size, torch.cuda.current_stream().cuda_stream)
-                    _lib.check(st, "mh_zero_rows_f32")
+                    self._zero_word_rows(prev)
                     prev.zero_()
+        for ids in self._window_ids:
+            self._zero_word_rows(ids)
+        self._window_ids.clear()
         self._last_bwd_plan = plan
+
+    def add_flavour(self, plan: Plan) -> List[Segment]:
+        """The adding backward of `plan` (gradient accumulation): the plan's own backward, launch for launch over the same
+        activations and temporaries, with the weight gradients added in the GEMM epilogue (MH_GEMM_ACCUM), the word-table rows
+        added by mh_bert_embed_bwd_accum and every small gradient written to the scratch mirror and added by
+        mh_accum_spans_f32 at the end.  Built on first use; the overwriting segments are untouched."""
+        if plan.bwd_add is None:
+            if plan.gather is not None or plan.build_args is None:
+                raise ValueError("memehip: gradient accumulation is not available for a data-parallel plan (gather_world > 0)")
+            # a second builder over the plan's own buffers (found by name): its forward steps only restate which buffer is what
+            # (their launches are dropped), its backward steps emit the adding segments
+            b = _PlanBuilder(self, *plan.build_args, add_to=plan)
+            self._build_steps(b)
+            assert [sg.name for sg in b.pl.bwd_add] == [sg.name for sg in plan.bwd] and not b.pl.bwd
+            plan.keep.append(b.pl.keep)
+            plan.bwd_add = b.pl.bwd_add
+        return plan.bwd_add
 
     # ---- plan ----------------------------------------------------------------------------------------------
     def plan(self, B: int, S: int, training: bool = True, gather_world: int = 0, features=False,
@@ -239,6 +296,14 @@ class Engine:
     def _build(self, B: int, S: int, dropout_on: bool = False, gather_world: int = 0, pack: bool = False,
                features=False, last_rows: str = "pooled") -> Plan:
         b = _PlanBuilder(self, B, S, dropout_on, gather_world, pack, features, last_rows)
+        self._build_steps(b)
+        pl = b.pl
+        pl.build_args = (B, S, dropout_on, gather_world, pack, features, last_rows)
+        pl.n_launches = sum(1 for sg in [pl.fwd, pl.loss] + pl.bwd for c in sg.calls if c[0] is not None)
+        return pl
+
+    @staticmethod
+    def _build_steps(b: "_PlanBuilder"):
         nl = max(b.text.L, b.image.L)
         b.text_embed()
         b.image_embed()
@@ -251,9 +316,6 @@ class Engine:
         for l in range(nl - 1, -1, -1):
             b.bwd_layer(l)
         b.bwd_embed()
-        pl = b.pl
-        pl.n_launches = sum(1 for sg in [pl.fwd, pl.loss] + pl.bwd for c in sg.calls if c[0] is not None)
-        return pl
 
 
 # ---- what a plan is built from: typed jobs, per-layer activations and gradients, one record per tower ------------------
@@ -263,8 +325,8 @@ Site = namedtuple("Site", "rng p sid", defaults=(None, 0.0, 0))
 NO_DROP = Site()
 
 # One problem of a grouped GEMM launch (MhGemmProblem); `drop` = the dropout site of the epilogue.
-Gemm = namedtuple("Gemm", "A B C M N K lda ldb ldc bias residual aux mul rowsum gelu quick deriv_aux alpha drop rows_dev drop_rows",
-                  defaults=(None, None, None, None, None, False, False, False, 1.0, NO_DROP, None, None))
+Gemm = namedtuple("Gemm", "A B C M N K lda ldb ldc bias residual aux mul rowsum gelu quick deriv_aux alpha drop rows_dev drop_rows accum",
+                  defaults=(None, None, None, None, None, False, False, False, 1.0, NO_DROP, None, None, False))
 LnFwd = namedtuple("LnFwd", "x gamma beta y mean rstd rows D eps y32 rows_dev", defaults=(None, None))
 LnBwd = namedtuple("LnBwd", "dy x gamma mean rstd dx part rows D dx_add dx_drop drop rows_dev drop_rows",
                    defaults=(None, None, NO_DROP, None, None))
@@ -360,13 +422,17 @@ def _fill_ln_bwd(e: MhLnBwdJob, j: LnBwd):
 
 
 TXT, IMG = "bert.", "image_model."
+WORD_TABLE = TXT + "embeddings.word_embeddings.weight"
+HEAD_FIELDS = (("Wt", "bert_fc.weight"), ("bt", "bert_fc.bias"), ("Wi", "image_fc.weight"), ("bi", "image_fc.bias"),
+               ("Wf", "fusion_fc.weight"), ("bf_", "fusion_fc.bias"), ("Wo", "output_fc.weight"), ("bo", "output_fc.bias"))
 
 
 class _PlanBuilder:
     """Builds one Plan, step by step in execution order (Engine._build lists the steps).  What the steps share lives here:
     the plan, the two Tower records, the dropout sites and `alloc`."""
 
-    def __init__(self, eng: Engine, B: int, S: int, dropout_on: bool, gather_world: int, pack: bool, features, last_rows: str):
+    def __init__(self, eng: Engine, B: int, S: int, dropout_on: bool, gather_world: int, pack: bool, features, last_rows: str,
+                 add_to: Optional[Plan] = None):
         cfg, t, v = eng.cfg, eng.cfg.text, eng.cfg.image
         check_sequence_length(t, S)
         if B > 1024:
@@ -374,6 +440,14 @@ class _PlanBuilder:
         self.eng, self.cfg, self.B, self.S = eng, cfg, B, S
         self.T16 = eng.T16          # every 16-bit buffer uses the configured storage type
         self.pl = pl = Plan(B, S, eng.lib)
+        # gradient accumulation (add_to = the plan whose adding backward is built, Engine.add_flavour): the steps run over THAT plan's
+        # buffers -- `alloc` hands them back by name, what is new (a scratch of the adding flavour) joins them --, `g` gives the scratch
+        # mirror for the small gradients, and the backward segments go to `pl.bwd_add`
+        self.accum = add_to is not None
+        if add_to is not None:
+            pl.buf, pl.bwd_add = add_to.buf, []
+        self.acc_spans: List[Tuple[int, int]] = []          # (flat offset, elements) written to the mirror by the adding backward
+        self.acc_extra: List[Tuple[torch.Tensor, torch.Tensor]] = []      # further (destination, scratch) pairs added at its end
         self.gather_world, self.last_rows = gather_world, last_rows
         pl.dropout_on, pl.packed, pl.features = dropout_on, pack, features
         self.rng = self.alloc("rng", (4,), torch.int32, zero=True)     # the words every dropout site reads
@@ -386,16 +460,54 @@ class _PlanBuilder:
         self.towers = (self.text, self.image)
 
     def alloc(self, name, shape, dtype=None, zero=False):
+        if self.accum and name in self.pl.buf:
+            tns = self.pl.buf[name]
+            assert tuple(tns.shape) == tuple(shape) and tns.dtype == (dtype or self.T16), name
+            return tns
         tns = (torch.zeros if zero else torch.empty)(shape, dtype=dtype or self.T16, device=self.eng.dev)
         self.pl.buf[name] = tns
         return tns
+
+    def g(self, name, count=1, written: Optional[int] = None) -> torch.Tensor:
+        """Where the backward writes the gradient of `name`: its slice of the flat buffer, or, in the adding flavour, of the
+        scratch mirror for everything between the GEMM matrices and the word table (`written`: the leading elements the
+        backward really writes, when not all).  The matrices and the word table are added to in place."""
+        eng, s = self.eng, self.eng.layout.spec[name]
+        if not self.accum or not (eng.small0 <= s.offset < eng.small1):
+            return eng.g(name, count)
+        n = s.numel * count
+        self.acc_spans.append((s.offset, n if written is None else written))
+        return eng.mirror()[s.offset - eng.small0:s.offset - eng.small0 + n]
+
+    def _accum_spans(self, s: Segment):
+        """End of the adding backward: G[span] += mirror[span] for every span it wrote (adjacent ones merged; the tensors are
+        16-byte aligned and padded to 4 elements, the padding is zero in the mirror), plus the extra scratch pairs."""
+        eng = self.eng
+        merged: List[List[int]] = []
+        for off, n in sorted(set(self.acc_spans)):
+            end = off + (n + 3) // 4 * 4
+            if merged and off <= merged[-1][1]:
+                merged[-1][1] = max(merged[-1][1], end)
+            else:
+                merged.append([off, end])
+        mir = eng.mirror()
+        pairs = [(eng.G[a:min(b, eng.small1)], mir[a - eng.small0:min(b, eng.small1) - eng.small0]) for a, b in merged]
+        pairs += self.acc_extra
+        for i0 in range(0, len(pairs), _lib.MH_SPAN_MAX_JOBS):
+            chunk = pairs[i0:i0 + _lib.MH_SPAN_MAX_JOBS]
+            arr = (MhSpanJob * len(chunk))()
+            for e, (dst, src) in zip(arr, chunk):
+                assert dst.dtype == F32 and src.dtype == F32 and dst.numel() == src.numel() and dst.numel() >= 1
+                e.dst, e.src, e.n = _ptr(dst), _ptr(src), dst.numel()
+            self.pl.keep.append(arr)
+            s.c("mh_accum_spans_f32", arr, len(chunk))
 
     def site(self, p_, sid) -> Site:
         return Site(self.rng.data_ptr(), float(p_), int(sid)) if p_ > 0 else NO_DROP
 
     def seg(self, name) -> Segment:
         s = Segment(name, self.eng.lib)
-        self.pl.bwd.append(s)
+        (self.pl.bwd_add if self.accum else self.pl.bwd).append(s)
         return s
 
     # ---- packers: typed jobs -> one prepared grouped launch --------------------------------------------------
@@ -418,7 +530,9 @@ class _PlanBuilder:
             e.mul, e.rowsum = _ptr(d.mul), _ptr(d.rowsum)
             e.M, e.N, e.K, e.lda, e.ldb, e.ldc = M, N, K, lda, ldb, ldc
             e.flags = (MH_GEMM_GELU if d.gelu else 0) | (MH_GEMM_OUT_F32 if Cm.dtype == F32 else 0) | \
-                      (MH_GEMM_QUICK_GELU if d.quick else 0) | (MH_GEMM_DERIV_AUX if d.deriv_aux else 0)
+                      (MH_GEMM_QUICK_GELU if d.quick else 0) | (MH_GEMM_DERIV_AUX if d.deriv_aux else 0) | \
+                      (MH_GEMM_ACCUM if d.accum else 0)
+            assert not d.accum or Cm.dtype == F32
             e.alpha = float(d.alpha)
             if d.drop.rng is not None:
                 e.drop_rng, e.drop_p, e.drop_stream = d.drop
@@ -456,7 +570,9 @@ class _PlanBuilder:
 
     def _linear_wgrad(self, tw: Tower, l, stem, dy, x, M, N_out, K_in, count=1, **kw) -> Gemm:
         nm = tw.name(l, stem)
-        return self._wgrad_prob(dy, x, self.eng.g(nm + ".weight", count), self.eng.g(nm + ".bias", count), M, N_out, K_in, **kw)
+        # adding flavour: the matrix gradient is added to in the epilogue (the old value is read once, there); the bias gradient
+        # (`rowsum`, overwritten also under MH_GEMM_ACCUM) goes to the mirror
+        return self._wgrad_prob(dy, x, self.g(nm + ".weight", count), self.g(nm + ".bias", count), M, N_out, K_in, accum=self.accum, **kw)
 
     def _ln_fwd_job(self, x, name, y, mean, rstd, rows, D, eps, y32=None, rows_dev=None) -> LnFwd:
         return LnFwd(x, self.eng.p(name + ".weight"), self.eng.p(name + ".bias"), y, mean, rstd, rows, D, float(eps), y32, rows_dev)
@@ -464,7 +580,7 @@ class _PlanBuilder:
     def _ln_bwd_job(self, dy, x, name, mean, rstd, dx, rows, D, dx_add=None, dx_drop=None, drop=NO_DROP, rows_dev=None,
                     drop_rows=None) -> LnBwd:
         part = self.alloc(f"lnpart.{name}.weight", (2, LN_PARTS, D), F32)
-        self.pl._ln_jobs.setdefault(D, []).append((part, self.eng.g(name + ".weight"), self.eng.g(name + ".bias")))
+        self.pl._ln_jobs.setdefault(D, []).append((part, self.g(name + ".weight"), self.g(name + ".bias")))
         on = drop.rng is not None and dx_drop is not None
         return LnBwd(dy, x, self.eng.p(name + ".weight"), mean, rstd, dx, part, rows, D, dx_add, dx_drop if on else None,
                      drop if on else NO_DROP, rows_dev, drop_rows if on else None)
@@ -696,9 +812,7 @@ class _PlanBuilder:
         eng, pl, f, B, alloc, t, v = self.eng, self.pl, self.pl.fwd, self.B, self.alloc, self.text, self.image
         P_, Cn = self.cfg.proj, self.cfg.num_classes
         self.hp, self.hg = MhHeadParams(), MhHeadGrads()
-        for fld, nm in (("Wt", "bert_fc.weight"), ("bt", "bert_fc.bias"), ("Wi", "image_fc.weight"),
-                        ("bi", "image_fc.bias"), ("Wf", "fusion_fc.weight"), ("bf_", "fusion_fc.bias"),
-                        ("Wo", "output_fc.weight"), ("bo", "output_fc.bias")):
+        for fld, nm in HEAD_FIELDS:
             setattr(self.hp, fld, _ptr(eng.p(nm)))
             setattr(self.hg, fld, _ptr(eng.g(nm)))
         pl.keep += [self.hp, self.hg]
@@ -736,7 +850,11 @@ class _PlanBuilder:
             # the built-in head is not part of this graph: its gradient slots must not keep stale values
             h0 = eng.layout.spec["bert_fc.weight"].offset
             h1 = eng.layout.spec["output_fc.bias"].offset + eng.layout.spec["output_fc.bias"].numel
-            head_grads = eng.G[h0:h1]
+            if self.accum:      # adding flavour: zeros in the mirror, added like every other small gradient
+                head_grads = eng.mirror()[h0 - eng.small0:h1 - eng.small0]
+                self.acc_spans.append((h0, h1 - h0))
+            else:
+                head_grads = eng.G[h0:h1]
             s.py(head_grads.zero_)
             if pl.features == "sequence":      # the caller's gradient w.r.t. every hidden state (already times the stream scale)
                 s.c("mh_cast_f32_bf16", _ptr(self.d_seq_t), _ptr(t.d_last), t.T * t.D)
@@ -745,7 +863,13 @@ class _PlanBuilder:
                 s.c("mh_pool_bwd", _ptr(self.d_pooled), _ptr(t.d_last), _ptr(dXf), pool_h, B, S_h, Nt_h, t.D, v.D, float(eng.gscale),
                     _ptr(rows_h))
         else:
-            s.c("mh_head_bwd", C.byref(self.hp), C.byref(self.hg), _ptr(self.dlogits), _ptr(self.pooled), _ptr(self.feat),
+            hg = self.hg
+            if self.accum:
+                hg = MhHeadGrads()
+                for fld, nm in HEAD_FIELDS:
+                    setattr(hg, fld, _ptr(self.g(nm)))
+                pl.keep.append(hg)
+            s.c("mh_head_bwd", C.byref(self.hp), C.byref(hg), _ptr(self.dlogits), _ptr(self.pooled), _ptr(self.feat),
                 _ptr(self.fused), _ptr(dfeat), _ptr(dfused), _ptr(t.d_last), _ptr(dXf), pool_h, B, S_h, Nt_h, t.D, v.D, P_, Cn,
                 float(eng.gscale), *self.site(self.p_head, 7), _ptr(rows_h))
         t.grads, v.grads = self._text_grads(), self._image_grads()
@@ -885,8 +1009,8 @@ class _PlanBuilder:
             d_x0 = alloc("i.dx0pre", (Ti, Di))
             self._ln_bwd(s, [self._ln_bwd_job(tw.d_x(-1), pl.buf["i.x0pre"], IMG + "pre_layernorm", pl.buf["i.mpre"], pl.buf["i.rpre"],
                                               d_x0, Ti, Di)])
-        s.c("mh_vit_assemble_bwd", _ptr(d_x0), _ptr(i_dproj), _ptr(eng.g(IMG + "embeddings.cls_token")),
-            _ptr(eng.g(IMG + "embeddings.position_embeddings")), B, Np, Di, 1.0 / eng.gscale)
+        s.c("mh_vit_assemble_bwd", _ptr(d_x0), _ptr(i_dproj), _ptr(self.g(IMG + "embeddings.cls_token")),
+            _ptr(self.g(IMG + "embeddings.position_embeddings")), B, Np, Di, 1.0 / eng.gscale)
         self._patch_wgrad(s, i_dproj)
         if self.gather_world <= 0:
             self._table_grads(s, self.ids, self.t_dpre, self.prev_ids, B)
@@ -899,6 +1023,8 @@ class _PlanBuilder:
                     arr[j].part, arr[j].out0, arr[j].out1 = _ptr(part), _ptr(o0), _ptr(o1)
                 pl.keep.append(arr)
                 s.c("mh_colsum_partials_f32", arr, len(chunk), LN_PARTS, D, 1.0 / eng.gscale)
+        if self.accum:
+            self._accum_spans(s)
         tail0 = eng.layout.layer_ranges[-1][2]
         if self.gather_world <= 0:
             pl.bucket_after[s.name] = (tail0, eng.layout.n_total)
@@ -912,10 +1038,16 @@ class _PlanBuilder:
         eng, pl, alloc, v, Di = self.eng, self.pl, self.alloc, self.cfg.image, self.image.D
         Kp, Kpp, Tp = v.patch_dim, v.patch_dim_padded, self.B * v.n_patches
         gw = gw_out = eng.g(IMG + "embeddings.patch_embeddings.projection.weight")
-        gb = eng.g(IMG + "embeddings.patch_embeddings.projection.bias") if v.patch_bias else None
+        gb = self.g(IMG + "embeddings.patch_embeddings.projection.bias") if v.patch_bias else None
+        nsplit = min(_lib.MH_GEMM_MAX_GROUP, max(1, Tp // 512))
+        # adding flavour: the plain case adds in the GEMM epilogue; split-K and padded-K finish through mh_colsum_partials_f32 /
+        # mh_copy2d_u32, which overwrite: they finish into a scratch of the weight's size, added at the end of the backward
+        plain_add = self.accum and nsplit == 1 and Kpp == Kp
+        if self.accum and not plain_add:
+            gw = gw_out = alloc("i.dwp_acc", (Di * Kp,), F32)
+            self.acc_extra.append((eng.g(IMG + "embeddings.patch_embeddings.projection.weight"), gw_out))
         if Kpp != Kp:       # the GEMM writes a [Di][Kpp] gradient; its first Kp columns are copied into the flat buffer
             gw = alloc("i.dwp_pad", (Di * Kpp,), F32)
-        nsplit = min(_lib.MH_GEMM_MAX_GROUP, max(1, Tp // 512))
         if nsplit > 1:
             # split-K: the contraction over B*Np patches is cut into `nsplit` grouped problems with their own f32
             # outputs (288 tiles instead of 36), summed in a fixed order by the partial-sum kernel
@@ -940,23 +1072,27 @@ class _PlanBuilder:
                 pl.keep.append(arr)
                 s.c("mh_colsum_partials_f32", arr, 1, nsplit, D_, 1.0)
         else:
-            self._gemm(s, [self._wgrad_prob(i_dproj, self.patches, gw, gb, Tp, Di, Kpp)], True, True)
+            self._gemm(s, [self._wgrad_prob(i_dproj, self.patches, gw, gb, Tp, Di, Kpp, accum=plain_add)], True, True)
         if Kpp != Kp:
             s.c("mh_copy2d_u32", _ptr(gw), Kpp, _ptr(gw_out), Kp, Di, Kp, Kp)
 
     def _table_grads(self, sg: Segment, ids_, dpre_, prev_, nb):
         eng, t, S, Dt = self.eng, self.cfg.text, self.S, self.text.D
-        gword = eng.g(TXT + "embeddings.word_embeddings.weight")
-        gtype0 = eng.g(TXT + "embeddings.token_type_embeddings.weight")[:Dt] if t.type_vocab > 0 else None
-        gpos = eng.g(TXT + "embeddings.position_embeddings.weight")
-        # dense-Adam semantics: the table gradient is dense; only rows touched last step need re-zeroing
-        sg.c("mh_zero_rows_f32", _ptr(prev_), _ptr(gword), nb * S, Dt, t.vocab_size)
         roberta = t.position_scheme == "roberta"
+        gword = eng.g(WORD_TABLE)
+        # (only row 0 of the token-type table and, in the bert scheme, the first S rows of the position table are written)
+        gtype0 = self.g(TXT + "embeddings.token_type_embeddings.weight", written=Dt)[:Dt] if t.type_vocab > 0 else None
+        gpos = self.g(TXT + "embeddings.position_embeddings.weight", written=None if roberta else S * Dt)
+        # dense-Adam semantics: the table gradient is dense; only rows touched last step need re-zeroing.  The adding flavour
+        # clears nothing: it adds its row sums to the rows it touches (untouched rows are zero) and leaves its ids with the engine,
+        # for the first backward of the next window (Engine.before_backward)
+        if not self.accum:
+            sg.c("mh_zero_rows_f32", _ptr(prev_), _ptr(gword), nb * S, Dt, t.vocab_size)
         # roberta scheme: the per-position sums of mh_bert_embed_bwd (which the token-type gradient is made of) go to a scratch,
         # and the position table gets its gradient by table row below
         dpos = self.alloc("t.dpos_by_s", (S, Dt), F32) if roberta else gpos
-        sg.c("mh_bert_embed_bwd", _ptr(ids_), _ptr(dpre_), _ptr(gword), _ptr(dpos), _ptr(gtype0), nb, S, Dt, t.vocab_size,
-             int(t.pad_token_id), 1.0 / eng.gscale, eng.word_row_live.data_ptr(), eng.word_first.data_ptr(),
+        sg.c("mh_bert_embed_bwd_accum" if self.accum else "mh_bert_embed_bwd", _ptr(ids_), _ptr(dpre_), _ptr(gword), _ptr(dpos), _ptr(gtype0),
+             nb, S, Dt, t.vocab_size, int(t.pad_token_id), 1.0 / eng.gscale, eng.word_row_live.data_ptr(), eng.word_first.data_ptr(),
              eng.word_count.data_ptr())
         if roberta:
             pos_inv = self.pos_inv
@@ -968,7 +1104,11 @@ class _PlanBuilder:
             # writes every row of the table gradient (zeros where no token reads the row): nothing to re-zero
             sg.c("mh_embed_pos_bwd", _ptr(dpre_), _ptr(pos_inv), _ptr(gpos), None, None, nb, S, Dt, t.max_position,
                  1.0 / eng.gscale)
-        sg.py(lambda: prev_.copy_(ids_))
+        if self.accum:
+            window = eng._window_ids       # (the list, not the engine: a callback that held the engine would tie plan and engine into a cycle)
+            sg.py(lambda: window.append(ids_.clone()))
+        else:
+            sg.py(lambda: prev_.copy_(ids_))
 
     def _bwd_embed_tables(self, s: Segment, tail0: int):
         """Data parallel: word / position / token-type tables sit at the end of the flat buffer; their gradients

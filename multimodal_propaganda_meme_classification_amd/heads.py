@@ -35,6 +35,23 @@ class _Composite(nn.Module):
     behind reference-style key names): load_state_dict hands every child ITS slice of the checkpoint, so the tower's own
     loader (key translation, 16-bit shadow invalidation) runs instead of nn.Module's recursion into the tower's internals."""
 
+    def _hip_towers(self):
+        return [m for m in self.modules() if isinstance(m, MultimodalClassifier)]
+
+    def set_grad_accumulation(self, on: bool = True):
+        """Gradient accumulation over micro-batches (MultimodalClassifier.set_grad_accumulation) for every HIP transformer tower
+        below this module.  Everything else in a composite -- heads, the ResNet / ConvNeXt towers -- accumulates into ``.grad``
+        already, so with it on the whole module follows torch's rule: add until ``zero_grad()``.  With HF Trainer call it when
+        ``TrainingArguments.gradient_accumulation_steps > 1``."""
+        for m in self._hip_towers():
+            m.set_grad_accumulation(on)
+        return self
+
+    @property
+    def grad_accumulation(self) -> bool:
+        towers = self._hip_towers()
+        return bool(towers) and all(m.grad_accumulation for m in towers)
+
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         missing, unexpected = [], []
         seen = set()

@@ -151,7 +151,7 @@ best_macro_f1 = 0.0          # the reference's module global (Multimodal_example
 def train(model, train_loader, criterion, optimizer, scheduler, device, epoch, scaler=None, image_pipeline: Optional[DeviceImagePipeline] = None,
           max_grad_norm: Optional[float] = None, eval_fn: Optional[Callable] = None, log_every: int = 10, test_df=None, val_df=None,
           stay_in_eval_mode_after_check: bool = True, evaluate_kwargs: Optional[dict] = None,
-          clip_scaled_gradients: Optional[bool] = None) -> Tuple[float, float]:
+          clip_scaled_gradients: Optional[bool] = None, accumulation_steps: int = 1) -> Tuple[float, float]:
     """Multimodal_example_task2C.py:688-776.
 
     ``test_df`` / ``val_df`` (the reference reads them as globals, :756-759): when given, the reference's mid-epoch check runs every
@@ -173,10 +173,20 @@ def train(model, train_loader, criterion, optimizer, scheduler, device, epoch, s
     with no ``unscale_`` before it -- and only then lets ``scaler.step`` divide by the scale (:716).  With torch's scale of 65536 the
     clipped TRUE gradient has norm <= 1.5e-5: the step is a fraction of the learning rate.  True reproduces exactly that (pinned to
     the reference run: tests/golden/ref_kevin_2c_fp16.npz); False unscales first and clips the true gradients, the corrected
-    semantics.  With ``memehip.Adam`` the flag is written to ``optimizer.clip_scaled_gradients``."""
+    semantics.  With ``memehip.Adam`` the flag is written to ``optimizer.clip_scaled_gradients``.
+
+    ``accumulation_steps`` = N > 1: gradient accumulation over windows of N batches -- each batch's loss is divided by N,
+    ``zero_grad()`` runs in front of a window and the clip, ``optimizer.step()`` / ``scaler.step()`` and ``scheduler.step()`` once
+    behind it; the last window of an epoch may be short and steps with what it has.  The model's ``set_grad_accumulation(True)`` is
+    called, and the logged gradient norm is that of the last complete window.  N = 1 is the loop above, call for call."""
     global best_macro_f1
     from .model import Adam
     model.train()
+    N = int(accumulation_steps)
+    if N < 1:
+        raise ValueError(f"accumulation_steps must be >= 1, got {accumulation_steps}")
+    if N > 1 and hasattr(model, "set_grad_accumulation"):       # (a plain torch module accumulates into .grad by itself)
+        model.set_grad_accumulation(True)
     pipe = image_pipeline or DeviceImagePipeline(mode="stretch", augment=True, device=device)
     fused = isinstance(optimizer, Adam)
     if clip_scaled_gradients is None:
@@ -192,29 +202,38 @@ def train(model, train_loader, criterion, optimizer, scheduler, device, epoch, s
     check_interval = max(total_batches // 2, 1)
     window = []
     n_seen = 0
+    grad_norm = None
     for batch_idx, data in enumerate(train_loader, 1):
-        optimizer.zero_grad()
+        opens = (batch_idx - 1) % N == 0                       # this batch opens / closes a window (N = 1: every batch does both)
+        closes = batch_idx % N == 0 or batch_idx == total_batches
+        if opens:
+            optimizer.zero_grad()
         labels = data["label"].to(device).float()
         output = _forward(model, data, device, pipe)
         loss = criterion(output, labels, alpha=0.25, gamma=2.0, reduction="mean")
+        micro_loss = loss if N == 1 else loss / N
         if scaler is not None and hasattr(scaler, "scale"):
-            scaler.scale(loss).backward()                      # :712
+            scaler.scale(micro_loss).backward()                # :712
         else:
-            loss.backward()
-        if fused:
-            grad_norm = optimizer.grad_norm() if (log_every and batch_idx % log_every == 0) else None
-        else:
-            if scaler is not None and hasattr(scaler, "unscale_") and not clip_scaled_gradients:
-                scaler.unscale_(optimizer)                      # corrected semantics: clip the TRUE gradients (the reference clips the scaled ones, :713-715)
-            grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), float("inf"))
-            if max_grad_norm is not None:
-                torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
-        if scaler is not None and hasattr(scaler, "step"):
-            scaler.step(optimizer)
-            scaler.update()
-        else:
-            optimizer.step()
-        scheduler.step()
+            micro_loss.backward()
+        if closes:
+            if fused:
+                if N == 1:
+                    grad_norm = optimizer.grad_norm() if (log_every and batch_idx % log_every == 0) else None
+                elif log_every:
+                    grad_norm = optimizer.grad_norm()          # the window's norm (a device scalar, no synchronisation)
+            else:
+                if scaler is not None and hasattr(scaler, "unscale_") and not clip_scaled_gradients:
+                    scaler.unscale_(optimizer)                  # corrected semantics: clip the TRUE gradients (the reference clips the scaled ones, :713-715)
+                grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), float("inf"))
+                if max_grad_norm is not None:
+                    torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
+            if scaler is not None and hasattr(scaler, "step"):
+                scaler.step(optimizer)
+                scaler.update()
+            else:
+                optimizer.step()
+            scheduler.step()
         loss_sum += loss.detach() * labels.size(0)
         window.append(loss.detach())
         n_seen += labels.size(0)
@@ -227,7 +246,7 @@ def train(model, train_loader, criterion, optimizer, scheduler, device, epoch, s
             avg = float(torch.stack(window).mean())
             window = []
             print(f"TRAIN | Epoch [{epoch}] | Batch [{batch_idx}/{total_batches}] | Loss: {avg:.4f} | LR: {scheduler.get_last_lr()[0]} | "
-                  f"Grad Norm: {float(grad_norm):.4f} |")
+                  f"Grad Norm: {float(grad_norm if grad_norm is not None else float('nan')):.4f} |")
         if batch_idx % check_interval == 0 or batch_idx == total_batches:
             if test_df is not None and val_df is not None:
                 t_loss, t_accuracy, t_macro_f1, t_optimal_threshold = test(model, test_df, criterion, device, epoch, image_pipeline=image_pipeline)

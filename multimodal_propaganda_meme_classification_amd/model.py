@@ -67,7 +67,8 @@ def _check_generation(ctx):
         raise RuntimeError(
             "memehip: backward() of a forward whose activations were overwritten by a later forward of the same shape "
             "(the launch plan keeps ONE set of activations per (batch, seq_len)); run backward before the next forward. "
-            "Gradient accumulation over micro-batches is not supported: every backward overwrites .grad.")
+            "To accumulate gradients over micro-batches call set_grad_accumulation(True) and run each micro-batch's backward "
+            "before the next forward; without it every backward overwrites .grad.")
 
 
 class _ModelFn(torch.autograd.Function):
@@ -294,6 +295,10 @@ class MultimodalClassifier(nn.Module):
         self._shadow_version = -1       # self._P._version the 16-bit shadow was cast from (see weights_changed)
         self._rng_seed, self._rng_step = 0x5EED1234, 0
         self._rng_ring = None
+        # gradient accumulation over micro-batches (set_grad_accumulation): off = every backward overwrites .grad.  On: a backward
+        # overwrites when the gradients were cleared since the previous one (_grads_cleared) and adds otherwise.
+        self._accum = False
+        self._cleared = True
         if init:
             self.reset_parameters(seed)
         self._attach_grads()
@@ -448,13 +453,48 @@ class MultimodalClassifier(nn.Module):
             plan.buf["labels"].copy_(labels.to(torch.int64), non_blocking=True)
         return plan
 
+    # ---- gradient accumulation over micro-batches -------------------------------------------------------------------
+    def set_grad_accumulation(self, on: bool = True):
+        """Opt in to torch's ``.grad`` semantics over micro-batches: with it on, a backward OVERWRITES the gradients when they were
+        cleared since the previous backward -- ``memehip.Adam.zero_grad()``, this module's ``zero_grad()``, or ``.grad is None`` on
+        its parameters (what ``nn.Module.zero_grad()`` on a parent and ``torch.optim.Optimizer.zero_grad()`` leave) -- and ADDS to
+        them otherwise (``zero_grad(set_to_none=False)`` zeroes in place; adding is then right by itself).  The first backward of
+        a window is the overwriting backward, launch for launch; the later ones add the weight gradients in the GEMM epilogue, the
+        word-table rows in place and everything else through one span-add launch (Engine.add_flavour).  The micro-batches of a
+        window may differ in batch size and sequence length; each backward must still run before the next forward of its shape.
+        Off (the default): every backward overwrites.  Switching it on starts a new window.  ``GraphedStep``, ``forward_backward``
+        and the data-parallel reducer hooks refuse a model that has it on."""
+        on = bool(on)
+        if on and not self._accum:
+            self._cleared = True
+        self._accum = on
+        return self
+
+    @property
+    def grad_accumulation(self) -> bool:
+        return self._accum
+
+    def zero_grad(self, set_to_none: bool = True):
+        super().zero_grad(set_to_none=set_to_none)
+        self._cleared = True
+
+    def _grads_cleared(self) -> bool:
+        return self._cleared or self._params[self._names[0]].grad is None or self._params[self._names[-1]].grad is None
+
     def _run_backward(self, plan: Plan, hook=None):
-        self._get_engine().before_backward(plan)
+        eng = self._get_engine()
+        add = self._accum and not self._grads_cleared()
+        if self._accum and hook is not None:
+            raise ValueError("memehip: gradient accumulation is on (set_grad_accumulation): the data-parallel reducer hooks "
+                             "(forward_backward(grad_hook=...)) all-reduce every backward's gradients and are not supported with it")
+        segments = eng.add_flavour(plan) if add else plan.bwd
+        eng.before_backward(plan, add=add, accumulating=self._accum)
         stream = torch.cuda.current_stream().cuda_stream
-        for seg in plan.bwd:
+        for seg in segments:
             seg.run(stream)
             if hook is not None:
                 hook(seg.name, plan.bucket_after.get(seg.name))
+        self._cleared = False
         self._attach_grads()
 
     def forward(self, text: torch.Tensor, image: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
@@ -521,6 +561,13 @@ class MultimodalClassifier(nn.Module):
 
     def forward_backward(self, text, image, mask, labels, grad_hook=None):
         """Returns (loss[1], n_correct[1], logits[B,C]) device tensors; gradients land in .grad."""
+        if self._accum:
+            if grad_hook is not None:
+                raise ValueError("memehip: gradient accumulation is on (set_grad_accumulation): the data-parallel reducer hooks "
+                                 "(forward_backward(grad_hook=...)) all-reduce every backward's gradients and are not supported with it")
+            raise ValueError("memehip: gradient accumulation is on (set_grad_accumulation): forward_backward computes its loss inside "
+                             "the launch plan, where a micro-batch has no weight (loss / N); use the autograd path -- "
+                             "loss = criterion(model(text, image, mask), labels) / N; loss.backward()")
         plan = self._prepare(text, image, mask, labels)
         stream = torch.cuda.current_stream().cuda_stream
         _run_forward(plan)
@@ -582,6 +629,15 @@ class TextEncoder(nn.Module):
     def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
         t, _ = self.inner.encode(input_ids, self._stub_image(input_ids.shape[0], input_ids.device), attention_mask)
         return t
+
+    def set_grad_accumulation(self, on: bool = True):
+        """Gradient accumulation over micro-batches for this tower (MultimodalClassifier.set_grad_accumulation)."""
+        self.inner.set_grad_accumulation(on)
+        return self
+
+    @property
+    def grad_accumulation(self) -> bool:
+        return self.inner.grad_accumulation
 
     def hidden_states(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
         h, _ = self.inner.encode_sequence(input_ids, self._stub_image(input_ids.shape[0], input_ids.device), attention_mask)
@@ -785,18 +841,26 @@ class Adam(torch.optim.Optimizer):
         # every tower gradient is overwritten by the next backward (the embedding table re-zeroes the rows
         # it touched), so there is nothing to clear; the views stay attached.  Heads re-homed by
         # flatten_parameters() receive their gradients from autograd, which ACCUMULATES: zero those buffers.
+        # A tower with gradient accumulation on (set_grad_accumulation) is told that its gradients count as cleared: its next
+        # backward overwrites, the ones after it add.
         if self._flat is not None:
             for f in self._buckets:
                 if f["model"] is None:
                     f["G"].zero_()
+                else:
+                    f["model"]._cleared = True
         else:
             seen = set()
             for g in self.param_groups:
                 for p in g["params"]:
                     sp = p.untyped_storage().data_ptr()
-                    if sp not in seen and sp in _LOOSE:
-                        seen.add(sp)
+                    if sp in seen:
+                        continue
+                    seen.add(sp)
+                    if sp in _LOOSE:
                         _LOOSE[sp].zero_()
+                    elif sp in _REGISTRY:
+                        _REGISTRY[sp]._cleared = True
         return None
 
     @property
@@ -1281,6 +1345,7 @@ class GraphedStep:
                  scaler: Optional["GradScaler"] = None, last_rows: str = "pooled"):
         # last_rows: "pooled" computes, behind the last attention of each tower, only the rows the pooling reads (Engine.plan);
         # "all" every row.  self.plan.last_rows tells which form the step runs.
+        self._refuse_accumulation(model)
         self.model, self.opt = model, optimizer
         optimizer._model = model
         optimizer._resolve_skip(model)
@@ -1345,6 +1410,13 @@ class GraphedStep:
         self.units, self.groups = self._schedule()
         self.closed = False
         _ddp._LIVE_STEPS.add(self)
+
+    @staticmethod
+    def _refuse_accumulation(model):
+        if getattr(model, "grad_accumulation", False):
+            raise ValueError("memehip.GraphedStep: gradient accumulation is on (model.set_grad_accumulation): a captured step is "
+                             "forward + backward + optimizer update of ONE batch; accumulate over micro-batches on the autograd "
+                             "path (loss.backward() per micro-batch, optimizer.step() per window)")
 
     def close(self):
         """Explicit teardown, in dependency order: wait for the device, reset the hipGraphs (last captured first; the data-parallel
@@ -1514,6 +1586,7 @@ class GraphedStep:
         """One step on the batch currently in the static input buffers. Returns (loss, n_correct) device tensors."""
         if self.closed:
             raise RuntimeError("GraphedStep is closed")
+        self._refuse_accumulation(self.model)
         opt = self.opt
         if opt._flat is None:
             self.model._attach_grads()

@@ -16,27 +16,50 @@ import torch
 from .data import id2l, normalize_images
 
 
-def train(model, train_loader, criterion, optimizer, device, sync_every_step: bool = False) -> Tuple[float, float]:
+def train(model, train_loader, criterion, optimizer, device, sync_every_step: bool = False, accumulation_steps: int = 1,
+          scheduler=None) -> Tuple[float, float]:
+    """``accumulation_steps`` = N > 1: gradient accumulation over windows of N batches -- ``zero_grad()`` in front of a window, every
+    batch's loss divided by N, ``optimizer.step()`` (and ``scheduler.step()``, when one is given) once behind it; the last window
+    of an epoch may be short and steps with what it has.  The model's ``set_grad_accumulation(True)`` is called.  N = 1 is the
+    reference's loop, call for call (a scheduler, which the reference's loop does not have, steps after every batch)."""
+    N = int(accumulation_steps)
+    if N < 1:
+        raise ValueError(f"accumulation_steps must be >= 1, got {accumulation_steps}")
     model.train()
+    if N > 1 and hasattr(model, "set_grad_accumulation"):       # (a plain torch module accumulates into .grad by itself)
+        model.set_grad_accumulation(True)
     loss_sum = torch.zeros((), device=device)
     correct = torch.zeros((), device=device, dtype=torch.long)
+    pending = 0          # backwards since the last optimizer step
     for data in train_loader:
-        optimizer.zero_grad()
+        if pending == 0:
+            optimizer.zero_grad()
         text = data["text"].to(device)
         image = normalize_images(data["image"].to(device, non_blocking=True))
         mask = data["text_mask"].to(device)
         labels = data["label"].to(device)
         output = model(text, image, mask)
         loss = criterion(output, labels)
-        loss.backward()
-        optimizer.step()
+        (loss if N == 1 else loss / N).backward()
+        pending += 1
+        if pending == N:
+            pending = _window_step(optimizer, scheduler)
         loss_sum += loss.detach() * labels.size(0)
         _, predicted = torch.max(output.detach(), 1)
         correct += (predicted == labels).sum()
         if sync_every_step:
             loss_sum.item()
+    if pending:          # the epoch's last, short window
+        _window_step(optimizer, scheduler)
     n = len(train_loader.dataset)
     return float(loss_sum) / n, int(correct) / n
+
+
+def _window_step(optimizer, scheduler) -> int:
+    optimizer.step()
+    if scheduler is not None:
+        scheduler.step()
+    return 0
 
 
 def test(model, test_loader, criterion, device) -> Tuple[float, float]:
