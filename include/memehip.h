@@ -854,6 +854,52 @@ int mh_greedy_step(const float* logits, int ldl, int V, int B, int64_t* out_ids,
                    int32_t* finished /*[B]*/, int32_t* state /*[4]*/, int prompt_len, int64_t eos_id, int64_t pad_id,
                    mh_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * SVM (svm.hip): sklearn.svm.SVC(C, kernel='linear') of the organizers' baselines (baselines/subtask_2c.py:61,85,
+ * subtask_2b.py), i.e. libsvm's SMO solver for the C-SVC dual
+ *     minimise 1/2 a^T Q a - e^T a   subject to  0 <= a_t <= C_t,  y^T a = 0,   Q_st = y_s y_t K_st,  K = X X^T
+ * for a batch of P problems that share the labels y and the Gram matrix K and differ in their per-sample bounds Cv [P][n]
+ * (a C grid, class_weight / sample_weight, fold masks: a sample with C_t = 0 never enters the working set and keeps a_t = 0).
+ * K comes from mh_gemm_f32 (A = B = X); coef = (a * y)^T X and the decision values go through mh_gemm_f32 as well.
+ *
+ * Working-set selection WSS2 (Fan, Chen, Lin 2005), gradient G = Q a - e:
+ *     I_up  = {y_t = +1, a_t < C_t} u {y_t = -1, a_t > 0},   I_low = {y_t = +1, a_t > 0} u {y_t = -1, a_t < C_t}
+ *     i = argmax_{I_up} -y_t G_t (= Gmax);   j = argmax_{t in I_low, b_t > 0} b_t^2 / a_t  with  b_t = Gmax + y_t G_t,
+ *     a_t = K_ii + K_tt - 2 K_it (1e-12 when not positive);   ties go to the LOWEST index (libsvm: the highest), so a run is
+ *     deterministic (for j the rule holds up to the rounding of the quotient: the samples one thread owns are ordered by the
+ *     cross-multiplied b_1^2 a_2 > b_2^2 a_1, one division per thread; a near-tie may so pick another j of the same gain to
+ *     within an ulp, which optimality does not see); libsvm's two-variable update with its clipping against C_i and C_j;  stop when
+ *     gap = Gmax - min_{I_low} -y_t G_t < tol.   rho = mean of y_t G_t over the free vectors (0 < a_t < C_t), or the midpoint of
+ *     the two bounds when there is none; samples with C_t = 0 take no part in it.
+ * One workgroup of 1024 threads per problem: alpha and G live in float64 registers, K is f32; n <= MH_SVC_MAX_N (16 samples per
+ * thread), P <= MH_SVC_MAX_PROBLEMS, else MH_ESHAPE.  No unbounded device loop: a launch runs at most `budget` iterations per
+ * problem (MH_SVC_LAUNCH_ITERS is what the package passes), then writes alpha, G and state[p] = {status, iterations so far,
+ * gap, rho} (MH_SVC_STATE doubles) and returns; the caller launches again while a status is MH_SVC_RUNNING -- the buffers are the
+ * whole state, so a launch resumes.  max_iter < 0: no limit; else status MH_SVC_MAXITER once that many iterations are done.
+ *   mh_svc_init : alpha = 0, G = -1, state = {MH_SVC_RUNNING, 0, inf, 0}
+ *   mh_svc_solve: one launch
+ * ------------------------------------------------------------------------------------------ */
+#define MH_SVC_MAX_N 16384
+#define MH_SVC_MAX_PROBLEMS 64
+#define MH_SVC_LAUNCH_ITERS 4096
+#define MH_SVC_STATE 4
+#define MH_SVC_RUNNING 0
+#define MH_SVC_CONVERGED 1
+#define MH_SVC_MAXITER 2
+typedef struct MhSvcProblem {
+    const float* K;      /* f32 [n][ldk] */
+    const float* y;      /* f32 [n], +1 / -1 */
+    const double* Cv;    /* f64 [P][n] */
+    double* alpha;       /* f64 [P][n] */
+    double* G;           /* f64 [P][n] */
+    double* state;       /* f64 [P][MH_SVC_STATE] */
+    int32_t n, ldk, P, budget;
+    int32_t max_iter, reserved_;
+    double tol;
+} MhSvcProblem;
+int mh_svc_init(const MhSvcProblem* p /*host*/, mh_stream_t stream);
+int mh_svc_solve(const MhSvcProblem* p /*host*/, mh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,3 +19,7 @@ from .blip import BlipCaptioner  # noqa: F401
 from .resnet import BasicBlock, Bottleneck, ResNet18, ResNet34, ResNet50, ResNetClassifier, TowerOptions  # noqa: F401
 from .convnext import CNBlock, ConvNeXtTiny  # noqa: F401
 from .features import dump_features, get_features  # noqa: F401
+from . import svm  # noqa: F401
+from .svm import SVC  # noqa: F401
+from . import baselines  # noqa: F401
+from .baselines import run_image_baseline, run_imgbert_baseline  # noqa: F401

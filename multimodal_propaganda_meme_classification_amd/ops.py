@@ -836,3 +836,41 @@ def beam_step(logits, V, st, prompt_len, length_penalty, early_stopping, eos_id)
     es = 1 if early_stopping is True else (2 if early_stopping == "never" else 0)
     check(_lib.load().mh_beam_step(_p(logits), logits.shape[1], int(V), B, K, C.byref(st["_c"]), cap, int(prompt_len), float(length_penalty),
                                    es, int(eos_id), _stream()), "mh_beam_step")
+
+
+# ---------------------------------------------------------------------------------------------
+# SVM (svm.hip): the batched C-SVC solver.  svm.py drives these two.
+# ---------------------------------------------------------------------------------------------
+
+F64 = torch.float64
+
+
+def _svc_problem(K, y, Cv, alpha, G, state, tol, budget, max_iter):
+    """MhSvcProblem over K f32 [n, ldk], y f32 [n], Cv / alpha / G f64 [P, n], state f64 [P, MH_SVC_STATE]; shapes checked here,
+    the limits (n <= MH_SVC_MAX_N, P <= MH_SVC_MAX_PROBLEMS) by the library."""
+    _chk(K, F32, "K"), _chk(y, F32, "y")
+    for name, t in (("Cv", Cv), ("alpha", alpha), ("G", G), ("state", state)):
+        _chk(t, F64, name)
+    if Cv.dim() != 2 or K.dim() != 2:
+        raise ValueError("svc: K is [n, ldk] and Cv is [P, n]")
+    P, n = Cv.shape
+    if K.shape[0] != n or K.shape[1] < n or y.numel() != n or alpha.shape != Cv.shape or G.shape != Cv.shape or \
+            tuple(state.shape) != (P, _lib.MH_SVC_STATE):
+        raise ValueError("svc: K [n, ldk >= n], y [n], Cv / alpha / G [P, n] and state [P, MH_SVC_STATE] do not fit together")
+    p = _lib.MhSvcProblem()
+    p.K, p.y, p.Cv, p.alpha, p.G, p.state = _p(K), _p(y), _p(Cv), _p(alpha), _p(G), _p(state)
+    p.n, p.ldk, p.P, p.budget, p.max_iter, p.tol = n, K.shape[1], P, int(budget), int(max_iter), float(tol)
+    return p
+
+
+def svc_init(K, y, Cv, alpha, G, state):
+    """mh_svc_init: alpha = 0, G = -1, every problem MH_SVC_RUNNING with 0 iterations."""
+    p = _svc_problem(K, y, Cv, alpha, G, state, 1e-3, 1, -1)
+    check(_lib.load().mh_svc_init(C.byref(p), _stream()), "mh_svc_init")
+
+
+def svc_solve(K, y, Cv, alpha, G, state, tol: float = 1e-3, budget: int = _lib.MH_SVC_LAUNCH_ITERS, max_iter: int = -1):
+    """mh_svc_solve: ONE launch of at most ``budget`` SMO iterations per problem; alpha, G and state carry on from where they are.
+    state[p] = {status, iterations so far, gap, rho}: launch again while a status is MH_SVC_RUNNING (svm.solve_batch does)."""
+    p = _svc_problem(K, y, Cv, alpha, G, state, tol, budget, max_iter)
+    check(_lib.load().mh_svc_solve(C.byref(p), _stream()), "mh_svc_solve")
