@@ -191,7 +191,7 @@ class Engine:
         self._mirror: Optional[torch.Tensor] = None
         self._window_ids: List[torch.Tensor] = []
         # bert position scheme: a backward writes the first S rows of the position-table gradient only; the leading rows that may
-        # be non-zero.  An accumulation window that opens with a shorter sequence clears the rest (before_backward).
+        # be non-zero.  An overwriting backward under a shorter sequence clears the rest (before_backward).
         self._pos_rows = 0
 
     # ---- parameter / gradient views -----------------------------------------------------------------
@@ -223,18 +223,19 @@ class Engine:
                                        self.cfg.text.vocab_size, torch.cuda.current_stream().cuda_stream)
         _lib.check(st, "mh_zero_rows_f32")
 
-    def before_backward(self, plan: Plan, add: bool = False, accumulating: bool = False):
+    def before_backward(self, plan: Plan, add: bool = False):
         """Each plan re-zeroes the word-embedding gradient rows IT touched last time (the table gradient is dense,
         only touched rows are ever non-zero).  When the previous backward ran under a different plan (another
         batch size / sequence length), clear that plan's rows first so no stale row survives the switch.
         add = True (an adding backward inside an accumulation window): nothing is cleared, whatever plan ran last -- the rows
         of every micro-batch stay until the first (overwriting) backward of the next window, which clears them here.
-        accumulating = True (that first backward of a window): the rows of the position-table gradient past this plan's
-        sequence length, which a longer micro-batch of the window before wrote, are cleared as well."""
+        Every overwriting backward, accumulating or not, also clears the rows of the position-table gradient past this plan's
+        sequence length, which a longer batch (or a longer micro-batch of the window before) wrote: the absolute scheme writes
+        the first S rows only.  (The roberta scheme writes every row of the table gradient itself.)"""
         if add:
             self._pos_rows = max(self._pos_rows, plan.S)
             return
-        if accumulating and self._pos_rows > plan.S and self.cfg.text.position_scheme != "roberta":
+        if self._pos_rows > plan.S and self.cfg.text.position_scheme != "roberta":
             D = self.cfg.text.hidden
             self.g(TXT + "embeddings.position_embeddings.weight")[plan.S * D:self._pos_rows * D].zero_()
             self._pos_rows = plan.S

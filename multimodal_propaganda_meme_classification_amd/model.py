@@ -488,7 +488,7 @@ class MultimodalClassifier(nn.Module):
             raise ValueError("memehip: gradient accumulation is on (set_grad_accumulation): the data-parallel reducer hooks "
                              "(forward_backward(grad_hook=...)) all-reduce every backward's gradients and are not supported with it")
         segments = eng.add_flavour(plan) if add else plan.bwd
-        eng.before_backward(plan, add=add, accumulating=self._accum)
+        eng.before_backward(plan, add=add)
         stream = torch.cuda.current_stream().cuda_stream
         for seg in segments:
             seg.run(stream)

@@ -257,3 +257,70 @@ def test_blip_large_dimensions_teacher_forced():
     rel = err / float(want.std())
     parity_log(f"blip-large dims teacher-forced logits fp16 (24-layer ViT-L/16 @ 384, 12-layer decoder): max|err|={err:.3e} err/std={rel:.3e}")
     assert rel < 5e-2
+
+
+# ---- history independence of the decode state -----------------------------------------------------------------------------------
+# BlipCaptioner keeps one decode state per (B, cap, K): the self-attention cache (zeroed only at allocation), the cross k / v, the
+# beam ancestry table, and a captured step keyed by (P, num_beams, length_penalty, early_stopping).  A call's result is a function of
+# the weights and its own arguments, never of the call before it.
+
+def _gen_len(row, P):
+    """generated tokens of one returned row up to and including the first eos (the whole tail when there is none)"""
+    hit = (row[P:] == EOS).nonzero().flatten()
+    return int(hit[0]) + 1 if hit.numel() else row.numel() - P
+
+
+def _short_and_long(cfg, sd, dtype, pix, prompt, kw_x, kw_y):
+    """two images whose captions under kw_x are the shortest and two whose captions under kw_y are the longest of the sixteen, found
+    with a captioner of their own; the generated lengths (x, y) come back for the record"""
+    scout = BlipCaptioner.from_config(cfg, compute_dtype=dtype, device=DEV)
+    scout.load_state_dict(sd, strict=True)
+    P = prompt.shape[1] - 1
+    def lengths(kw):        # eight images a call
+        return torch.tensor([_gen_len(r, P) for i in range(0, pix.shape[0], 8)
+                             for r in scout.generate(pix[i:i + 8].to(DEV), prompt[i:i + 8].clone(), max_new_tokens=12, **kw).cpu()])
+
+    lx, ly = lengths(kw_x), lengths(kw_y)
+    parity_log(f"blip history scout {dtype}: generated lengths under X's arguments {lx.tolist()}, under Y's {ly.tolist()}")
+    ix, iy = lx.argsort(stable=True)[:2], ly.argsort(stable=True)[-2:]
+    return ix, iy, lx[ix].tolist(), ly[iy].tolist()
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("case", ["greedy-after-greedy", "beams-after-beams-other-length-penalty", "greedy-after-beams"])
+def test_generate_does_not_depend_on_the_call_before(dtype, case):
+    """generate(Y) then generate(X) on one captioner equals a fresh captioner's generate(X) token for token, and
+    teacher_forced_logits after them equals a fresh captioner's bit for bit.  Y has X's batch size and cap (and, in the first two
+    cases, its beam count: the same decode state) and runs LONGER than X -- asserted from the returned lengths -- so the cache and
+    the sequences hold Y's tokens beyond where X stops.  Beams after beams with another length_penalty re-captures the step."""
+    kw_x, kw_y = {"greedy-after-greedy": ({}, {}),
+                  "beams-after-beams-other-length-penalty": (dict(num_beams=3, length_penalty=1.0), dict(num_beams=3, length_penalty=2.0)),
+                  "greedy-after-beams": ({}, dict(num_beams=3))}[case]
+    cfg = tiny_config()
+    ref = _randomize(BlipForConditionalGeneration(cfg), 0.1, 1, 1.0)
+    sd = ref.state_dict()
+
+    def captioner():
+        c = BlipCaptioner.from_config(cfg, compute_dtype=dtype, device=DEV)
+        c.load_state_dict(sd, strict=True)
+        return c
+
+    pix = _pix(16, 64, seed=21)
+    prompt = torch.tensor([[101, 7, 8, 9, 102]] * 16)
+    ix, iy, len_x, len_y = _short_and_long(cfg, sd, dtype, pix, prompt, kw_x, kw_y)
+    parity_log(f"blip history {case} {dtype}: generated lengths X {len_x} (images {ix.tolist()}), Y {len_y} (images {iy.tolist()})")
+    px, py, p2 = pix[ix].to(DEV), pix[iy].to(DEV), prompt[:2]
+    used, fresh, fresh_tf = captioner(), captioner(), captioner()
+    got_y = used.generate(py, p2.clone(), max_new_tokens=12, **kw_y).cpu()
+    got_x = used.generate(px, p2.clone(), max_new_tokens=12, **kw_x).cpu()
+    want_x = fresh.generate(px, p2.clone(), max_new_tokens=12, **kw_x).cpu()
+    assert got_y.shape[1] > got_x.shape[1], ("Y has to run longer than X", got_y.shape, got_x.shape)
+    assert got_x.shape == want_x.shape and torch.equal(got_x, want_x), (case, got_x.tolist(), want_x.tolist())
+    if not kw_x and not kw_y:
+        assert len(used._states) == 1 and next(iter(used._states))[:2] == (2, 4 + 12), "X and Y share one decode state"
+    # teacher forcing over cap - 1 tokens: the greedy state of (B, cap) again
+    ids = torch.randint(0, 200, (2, 4 + 12 - 1), generator=torch.Generator().manual_seed(6))
+    ids[:, 0] = 150
+    tf_used, tf_fresh = used.teacher_forced_logits(px, ids), fresh_tf.teacher_forced_logits(px, ids)
+    assert tf_used.shape == tf_fresh.shape and torch.equal(tf_used.view(torch.int32), tf_fresh.view(torch.int32))
+    assert bool(torch.isfinite(tf_fresh).all())

@@ -10,9 +10,6 @@ What is asserted, and why it can be asserted bit for bit:
     add), in ``mh_bert_embed_bwd_accum`` (product and sum rounded separately) and in ``mh_accum_spans_f32`` for everything else.
     So ``.grad`` after a window of three micro-batches is ``((g_1 + g_2) + g_3)`` as torch computes it in f32 from the three
     gradients taken alone.  No path of the towers is held to anything weaker.
-
-Each ``g_k`` is taken with the switch off from a zeroed gradient buffer: with the switch off a backward writes only the first S rows
-of the absolute position table's gradient, so after a longer batch the rows past S would still hold that batch's values.
 """
 import os
 
@@ -215,7 +212,8 @@ def _loss(model, crit, features, mb, weight=1.0):
 
 
 def _alone(model, crit, features, mb, weight=1.0):
-    """The micro-batch's gradient with the switch off, from a zeroed buffer (see the module docstring): the whole flat buffer."""
+    """The micro-batch's gradient with the switch off, from a zeroed buffer: the whole flat buffer.  (A step's gradient does not
+    depend on what the buffer held, tests/test_history_independence_gpu.py; the zeroing only keeps this helper self-contained.)"""
     was = model.grad_accumulation
     model.set_grad_accumulation(False)
     model.flat_grads.zero_()
