@@ -345,6 +345,24 @@ int mh_image_resample_u8(const uint8_t* arena, const int64_t* src_off, const int
 int mh_image_luma_sum_u8(const uint8_t* img, unsigned long long* sums, int B, int HW, mh_stream_t stream);
 int mh_image_jitter_rotate_u8(const uint8_t* in, uint8_t* scratch, uint8_t* out, const void* params, unsigned long long* lsum,
                               int B, int H, int W, mh_stream_t stream);
+/* The grayscale path (ResNet_example_task2B.py:158-167: convert("L") -> Resize -> CenterCrop -> ToTensor -> Normalize(mean=[0.45],
+ * std=[0.22])): the L conversion runs on the SOURCE, at its own size, before the resize -- converting after an RGB resize gives other
+ * pixels.  Same arena as mh_image_resample_u8.
+ * mh_image_luma_u8: Pillow's RGB -> L (Convert.c rgb2l), L = (R*19595 + G*38470 + B*7471 + 0x8000) >> 16, of every image of the
+ *   packed arena.  src_off[b] is a multiple of 3 (the images are whole RGB pixels back to back): the L image of b is written as
+ *   uint8 [h][w] at gray + src_off[b] / 3, so gray needs (arena bytes) / 3 bytes.  max_hw >= h * w of every image.
+ * mh_image_resample_l_u8: mh_image_resample_u8 on that one band -- the same windows, coefficients, pass order (`vfirst`), rounding and
+ *   `flip`, src_off STILL the arena's RGB byte offsets (the image is read at gray + src_off[b] / 3);
+ *   tmp uint8 [B][max(max_h * OW, OH * max_w)], out uint8 [B][OH][OW] (= [B][OH][OW][1]).
+ * mh_image_normalize_l_u8: src uint8 [B][H][W] -> dst f32 [B][1][H][W] = (src/255 - mean) / std in torchvision's float32 arithmetic
+ *   (bit-exact); n = B*H*W elements, src 4-byte and dst 16-byte aligned. */
+int mh_image_luma_u8(const uint8_t* arena, const int64_t* src_off, const int32_t* hw, uint8_t* gray, int B, int max_hw,
+                     mh_stream_t stream);
+int mh_image_resample_l_u8(const uint8_t* gray, const int64_t* src_off, const int32_t* hw, const int32_t* xbounds,
+                           const int32_t* xcoef, int KX, const int32_t* ybounds, const int32_t* ycoef, int KY, const uint8_t* flip,
+                           const uint8_t* vfirst, uint8_t* tmp, uint8_t* out, int B, int max_h, int max_w, int OH, int OW,
+                           mh_stream_t stream);
+int mh_image_normalize_l_u8(const uint8_t* src, float* dst, int64_t n, float mean, float std, mh_stream_t stream);
 /* Dropout helpers.  mh_dropout_apply: x[i] *= mask(i)/(1-p) in place (16-bit), e.g. the gradient arriving at a
  * dropped activation.  mh_dropout_mask_u8: the 0/1 mask a site would use for element indices 0..n-1 (tests). */
 int mh_dropout_apply(void* x, int64_t n, const uint32_t* rng, float p, uint32_t stream_id, mh_stream_t stream);

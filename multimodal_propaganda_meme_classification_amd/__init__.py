@@ -16,7 +16,8 @@ from .train import evaluate, test, train  # noqa: F401
 from . import kevin  # noqa: F401
 from .kevin import BlipImageCaptioning, KevinMultimodalDataset, blip_caption_fn, kevin_collate  # noqa: F401
 from .blip import BlipCaptioner  # noqa: F401
-from .resnet import BasicBlock, Bottleneck, ResNet18, ResNet34, ResNet50, ResNetClassifier, TowerOptions  # noqa: F401
+from .resnet import (BasicBlock, Bottleneck, HFResNetForImageClassification, ResNet18, ResNet34, ResNet50, ResNetClassifier,  # noqa: F401
+                     TowerOptions)
 from .convnext import CNBlock, ConvNeXtTiny  # noqa: F401
 from .features import dump_features, get_features  # noqa: F401
 from . import svm  # noqa: F401

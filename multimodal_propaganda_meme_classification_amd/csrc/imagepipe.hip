@@ -8,6 +8,8 @@
 // h > 100 w with a shrinking height, which the host marks per image): the host computes the per-output-pixel windows and integer coefficients with
 // PIL's formulas (data.pil_resample_coeffs), the kernels do the integer sums, so the result equals PIL's bit for bit; the
 // centre crop only restricts which output pixels are computed.  ToTensor + Normalize: mh_image_normalize_u8 (embed.hip).
+//   organizers, Subtask 2B (ResNet_example_task2B.py:158-167): convert("L") -> Resize(256) -> CenterCrop(224) -> ToTensor -> Normalize(0.45, 0.22):
+//   mh_image_luma_u8 on the source, the same two passes on one band (mh_image_resample_l_u8), mh_image_normalize_l_u8.
 #include "common.h"
 
 namespace {
@@ -16,21 +18,24 @@ constexpr int PRECISION_BITS = 22;      // PIL ImagingResample: 32 - 8 - 2
 
 MH_DEV uint8_t clip8(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
-// one 22-bit fixed-point window sum over n pixels `stride` bytes apart, rounded and clipped as ImagingResample does
+// one 22-bit fixed-point window sum over n pixels of NC bands `stride` bytes apart, rounded and clipped as ImagingResample does
+template <int NC>
 MH_DEV void window_sum(const uint8_t* p, size_t stride, const int32_t* k, int n, uint8_t* o) {
-    int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
+    int s[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) s[c] = 1 << (PRECISION_BITS - 1);
     for (int i = 0; i < n; ++i, p += stride) {
-        s0 += p[0] * k[i];
-        s1 += p[1] * k[i];
-        s2 += p[2] * k[i];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) s[c] += p[c] * k[i];
     }
-    o[0] = clip8(s0 >> PRECISION_BITS);
-    o[1] = clip8(s1 >> PRECISION_BITS);
-    o[2] = clip8(s2 >> PRECISION_BITS);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) o[c] = clip8(s[c] >> PRECISION_BITS);
 }
 // first pass.  Horizontal (the usual order): tmp[b][y][xo][c] = clip8((2^21 + sum_k src[b][y][x0 + k][c] * xcoef[b][xo][k]) >> 22),
 // y < h_b.  An image with vfirst[b] set takes the vertical pass first, as Image.resize does for h > 100 w when the height shrinks:
 // tmp[b][yo][x][c] = clip8((2^21 + sum_k src[b][y0 + k][x][c] * ycoef[b][yo][k]) >> 22), x < w_b.  Each image owns tstride bytes of tmp.
+// NC = 3: RGB; NC = 1: the L band mh_image_luma_u8 left, image b at a third of its RGB byte offset.
+template <int NC>
 __global__ __launch_bounds__(256) void resample_pass1_kernel(const uint8_t* __restrict__ arena, const int64_t* __restrict__ src_off,
                                                              const int32_t* __restrict__ hw, const int32_t* __restrict__ xbounds,
                                                              const int32_t* __restrict__ xcoef, int KX, const int32_t* __restrict__ ybounds,
@@ -39,22 +44,23 @@ __global__ __launch_bounds__(256) void resample_pass1_kernel(const uint8_t* __re
     const int b = blockIdx.y;
     const int h = hw[2 * b], w = hw[2 * b + 1];
     const int idx = blockIdx.x * 256 + threadIdx.x;
-    const uint8_t* src = arena + src_off[b];
+    const uint8_t* src = arena + src_off[b] / (3 / NC);
     if (vfirst && vfirst[b]) {
         if (idx >= OH * w) return;
         const int yo = idx / w, x = idx % w;
         const int y0 = ybounds[((size_t)b * OH + yo) * 2], n = ybounds[((size_t)b * OH + yo) * 2 + 1];
-        window_sum(src + ((size_t)y0 * w + x) * 3, (size_t)w * 3, ycoef + ((size_t)b * OH + yo) * KY, n,
-                   tmp + (size_t)b * tstride + ((size_t)yo * w + x) * 3);
+        window_sum<NC>(src + ((size_t)y0 * w + x) * NC, (size_t)w * NC, ycoef + ((size_t)b * OH + yo) * KY, n,
+                       tmp + (size_t)b * tstride + ((size_t)yo * w + x) * NC);
         return;
     }
     if (idx >= h * OW) return;
     const int y = idx / OW, xo = idx % OW;
     const int x0 = xbounds[((size_t)b * OW + xo) * 2], n = xbounds[((size_t)b * OW + xo) * 2 + 1];
-    window_sum(src + ((size_t)y * w + x0) * 3, 3, xcoef + ((size_t)b * OW + xo) * KX, n,
-               tmp + (size_t)b * tstride + ((size_t)y * OW + xo) * 3);
+    window_sum<NC>(src + ((size_t)y * w + x0) * NC, NC, xcoef + ((size_t)b * OW + xo) * KX, n,
+                   tmp + (size_t)b * tstride + ((size_t)y * OW + xo) * NC);
 }
 // second pass, the other axis (+ optional horizontal flip of the OUTPUT): out[b][yo][xo][c]
+template <int NC>
 __global__ __launch_bounds__(256) void resample_pass2_kernel(const uint8_t* __restrict__ tmp, const int32_t* __restrict__ hw,
                                                              const int32_t* __restrict__ xbounds, const int32_t* __restrict__ xcoef, int KX,
                                                              const int32_t* __restrict__ ybounds, const int32_t* __restrict__ ycoef, int KY,
@@ -65,20 +71,44 @@ __global__ __launch_bounds__(256) void resample_pass2_kernel(const uint8_t* __re
     if (idx >= OH * OW) return;
     const int yo = idx / OW, xo = idx % OW;
     const int xd = (flip && flip[b]) ? OW - 1 - xo : xo;
-    uint8_t* o = out + (((size_t)b * OH + yo) * OW + xd) * 3;
+    uint8_t* o = out + (((size_t)b * OH + yo) * OW + xd) * NC;
     const uint8_t* t = tmp + (size_t)b * tstride;
     if (vfirst && vfirst[b]) {
         const int w = hw[2 * b + 1];
         const int x0 = xbounds[((size_t)b * OW + xo) * 2], n = xbounds[((size_t)b * OW + xo) * 2 + 1];
-        window_sum(t + ((size_t)yo * w + x0) * 3, 3, xcoef + ((size_t)b * OW + xo) * KX, n, o);
+        window_sum<NC>(t + ((size_t)yo * w + x0) * NC, NC, xcoef + ((size_t)b * OW + xo) * KX, n, o);
         return;
     }
     const int y0 = ybounds[((size_t)b * OH + yo) * 2], n = ybounds[((size_t)b * OH + yo) * 2 + 1];
-    window_sum(t + ((size_t)y0 * OW + xo) * 3, (size_t)OW * 3, ycoef + ((size_t)b * OH + yo) * KY, n, o);
+    window_sum<NC>(t + ((size_t)y0 * OW + xo) * NC, (size_t)OW * NC, ycoef + ((size_t)b * OH + yo) * KY, n, o);
 }
 
 // PIL "L" conversion of an RGB pixel (ImagingConvert rgb2l): (R*19595 + G*38470 + B*7471 + 0x8000) >> 16
 MH_DEV int luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
+// convert("L") of every image of the packed arena, at its own size: gray[src_off[b] / 3 + i] = luma(pixel i of image b)
+__global__ __launch_bounds__(256) void luma_kernel(const uint8_t* __restrict__ arena, const int64_t* __restrict__ src_off,
+                                                   const int32_t* __restrict__ hw, uint8_t* __restrict__ gray) {
+    const int b = blockIdx.y;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= hw[2 * b] * hw[2 * b + 1]) return;
+    const uint8_t* p = arena + src_off[b] + (size_t)idx * 3;
+    gray[src_off[b] / 3 + idx] = (uint8_t)luma(p[0], p[1], p[2]);
+}
+// ToTensor + Normalize of one band: (x / 255 - mean) / std, the float32 operations of torchvision in their order (IEEE division)
+__global__ __launch_bounds__(256) void normalize_l_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, size_t n, float mean,
+                                                          float sd) {
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;      // four pixels: one 4-byte load, one 16-byte store
+    if (i >= n) return;
+    if (i + 4 <= n) {
+        const uint32_t v = *(const uint32_t*)(src + i);
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = ((float)((v >> (8 * k)) & 0xFF) / 255.0f - mean) / sd;
+        *(f32x4*)(dst + i) = o;
+        return;
+    }
+    for (size_t j = i; j < n; ++j) dst[j] = ((float)src[j] / 255.0f - mean) / sd;
+}
 // PIL Image.blend(im1, im2, alpha) on one band: truncating cast inside [0, 1], clipped outside
 MH_DEV int blend8(int a, int b, float alpha) {
     // ImagingBlend: float temp = in1 + alpha * (in2 - in1): a product rounded to float, then a sum rounded to float.  The build's
@@ -211,19 +241,51 @@ __global__ __launch_bounds__(256) void jitter_rotate_kernel(const uint8_t* __res
 
 }  // namespace
 
-extern "C" int mh_image_resample_u8(const uint8_t* arena, const int64_t* src_off, const int32_t* hw, const int32_t* xbounds,
-                                    const int32_t* xcoef, int KX, const int32_t* ybounds, const int32_t* ycoef, int KY,
-                                    const uint8_t* flip, const uint8_t* vfirst, uint8_t* tmp, uint8_t* out, int B, int max_h, int max_w,
-                                    int OH, int OW, mh_stream_t stream) {
+namespace {
+template <int NC>
+int resample_launch(const uint8_t* arena, const int64_t* src_off, const int32_t* hw, const int32_t* xbounds, const int32_t* xcoef, int KX,
+                    const int32_t* ybounds, const int32_t* ycoef, int KY, const uint8_t* flip, const uint8_t* vfirst, uint8_t* tmp,
+                    uint8_t* out, int B, int max_h, int max_w, int OH, int OW, mh_stream_t stream) {
     if (!arena || !src_off || !hw || !xbounds || !xcoef || !ybounds || !ycoef || !tmp || !out) return MH_EINVAL;
     if (B < 1 || max_h < 1 || OH < 1 || OW < 1 || KX < 1 || KY < 1 || max_w < (vfirst ? 1 : 0)) return MH_ESHAPE;
     hipStream_t s = (hipStream_t)stream;
     // per image: [max_h][OW] pixels (horizontal pass first) or [OH][max_w] (vertical pass first), whichever is larger
     const size_t px1 = (size_t)max_h * OW, px1v = vfirst ? (size_t)OH * max_w : 0, px = px1 > px1v ? px1 : px1v;
-    hipLaunchKernelGGL(resample_pass1_kernel, dim3((unsigned)((px + 255) / 256), B), dim3(256), 0, s, arena, src_off, hw, xbounds, xcoef, KX,
-                       ybounds, ycoef, KY, vfirst, tmp, px * 3, OH, OW);
-    hipLaunchKernelGGL(resample_pass2_kernel, dim3((OH * OW + 255) / 256, B), dim3(256), 0, s, tmp, hw, xbounds, xcoef, KX, ybounds, ycoef,
-                       KY, vfirst, flip, out, px * 3, OH, OW);
+    hipLaunchKernelGGL(resample_pass1_kernel<NC>, dim3((unsigned)((px + 255) / 256), B), dim3(256), 0, s, arena, src_off, hw, xbounds, xcoef, KX,
+                       ybounds, ycoef, KY, vfirst, tmp, px * NC, OH, OW);
+    hipLaunchKernelGGL(resample_pass2_kernel<NC>, dim3((OH * OW + 255) / 256, B), dim3(256), 0, s, tmp, hw, xbounds, xcoef, KX, ybounds, ycoef,
+                       KY, vfirst, flip, out, px * NC, OH, OW);
+    return mh_launch_status();
+}
+}  // namespace
+
+extern "C" int mh_image_resample_u8(const uint8_t* arena, const int64_t* src_off, const int32_t* hw, const int32_t* xbounds,
+                                    const int32_t* xcoef, int KX, const int32_t* ybounds, const int32_t* ycoef, int KY,
+                                    const uint8_t* flip, const uint8_t* vfirst, uint8_t* tmp, uint8_t* out, int B, int max_h, int max_w,
+                                    int OH, int OW, mh_stream_t stream) {
+    return resample_launch<3>(arena, src_off, hw, xbounds, xcoef, KX, ybounds, ycoef, KY, flip, vfirst, tmp, out, B, max_h, max_w, OH, OW, stream);
+}
+
+extern "C" int mh_image_luma_u8(const uint8_t* arena, const int64_t* src_off, const int32_t* hw, uint8_t* gray, int B, int max_hw,
+                                mh_stream_t stream) {
+    if (!arena || !src_off || !hw || !gray) return MH_EINVAL;
+    if (B < 1 || max_hw < 1) return MH_ESHAPE;
+    hipLaunchKernelGGL(luma_kernel, dim3((unsigned)((max_hw + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, arena, src_off, hw, gray);
+    return mh_launch_status();
+}
+
+extern "C" int mh_image_resample_l_u8(const uint8_t* gray, const int64_t* src_off, const int32_t* hw, const int32_t* xbounds,
+                                      const int32_t* xcoef, int KX, const int32_t* ybounds, const int32_t* ycoef, int KY,
+                                      const uint8_t* flip, const uint8_t* vfirst, uint8_t* tmp, uint8_t* out, int B, int max_h, int max_w,
+                                      int OH, int OW, mh_stream_t stream) {
+    return resample_launch<1>(gray, src_off, hw, xbounds, xcoef, KX, ybounds, ycoef, KY, flip, vfirst, tmp, out, B, max_h, max_w, OH, OW, stream);
+}
+
+extern "C" int mh_image_normalize_l_u8(const uint8_t* src, float* dst, int64_t n, float mean, float sd, mh_stream_t stream) {
+    if (!src || !dst) return MH_EINVAL;
+    if (n < 1 || n >= (1ll << 40)) return MH_ESHAPE;
+    if (((uintptr_t)src & 3) || ((uintptr_t)dst & 15)) return MH_EINVAL;
+    hipLaunchKernelGGL(normalize_l_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, src, dst, (size_t)n, mean, sd);
     return mh_launch_status();
 }
 

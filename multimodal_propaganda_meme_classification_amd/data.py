@@ -243,6 +243,13 @@ def resample_u8_reference(img: np.ndarray, bx, cx, by, cy, vertical_first: bool 
     return horizontal(vertical(img)) if vertical_first else vertical(horizontal(img))
 
 
+def luma_u8_reference(rgb: np.ndarray) -> np.ndarray:
+    """numpy statement of what mh_image_luma_u8 computes = Pillow's ``convert("L")`` of an RGB image (Convert.c rgb2l): uint8 [..., 3]
+    -> uint8 [...].  Tests only."""
+    r, g, b = (rgb[..., k].astype(np.uint32) for k in range(3))
+    return ((r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16).astype(np.uint8)
+
+
 def pil_rotate_fixed_coeffs(angle_deg: float, w: int, h: int):
     """``Image.rotate(angle, NEAREST, expand=False)`` (what torchvision's F.rotate calls on a PIL image) as the six 16.16 fixed-point
     coefficients libImaging/Geometry.c's affine_fixed walks: source x = (a2 + y a1 + x a0) >> 16, source y = (a5 + y a4 + x a3) >> 16.
@@ -303,12 +310,26 @@ class DeviceImagePipeline:
       vertical-first included (``pil_resize_vertical_first``);
     * ``mode="stretch"``: Resize((S, S)) (Kevin, Multimodal_example_task2C.py:224); ``augment=True`` adds
       RandomHorizontalFlip, ColorJitter(0.1, 0.1, 0.1, 0.1) and RandomRotation(15) with PIL's uint8 arithmetic; the random
-      factors come from ``generator`` (torchvision's own RNG stream cannot be reproduced)."""
+      factors come from ``generator`` (torchvision's own RNG stream cannot be reproduced);
+    * ``grayscale=True, mean=(0.45,), std=(0.22,)``: the organizers' Subtask-2B transform (ResNet_example_task2B.py:158-167):
+      ``convert("L")`` of the source at its own size, THEN the resize and the crop on that one band (resizing RGB first and converting
+      afterwards gives other pixels), ToTensor, Normalize with one mean / std: f32 [B, 1, S, S], ``last_u8`` [B, S, S, 1], bit-identical
+      to Pillow + torchvision.  The host still packs RGB (``convert("RGB")`` then L equals a direct ``convert("L")`` for the modes a
+      decoded file arrives in); no augmentation on this path.
+
+    ``mean`` / ``std``: Normalize's, one per band (default: ImageNet's)."""
 
     def __init__(self, image_size: int = 224, resize: int = 256, mode: str = "center_crop", augment: bool = False,
-                 device="cuda", generator: Optional[torch.Generator] = None, jitter=(0.1, 0.1, 0.1, 0.1), degrees: float = 15.0):
+                 device="cuda", generator: Optional[torch.Generator] = None, jitter=(0.1, 0.1, 0.1, 0.1), degrees: float = 15.0,
+                 grayscale: bool = False, mean=IMAGENET_MEAN, std=IMAGENET_STD):
         if mode not in ("center_crop", "stretch"):
             raise ValueError(f"mode must be 'center_crop' or 'stretch', got {mode!r}")
+        if grayscale and augment:
+            raise ValueError("augment=True with grayscale=True is not supported (the Subtask-2B example has no augmentation)")
+        self.grayscale = bool(grayscale)
+        self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+        if len(self.mean) != len(self.std) or len(self.mean) != (1 if grayscale else 3):
+            raise ValueError(f"mean and std need {1 if grayscale else 3} value(s) each, got {mean!r} and {std!r}")
         self.S, self.resize, self.mode, self.augment = image_size, resize, mode, augment
         self.device = torch.device(device)
         self.gen = generator or torch.Generator().manual_seed(0)
@@ -385,6 +406,7 @@ class DeviceImagePipeline:
                     jit[b, 6:12] = co
             self.last_params = dict(flip=flips.copy(), factors=fac.copy(), order=orders, angle=list(angles))
         parts = meta + [x.view(np.uint8).reshape(-1) for x in (xb, xc, yb, yc)] + [flips, jit.view(np.uint8).reshape(-1), vfirst]
+        nc = 1 if self.grayscale else 3
         starts, pos = [], (total + 63) // 64 * 64
         for p_ in parts:
             starts.append(pos)
@@ -409,10 +431,22 @@ class DeviceImagePipeline:
         self._pinned[akey + ".event"] = ev
         base = dev.data_ptr()
         ptr = lambda i: base + starts[i]
-        tmp = torch.empty((B, max(max_h * S, S * max_w), 3), dtype=torch.uint8, device=self.device)
-        out = torch.empty((B, S, S, 3), dtype=torch.uint8, device=self.device)
+        tmp = torch.empty((B, max(max_h * S, S * max_w), nc), dtype=torch.uint8, device=self.device)
+        out = torch.empty((B, S, S, nc), dtype=torch.uint8, device=self.device)
         lib = _lib.load()
         stream = torch.cuda.current_stream().cuda_stream
+        if self.grayscale:
+            # convert("L") of every source at its own size (image b at a third of its RGB byte offset), then the same two passes on one band
+            gray = torch.empty(total // 3 + 16, dtype=torch.uint8, device=self.device)
+            _lib.check(lib.mh_image_luma_u8(base, ptr(0), ptr(1), gray.data_ptr(), B, max(s_ // 3 for s_ in sizes), stream), "mh_image_luma_u8")
+            _lib.check(lib.mh_image_resample_l_u8(gray.data_ptr(), ptr(0), ptr(1), ptr(2), ptr(3), KX, ptr(4), ptr(5), KY, None,
+                                                  ptr(8) if max_w else None, tmp.data_ptr(), out.data_ptr(), B, max_h, max_w, S, S, stream),
+                       "mh_image_resample_l_u8")
+            self.last_u8 = out
+            res = torch.empty((B, 1, S, S), dtype=torch.float32, device=self.device)
+            _lib.check(lib.mh_image_normalize_l_u8(out.data_ptr(), res.data_ptr(), B * S * S, self.mean[0], self.std[0], stream),
+                       "mh_image_normalize_l_u8")
+            return res
         _lib.check(lib.mh_image_resample_u8(base, ptr(0), ptr(1), ptr(2), ptr(3), KX, ptr(4), ptr(5), KY,
                                             ptr(6) if self.augment else None, ptr(8) if max_w else None, tmp.data_ptr(),
                                             out.data_ptr(), B, max_h, max_w, S, S, stream),
@@ -424,4 +458,4 @@ class DeviceImagePipeline:
                                                      stream), "mh_image_jitter_rotate_u8")
             out = out2
         self.last_u8 = out
-        return ops.image_normalize_u8(out, IMAGENET_MEAN, IMAGENET_STD)
+        return ops.image_normalize_u8(out, self.mean, self.std)

@@ -19,8 +19,13 @@ submodules only HOLD the parameters and running statistics; the arithmetic runs 
   backward; ``ResNet50.options`` (``TowerOptions``) holds its A/B switches;
 * the 16-bit gradient stream carries ``grad_stream_scale`` (8192 for fp16), removed where parameter gradients are produced.
 
-``ResNetClassifier`` is the Subtask-2B surface (ResNet_example_task2B.py:206-221): ``model(pixel_values=..., labels=...)``
-returns ``(loss, logits)`` for HF Trainer.
+``_ConvTower`` holds that machinery -- ONE forward and ONE backward walk over (conv, BatchNorm) units; a family (``_ResNet``: torchvision's
+names; ``HFResNetModel``: transformers') only builds its parameter holders from a stage list (``stage_blocks``) and hands them to ``_wire``.
+
+``ResNetClassifier`` is the ResNet-50 (/ 18 / 34) surface of BASELINE config 2 under the Subtask-2B Trainer protocol
+(ResNet_example_task2B.py:206-221): ``model(pixel_values=..., labels=...)`` returns ``(loss, logits)``.  The model that example itself
+trains -- ``ResNetForImageClassification(ResNetConfig(num_channels=1, layer_type="basic", depths=[2, 2], hidden_sizes=[32, 64]))``,
+:146-154 -- is ``HFResNetForImageClassification``: transformers' module tree and state_dict on the same walk.
 """
 from __future__ import annotations
 
@@ -185,7 +190,18 @@ class _Conv:
                   "mh_conv_dgrad")
             return dx, part
         dA = dx if route == GEMM else torch.empty((M, self.ldk), dtype=dy.dtype, device=dev)      # (GEMM: ldk == cp, the panel IS dx)
-        ops.gemm_grouped([ops.Gemm(dy, wk, dA, M, self.ldk, self.cout, self.cout, self.ldk, self.ldk)], False, True)
+        if self.cout % 64 == 0:
+            ops.gemm_grouped([ops.Gemm(dy, wk, dA, M, self.ldk, self.cout, self.cout, self.ldk, self.ldk)], False, True)
+        else:
+            # a contraction (= cout) that is no multiple of the 64-deep K tile: dy's rows are cout long, so the GEMM's K tile would run into the
+            # next row (it refuses).  The panel dA = dy . wk IS a 1x1 convolution of dy ([B][Ho][Wo][cout]) with wk transposed, and mh_conv_fwd's
+            # generic walk zero-fills a K tile past the last channel: the same 128x128 MFMA tile, no new kernel.  (wk^T: <= 36 KiB, made here.)
+            kt = (self.cout + 63) // 64 * 64
+            wt = torch.zeros((self.ldk, kt), dtype=dy.dtype, device=dev)
+            wt[:, :self.cout] = wk.t()
+            g = _lib.MhConvGeom()
+            g.B, g.H, g.W, g.C, g.KH, g.KW, g.stride, g.pad, g.Cout, g.ldk = B, Ho, Wo, self.cout, 1, 1, 1, 0, self.ldk, kt
+            check(lib.mh_conv_fwd(dy.data_ptr(), wt.data_ptr(), dA.data_ptr(), None, None, g, _stream()), "mh_conv_fwd (dgrad panel)")
         if route == COL2IM:
             check(lib.mh_col2im_nhwc(dA.data_ptr(), dx.data_ptr(), B, H, W, self.cp, self.kh, self.kw, self.stride, self.pad, self.ldk,
                                      _stream()), "mh_col2im_nhwc")
@@ -342,6 +358,10 @@ class Bottleneck(nn.Module):
         self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes * 4, 1, stride=stride, bias=False), nn.BatchNorm2d(planes * 4)) if downsample else None
         self.stride = stride
 
+    def conv_bn_pairs(self):
+        """(the main branch's (conv, bn) in order, the shortcut's or None): what _ConvTower._wire reads of a block"""
+        return [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)], (None if self.downsample is None else tuple(self.downsample))
+
 
 class BasicBlock(nn.Module):
     """torchvision.models.resnet.BasicBlock (= timm's for resnet18 / 34): parameter holder."""
@@ -355,6 +375,9 @@ class BasicBlock(nn.Module):
         self.bn2 = nn.BatchNorm2d(planes)
         self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes, 1, stride=stride, bias=False), nn.BatchNorm2d(planes)) if downsample else None
         self.stride = stride
+
+    def conv_bn_pairs(self):
+        return [(self.conv1, self.bn1), (self.conv2, self.bn2)], (None if self.downsample is None else tuple(self.downsample))
 
 
 class _TowerFn(torch.autograd.Function):
@@ -373,48 +396,42 @@ class _TowerFn(torch.autograd.Function):
         return (None, None) + tuple(grads[id(p)] for p in ctx.net._tower_params)
 
 
-class _ResNet(nn.Module):
-    """torchvision ResNet topology and state_dict over one block type (`block`: Bottleneck / BasicBlock) on the HIP kernels.
-    ``forward(image f32 [B,3,H,W]) -> logits [B, num_classes]`` (``num_classes=0``: no classifier, the features, as timm's
-    ``reset_classifier(0)``); ``features(image)`` returns the pooled ``feature_dim`` features;
-    ``options``: the backward's TowerOptions."""
-    block = None
-    default_layers = None
+def stage_blocks(stages, make_block):
+    """The blocks of a residual tower from its stage list [(blocks, in, out, stride)], one list per stage: a stage's first block takes the
+    stride and the channel change, and a projection shortcut when either is there; ``make_block(cin, cout, stride, shortcut)`` builds the
+    parameter holder under its family's names (torchvision's ``layerN.i.convK`` / transformers' ``stages.N.layers.i.layer.K``)."""
+    return [[make_block(cin if bi == 0 else cout, cout, stride if bi == 0 else 1, bi == 0 and (stride != 1 or cin != cout)) for bi in range(n)]
+            for n, cin, cout, stride in stages]
 
-    def __init__(self, num_classes: int = 1000, compute_dtype: str = "fp16", layers=None, width: int = 64,
-                 grad_stream_scale: float = 0.0, seed: int = 0, options: TowerOptions = TowerOptions()):
-        super().__init__()
-        block, layers = self.block, (self.default_layers if layers is None else layers)
+
+class _ConvTower(nn.Module):
+    """A stem (7x7 / 2 conv + BatchNorm + ReLU + 3x3 / 2 max pool), residual blocks, global average pool on the HIP kernels: the ONE
+    forward and backward walk of every ResNet family here.  A subclass builds its parameter holders under its own names and hands them to
+    ``_wire``; ``features(image f32 [B, in_channels, H, W])`` returns the pooled ``feature_dim`` features; ``options``: the backward's
+    TowerOptions."""
+
+    def _init_tower(self, compute_dtype: str, grad_stream_scale: float, options: TowerOptions):
         if compute_dtype not in ("bf16", "fp16"):
             raise ValueError(f"compute_dtype must be 'bf16' or 'fp16', got {compute_dtype!r}")
-        torch.manual_seed(seed)
         self.compute_dtype = compute_dtype
         self.options = options
         self.gscale = float(grad_stream_scale) if grad_stream_scale else (8192.0 if compute_dtype == "fp16" else 1.0)
-        self.conv1 = nn.Conv2d(3, width, 7, stride=2, padding=3, bias=False)
-        self.bn1 = nn.BatchNorm2d(width)
-        inplanes = width
-        for li, (n, planes, stride) in enumerate(zip(layers, (width, width * 2, width * 4, width * 8), (1, 2, 2, 2)), 1):
-            blocks = []
-            for bi in range(n):
-                s = stride if bi == 0 else 1
-                blocks.append(block(inplanes, planes, s, downsample=(bi == 0 and (s != 1 or inplanes != planes * block.expansion))))
-                inplanes = planes * block.expansion
-            setattr(self, f"layer{li}", nn.Sequential(*blocks))
-        self.feature_dim = inplanes
-        self.fc = nn.Linear(inplanes, num_classes) if num_classes > 0 else nn.Identity()      # 0: timm's reset_classifier(0), forward = features
-        for m in self.modules():          # torchvision's initialisation
-            if isinstance(m, nn.Conv2d):
-                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-        self._tower_params: List[nn.Parameter] = [p for n, p in self.named_parameters() if not n.startswith("fc.")]
+
+    def _wire(self, stem_conv: nn.Conv2d, stem_bn: nn.BatchNorm2d, blocks, tower_params: List[nn.Parameter]):
+        """`blocks`: the holders in forward order (each with ``conv_bn_pairs()``); the stem's input channels are zero-padded to 8."""
+        self._tower_params = tower_params
 
         def unit(conv, bn, cin_pad=None):
             return ConvBnRec(_Conv(conv, cin_pad), _BN(bn))
-        self._stem_unit = unit(self.conv1, self.bn1, 8)
-        self._block_units = [BlockRec(unit(b.conv1, b.bn1), unit(b.conv2, b.bn2), unit(b.conv3, b.bn3) if hasattr(b, "conv3") else None,
-                                      None if b.downsample is None else unit(b.downsample[0], b.downsample[1]))
-                             for li in range(1, 5) for b in getattr(self, f"layer{li}")]
+        self.in_channels = stem_conv.in_channels
+        self._stem_unit = unit(stem_conv, stem_bn, 8)
+        self._block_units = []
+        for b in blocks:
+            chain, shortcut = b.conv_bn_pairs()
+            c = [unit(*cb) for cb in chain]
+            self._block_units.append(BlockRec(c[0], c[1], c[2] if len(c) > 2 else None, None if shortcut is None else unit(*shortcut)))
         self._units = [self._stem_unit] + [u for b in self._block_units for u in b.units]
+        self.feature_dim = self._block_units[-1].chain[-1].conv.cout
 
     # ---- launches ----------------------------------------------------------------------------------------------
     def _forward_tape(self, image: torch.Tensor, training: bool) -> Tape:
@@ -423,11 +440,11 @@ class _ResNet(nn.Module):
         lib = _lib.load(self.compute_dtype)
         T16 = torch.float16 if self.compute_dtype == "fp16" else torch.bfloat16
         B, Cc, H, W = image.shape
-        if Cc != 3:
-            raise ValueError(f"{type(self).__name__} expects 3-channel images")
+        if Cc != self.in_channels:
+            raise ValueError(f"{type(self).__name__} expects {self.in_channels}-channel images")
         x = torch.empty((B * H * W, 8), dtype=T16, device=image.device)
         img32 = image.to(F32).contiguous()      # named: a temporary would be freed (and its block re-used) before the launch
-        check(lib.mh_nchw_to_nhwc(img32.data_ptr(), x.data_ptr(), B, 3, H, W, 8, _stream()), "mh_nchw_to_nhwc")
+        check(lib.mh_nchw_to_nhwc(img32.data_ptr(), x.data_ptr(), B, Cc, H, W, 8, _stream()), "mh_nchw_to_nhwc")
         packed = self._pack_all_weights(lib, T16)
         def conv_bn(u, xin, h, w, residual=None, relu=True) -> ConvBnRec:
             wk = packed[id(u.conv.mod)]
@@ -436,7 +453,7 @@ class _ResNet(nn.Module):
             return ConvBnRec(u.conv, u.bn, xin, wk, z, y, sm, sr, h, w, ho, wo, relu, residual is not None)
 
         stem = conv_bn(self._stem_unit, x, H, W)
-        C1 = self.conv1.out_channels
+        C1 = self._stem_unit.conv.cout
         h, w = (stem.Ho + 2 - 3) // 2 + 1, (stem.Wo + 2 - 3) // 2 + 1
         x = torch.empty((B * h * w, C1), dtype=T16, device=image.device)
         arg = torch.empty((B * h * w, C1), dtype=torch.uint8, device=image.device)
@@ -467,7 +484,7 @@ class _ResNet(nn.Module):
         launches of <= 64 jobs."""
         convs = [u.conv for u in self._units]
         total = sum(c.cout * c.ldk for c in convs)
-        buf = torch.empty(total, dtype=T16, device=self.conv1.weight.device)
+        buf = torch.empty(total, dtype=T16, device=self._stem_unit.conv.mod.weight.device)
         packed, off = {}, 0
         for i in range(0, len(convs), _lib.MH_CONV_MAX_JOBS):
             chunk = convs[i:i + _lib.MH_CONV_MAX_JOBS]
@@ -568,6 +585,36 @@ class _ResNet(nn.Module):
             return _TowerFn.apply(image, self, *self._tower_params)
         return self._forward_tape(image, training=self.training).pooled
 
+
+class _ResNet(_ConvTower):
+    """torchvision ResNet topology and state_dict over one block type (`block`: Bottleneck / BasicBlock) on the HIP kernels.
+    ``forward(image f32 [B,3,H,W]) -> logits [B, num_classes]`` (``num_classes=0``: no classifier, the features, as timm's
+    ``reset_classifier(0)``); ``features(image)`` returns the pooled ``feature_dim`` features;
+    ``options``: the backward's TowerOptions."""
+    block = None
+    default_layers = None
+
+    def __init__(self, num_classes: int = 1000, compute_dtype: str = "fp16", layers=None, width: int = 64,
+                 grad_stream_scale: float = 0.0, seed: int = 0, options: TowerOptions = TowerOptions()):
+        super().__init__()
+        block, layers = self.block, (self.default_layers if layers is None else layers)
+        self._init_tower(compute_dtype, grad_stream_scale, options)
+        torch.manual_seed(seed)
+        self.conv1 = nn.Conv2d(3, width, 7, stride=2, padding=3, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        outs = [width * m * block.expansion for m in (1, 2, 4, 8)]
+        stages = list(zip(layers, [width] + outs[:-1], outs, (1, 2, 2, 2)))      # (blocks, in, out, stride); four `layerN` at the most
+        built = stage_blocks(stages, lambda cin, cout, stride, shortcut: block(cin, cout // block.expansion, stride, downsample=shortcut))
+        for li, blocks in enumerate(built, 1):
+            setattr(self, f"layer{li}", nn.Sequential(*blocks))
+        inplanes = stages[-1][2]
+        self.fc = nn.Linear(inplanes, num_classes) if num_classes > 0 else nn.Identity()      # 0: timm's reset_classifier(0), forward = features
+        for m in self.modules():          # torchvision's initialisation
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+        self._wire(self.conv1, self.bn1, [b for blocks in built for b in blocks],
+                   [p for n, p in self.named_parameters() if not n.startswith("fc.")])
+
     def forward(self, image: torch.Tensor) -> torch.Tensor:
         f = self.features(image)
         return f if isinstance(self.fc, nn.Identity) else fused.linear(f, self.fc.weight, self.fc.bias)
@@ -591,9 +638,138 @@ class ResNet34(_ResNet):
 RESNETS = {"resnet50": ResNet50, "resnet18": ResNet18, "resnet34": ResNet34}
 
 
+# ---- transformers' ResNet (models/resnet/modeling_resnet.py): the same network under transformers' module names ----------------------
+class HFConvLayer(nn.Module):
+    """transformers' ResNetConvLayer / ResNetShortCut: ``convolution`` + ``normalization`` (the activation has no state): parameter holder."""
+
+    def __init__(self, cin: int, cout: int, kernel_size: int = 3, stride: int = 1):
+        super().__init__()
+        self.convolution = nn.Conv2d(cin, cout, kernel_size, stride=stride, padding=kernel_size // 2, bias=False)
+        self.normalization = nn.BatchNorm2d(cout)
+
+
+class HFLayer(nn.Module):
+    """transformers' ResNetBasicLayer (3x3, 3x3) / ResNetBottleNeckLayer (1x1 to out / 4, 3x3 with the stride, 1x1): ``shortcut`` (a
+    projection, or nn.Identity) and ``layer`` (the main branch): parameter holder."""
+
+    def __init__(self, cin: int, cout: int, stride: int, shortcut: bool, bottleneck: bool):
+        super().__init__()
+        self.shortcut = HFConvLayer(cin, cout, 1, stride) if shortcut else nn.Identity()
+        mid = cout // 4
+        self.layer = nn.Sequential(HFConvLayer(cin, mid, 1), HFConvLayer(mid, mid, 3, stride), HFConvLayer(mid, cout, 1)) if bottleneck else \
+            nn.Sequential(HFConvLayer(cin, cout, 3, stride), HFConvLayer(cout, cout, 3))
+
+    def conv_bn_pairs(self):
+        s = self.shortcut
+        return [(u.convolution, u.normalization) for u in self.layer], (None if isinstance(s, nn.Identity) else (s.convolution, s.normalization))
+
+
+class HFStage(nn.Module):
+    def __init__(self, layers):
+        super().__init__()
+        self.layers = nn.Sequential(*layers)
+
+
+class HFEmbeddings(nn.Module):
+    def __init__(self, num_channels: int, embedding_size: int):
+        super().__init__()
+        self.embedder = HFConvLayer(num_channels, embedding_size, 7, 2)
+        self.pooler = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+
+
+class HFEncoder(nn.Module):
+    def __init__(self, stages):
+        super().__init__()
+        self.stages = nn.ModuleList(stages)
+
+
+HF_RESNET_DEFAULTS = dict(num_channels=3, embedding_size=64, hidden_sizes=(256, 512, 1024, 2048), depths=(3, 4, 6, 3), layer_type="bottleneck",
+                          hidden_act="relu", downsample_in_first_stage=False, downsample_in_bottleneck=False, num_labels=2)
+
+
+class HFResNetModel(_ConvTower):
+    """transformers' ``ResNetModel`` (``embedder.embedder.convolution``, ``encoder.stages.N.layers.i.shortcut / layer.K`` ...) on the tower
+    walk: ``forward(pixel_values)`` returns the pooled features [B, hidden_sizes[-1]]."""
+
+    def __init__(self, cfg: dict, compute_dtype: str, grad_stream_scale: float, options: TowerOptions):
+        super().__init__()
+        self._init_tower(compute_dtype, grad_stream_scale, options)
+        hidden, depths = list(cfg["hidden_sizes"]), list(cfg["depths"])
+        bottleneck = cfg["layer_type"] == "bottleneck"
+        self.embedder = HFEmbeddings(cfg["num_channels"], cfg["embedding_size"])
+        stages = list(zip(depths, [cfg["embedding_size"]] + hidden[:-1], hidden, [2 if cfg["downsample_in_first_stage"] else 1] + [2] * (len(hidden) - 1)))
+        built = stage_blocks(stages, lambda cin, cout, stride, shortcut: HFLayer(cin, cout, stride, shortcut, bottleneck))
+        self.encoder = HFEncoder([HFStage(layers) for layers in built])
+        self.pooler = nn.AdaptiveAvgPool2d((1, 1))
+        for m in self.modules():          # transformers' ResNetPreTrainedModel._init_weights
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+        self._wire(self.embedder.embedder.convolution, self.embedder.embedder.normalization, [b for layers in built for b in layers],
+                   list(self.parameters()))
+
+    def forward(self, pixel_values: torch.Tensor) -> torch.Tensor:
+        return self.features(pixel_values)
+
+
+class HFResNetForImageClassification(nn.Module):
+    """transformers' ``ResNetForImageClassification`` as the organizers' Subtask-2B example builds it (ResNet_example_task2B.py:146-167:
+    ``ResNetConfig(num_channels=1, layer_type="basic", depths=[2, 2], hidden_sizes=[32, 64], num_labels=...)``) on the HIP tower:
+    transformers' module tree and state_dict, key for key (``resnet.encoder.stages.0.layers.0.shortcut.convolution.weight``,
+    ``classifier.1.bias``, every ``num_batches_tracked``), so ``load_state_dict`` takes the library model's weights and the Hub's HF-format
+    ResNet checkpoints (``microsoft/resnet-18`` / ``-50``) and gives them back.  ``config``: a ``transformers.ResNetConfig`` (or any object
+    / dict with its fields), or the fields as keywords with ResNetConfig's defaults.  Every channel count (for bottleneck layers
+    ``hidden // 4`` too) must be a multiple of 8; ``hidden_act != "relu"`` and ``downsample_in_bottleneck=True`` are refused.
+    ``model(pixel_values=..., labels=...)`` -> ``(loss, logits)``; without labels ``logits`` (HF Trainer's protocol)."""
+
+    def __init__(self, config=None, compute_dtype: str = "fp16", grad_stream_scale: float = 0.0, seed: int = 0,
+                 options: TowerOptions = TowerOptions(), **fields):
+        super().__init__()
+        unknown = sorted(set(fields) - set(HF_RESNET_DEFAULTS))
+        if unknown:
+            raise TypeError(f"HFResNetForImageClassification: unknown configuration fields {unknown}")
+        get = (lambda k, d: config.get(k, d)) if isinstance(config, dict) else (lambda k, d: getattr(config, k, d))
+        cfg = {k: fields[k] if k in fields else (d if config is None else get(k, d)) for k, d in HF_RESNET_DEFAULTS.items()}
+        if cfg["hidden_act"] != "relu":
+            raise ValueError(f"hidden_act must be 'relu' (the kernels fuse the ReLU), got {cfg['hidden_act']!r}")
+        if cfg["downsample_in_bottleneck"]:
+            raise ValueError("downsample_in_bottleneck=True is not supported (the stride sits on the 3x3 convolution)")
+        if cfg["layer_type"] not in ("basic", "bottleneck"):
+            raise ValueError(f"layer_type must be 'basic' or 'bottleneck', got {cfg['layer_type']!r}")
+        if cfg["num_channels"] not in (1, 3):
+            raise ValueError(f"num_channels must be 1 or 3, got {cfg['num_channels']!r}")
+        hidden, depths = list(cfg["hidden_sizes"]), list(cfg["depths"])
+        if not 1 <= len(hidden) <= 4 or len(depths) != len(hidden) or min(depths) < 1:
+            raise ValueError(f"hidden_sizes and depths must name the same 1 to 4 stages of at least one layer, got {hidden} and {depths}")
+        if cfg["embedding_size"] < 8 or cfg["embedding_size"] % 8:
+            raise ValueError(f"embedding_size must be a multiple of 8 (the kernels' channel granule), got {cfg['embedding_size']}")
+        for h in hidden:
+            if h < 8 or h % 8:
+                raise ValueError(f"hidden_sizes must be multiples of 8 (the kernels' channel granule), got {hidden}")
+            if cfg["layer_type"] == "bottleneck" and (h // 4 < 8 or (h // 4) % 8 or h % 4):
+                raise ValueError(f"hidden_sizes of bottleneck layers must be multiples of 32 (hidden // 4 a multiple of 8), got {hidden}")
+        if int(cfg["num_labels"]) < 1:
+            raise ValueError(f"num_labels must be positive, got {cfg['num_labels']!r}")
+        self.resnet_config = cfg          # (a dict, and not named `config`: transformers.Trainer writes its own fields into a model's .config)
+        self.num_labels = int(cfg["num_labels"])
+        torch.manual_seed(seed)
+        self.resnet = HFResNetModel(cfg, compute_dtype, grad_stream_scale, options)
+        self.classifier = nn.Sequential(nn.Flatten(), nn.Linear(hidden[-1], self.num_labels))
+        self.loss_fct = CrossEntropyLoss()
+
+    def forward(self, pixel_values=None, labels=None, **unused):
+        if pixel_values is None:
+            raise ValueError("HFResNetForImageClassification.forward needs pixel_values")
+        fc = self.classifier[1]
+        logits = fused.linear(self.resnet(pixel_values), fc.weight, fc.bias)
+        if labels is not None:
+            return self.loss_fct(logits, labels.view(-1)), logits
+        return logits
+
+
 class ResNetClassifier(nn.Module):
-    """Subtask-2B surface over a ResNet tower (ResNet_example_task2B.py:206-221): ``model(pixel_values=..., labels=...)`` ->
-    ``(loss, logits)``; without labels ``logits``.  ``arch``: "resnet50" (default) | "resnet18" | "resnet34"."""
+    """The ResNet-50 surface of BASELINE config 2 under the Subtask-2B Trainer protocol (ResNet_example_task2B.py:206-221):
+    ``model(pixel_values=..., labels=...)`` -> ``(loss, logits)``; without labels ``logits``.  ``arch``: "resnet50" (default) | "resnet18" |
+    "resnet34", torchvision's keys.  The model the 2B example itself builds (a ``ResNetConfig``) is ``HFResNetForImageClassification``."""
 
     def __init__(self, num_labels: int = 2, compute_dtype: str = "fp16", arch: str = "resnet50", **kw):
         super().__init__()
