@@ -137,7 +137,8 @@ int mh_layernorm_bwd(const void* dy /*bf16*/, const void* x /*bf16*/, const floa
 typedef struct MhLnFwdJob {
     const void* x; const float* gamma; const float* beta; void* y; float* y_f32; float* mean; float* rstd;
     int32_t rows; float eps;
-    const int32_t* rows_dev;  /* device int32 or NULL: live rows of a packed tensor (<= rows), read at launch time */
+    const int32_t* rows_dev;  /* device int32 or NULL: live rows of a packed tensor (<= rows), read at launch time.  x holds
+                                 `rows` rows and the forward may READ any of them; only live rows are written */
 } MhLnFwdJob;
 typedef struct MhLnBwdJob {
     const void* dy; const void* x; const float* gamma; const float* mean; const float* rstd;

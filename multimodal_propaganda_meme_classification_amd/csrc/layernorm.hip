@@ -95,18 +95,24 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwdGroup grp, int D
     float* __restrict__ y32 = jb.y_f32;
     float* __restrict__ mean = jb.mean;
     float* __restrict__ rstd = jb.rstd;
-    const int rows = jb.rows_dev ? min(jb.rows, *jb.rows_dev) : jb.rows;
+    // the live row count of a packed job is read from device memory.  It stays OFF the address path: the row loads go to the rows
+    // the launch was sized for (the buffers hold jb.rows rows), so they are in flight while the count arrives; only the stores and
+    // the statistics need it.
+    const int rows_max = jb.rows;
+    int rows = rows_max;
+    if (jb.rows_dev) rows = min(rows_max, *jb.rows_dev);
     const float eps = jb.eps;
     const int lane = threadIdx.x & 63;
     // (wave-uniform by construction; readfirstlane tells the compiler, so that the rows' buffer resources live in SGPRs)
     const int row0 = ((int)blockIdx.x - grp.start[j]) * (4 * RPW) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * RPW;
-    if (row0 >= rows) return;
+    if (row0 >= rows_max) return;
     i32x4 raw[RPW][NCH];
 #pragma unroll
-    for (int r = 0; r < RPW; ++r) load_row_raw<NCH>(x + (size_t)min(row0 + r, rows - 1) * D, D, lane, raw[r]);
+    for (int r = 0; r < RPW; ++r) load_row_raw<NCH>(x + (size_t)min(row0 + r, rows_max - 1) * D, D, lane, raw[r]);
     float g[NCH][8], b[NCH][8];
     load_row_f32<NCH>(gamma, D, lane, g);
     load_row_f32<NCH>(beta, D, lane, b);
+    if (row0 >= rows) return;
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
         const int row = row0 + r;
