@@ -14,6 +14,10 @@ Towers, poolings, Linear+BatchNorm1d+ReLU projections, ConcatAttention3, the foc
 Synthetic inputs (no dataset or checkpoints offline).   python examples/task2c_kevin.py [--full] [--caption-model {bert,roberta}]
                                                                                           [--image-model {vit,resnet18,convnext_tiny}]
                                                                                           [--accumulation-steps N]
+                                                                                          [--criterion {focal,bce}] [--pos-weight W]
+--criterion bce: ``nn.BCEWithLogitsLoss(pos_weight=...)`` in place of the focal loss -> memehip.BCEWithLogitsLoss (mh_bce_fwd_bwd);
+--pos-weight is a number or ``balanced`` = n_neg / n_pos of the training labels (the class-weighted criterion the reference names
+as the focal loss's alternative, :136-139, :166).
 --accumulation-steps N: gradient accumulation -- every step runs the batch as N micro-batches with loss / N and one
 optimizer.step() behind them (model.set_grad_accumulation(True)).
 --image-model resnet18: the image tower is the submitted model's ``image_model = "resnet18"`` (:82 default; the only family its
@@ -41,6 +45,8 @@ def main():
     ap.add_argument("--image-model", choices=("vit", "resnet18", "convnext_tiny"), default="vit")
     ap.add_argument("--accumulation-steps", type=int, default=1,
                     help="N > 1: every step accumulates the gradients of N micro-batches (the batch in N parts, loss / N)")
+    ap.add_argument("--criterion", choices=("focal", "bce"), default="focal")
+    ap.add_argument("--pos-weight", default="1", help="with --criterion bce: a number, or 'balanced' = n_neg / n_pos of the training labels")
     args = ap.parse_args()
     small, roberta, resnet = not args.full, args.caption_model == "roberta", args.image_model == "resnet18"
     convnext = args.image_model == "convnext_tiny"
@@ -82,7 +88,21 @@ def main():
     lr = 2e-5
     optimizer = memehip.Adam(model.get_params(lr), lr=lr, max_grad_norm=1.0)      # clip_grad_norm_(model.parameters(), 1.0), fused
     scheduler = memehip.get_linear_schedule_with_warmup(optimizer, num_warmup_steps=2, num_training_steps=10)
-    criterion = memehip.SigmoidFocalLoss()
+    if args.criterion == "bce":
+        n_pos = float(labels.sum())
+        if args.pos_weight == "balanced":
+            if n_pos == 0:
+                ap.error("--pos-weight balanced: the training labels hold no positive sample")
+            pos_weight = (B - n_pos) / n_pos
+        else:
+            try:
+                pos_weight = float(args.pos_weight)
+            except ValueError:
+                ap.error(f"--pos-weight must be a number or 'balanced', got {args.pos_weight!r}")
+        criterion = memehip.BCEWithLogitsLoss(pos_weight=pos_weight)
+        print(f"criterion: BCEWithLogitsLoss(pos_weight={pos_weight:.4f})")
+    else:
+        criterion = memehip.SigmoidFocalLoss()
     N = args.accumulation_steps
     if N < 1 or B % N:
         ap.error(f"--accumulation-steps must divide the batch of {B}")
@@ -106,7 +126,7 @@ def main():
         grad_norm = optimizer.grad_norm()          # clip_grad_norm_(model.parameters(), float("inf")) of the reference's log line
         optimizer.step()
         scheduler.step()
-        print(f"step {step}: focal loss {float(loss.detach()):.5f} | LR {scheduler.get_last_lr()[0]:.2e} | Grad Norm {float(grad_norm):.4f}",
+        print(f"step {step}: {args.criterion} loss {float(loss.detach()):.5f} | LR {scheduler.get_last_lr()[0]:.2e} | Grad Norm {float(grad_norm):.4f}",
               flush=True)
     print("ok")
 

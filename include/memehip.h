@@ -405,7 +405,8 @@ int mh_vit_assemble_bwd(const void* dx /*bf16 [B][Np+1][D]*/, void* dproj /*bf16
  *   pooled token rows; the other rows must be zero-filled by the caller).
  * mh_ce_fwd_bwd: loss (scalar f32), dlogits = (softmax - onehot)/B, n_correct (argmax == label, first maximum wins).
  *   A label outside [0, C) -- nn.CrossEntropyLoss's ignore_index -100 included -- is read as class 0 (it is NOT ignored:
- *   the loss, dlogits and n_correct are those of label 0, and the mean stays over all B rows).
+ *   the loss, dlogits and n_correct are those of label 0, and the mean stays over all B rows).  mh_ce_opts_fwd_bwd below
+ *   ignores a label on request.
  * ------------------------------------------------------------------------------------------ */
 typedef struct MhHeadParams {
     const float *Wt, *bt;   /* bert_fc   [P][Dt], [P] */
@@ -465,6 +466,31 @@ int mh_ce_fwd_bwd(const float* logits, const int64_t* labels, float* loss, float
 int mh_focal_fwd_bwd(const float* logits, int ld, const float* targets /*f32 [B] in {0,1}*/, float* loss,
                      float* dlogits, int32_t* n_correct, int B, float alpha, float gamma, float grad_scale,
                      const float* grad_scale_dev /*as in mh_ce_fwd_bwd*/, mh_stream_t stream);
+/* Cross-entropy with the arguments of torch.nn.functional.cross_entropy(weight=, ignore_index=, label_smoothing=, reduction=)
+ * (nn.CrossEntropyLoss(weight=class_weights), Multimodal_example_task2C.py:166).  One workgroup, one thread per row, B <= 1024.
+ *   w_c = class_weight[c] (1 when class_weight is NULL); k_i = 0 when has_ignore != 0 and y_i == ignore_index, else 1;
+ *   l_i = k_i [ (1 - eps) w_{y_i} (lse_i - z_{i,y_i}) + (eps / C) sum_c w_c (lse_i - z_{i,c}) ],  eps = label_smoothing
+ *   reduction MH_LOSS_MEAN: loss[0] = sum_i l_i / sum_i k_i w_{y_i} ; MH_LOSS_SUM: loss[0] = sum_i l_i ;
+ *   MH_LOSS_NONE: loss[i] = l_i (B values) and dlogits holds the derivative of each row's OWN loss (the caller multiplies the
+ *   upstream gradient in per row).
+ * dlogits [B][C] = the exact derivative of the above times grad_scale * grad_scale_dev[0]; every element is written, an
+ * ignored row as +0.0.  n_correct counts kept rows only (first maximum wins).  All rows ignored under MH_LOSS_MEAN: the loss
+ * is NaN (0 / 0, as in torch), dlogits all zero, n_correct 0.  A label outside [0, C) that is not the ignore index is read as
+ * class 0 (as in mh_ce_fwd_bwd).  MH_ESHAPE: label_smoothing outside [0, 1], an unknown reduction.
+ * With class_weight NULL, label_smoothing 0, no ignored row and MH_LOSS_MEAN the result equals mh_ce_fwd_bwd's bit for bit. */
+#define MH_LOSS_MEAN 0
+#define MH_LOSS_SUM 1
+#define MH_LOSS_NONE 2
+int mh_ce_opts_fwd_bwd(const float* logits, const int64_t* labels, const float* class_weight /*device f32 [C] or NULL*/,
+                       float* loss /*[1], or [B] with MH_LOSS_NONE*/, float* dlogits, int32_t* n_correct, int B, int C,
+                       int64_t ignore_index, int has_ignore, float label_smoothing, int reduction, float grad_scale,
+                       const float* grad_scale_dev /*as in mh_ce_fwd_bwd*/, mh_stream_t stream);
+/* Binary cross-entropy with logits over one logit per sample (F.binary_cross_entropy_with_logits(x, t, pos_weight=)):
+ *   l = (1 - t) softplus(x) + pos_weight t softplus(-x) ; loss = mean (MH_LOSS_MEAN) or sum (MH_LOSS_SUM) over the B rows;
+ * dlogits (stride ld) and n_correct = #(logit > 0 == target > 0.5) as in mh_focal_fwd_bwd.  pos_weight = 1: none. */
+int mh_bce_fwd_bwd(const float* logits, int ld, const float* targets /*f32 [B], soft targets allowed*/, float pos_weight,
+                   float* loss, float* dlogits, int32_t* n_correct, int B, int reduction, float grad_scale,
+                   const float* grad_scale_dev /*as in mh_ce_fwd_bwd*/, mh_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Heads on top of the towers (SURVEY section 8 f ranks 1-2), all fp32:

@@ -235,6 +235,141 @@ __global__ __launch_bounds__(1024) void focal_kernel(const float* __restrict__ l
     }
 }
 
+// cross-entropy with class weights, an ignored label, label smoothing and the three reductions
+// (torch.nn.functional.cross_entropy(weight=, ignore_index=, label_smoothing=, reduction=)); one block, B <= 1024.
+//   l_i = k_i [ (1 - eps) w_{y_i} (lse_i - z_{i,y_i}) + (eps / C) sum_c w_c (lse_i - z_{i,c}) ]
+//   mean: sum_i l_i / sum_i k_i w_{y_i} ; sum: sum_i l_i ; none: loss[i] = l_i, dlogits = each row's own derivative.
+// Two passes over a row: the first gives lse, l_i and the weight sum (needed by every row's gradient under "mean"), the second
+// writes dlogits.  Without weights and smoothing the arithmetic is ce_kernel's, operation for operation (the weight sum is then
+// the exact count of kept rows), so with no row ignored the two kernels give the same bits.
+__global__ __launch_bounds__(1024) void ce_opts_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                       const float* __restrict__ cw, float* __restrict__ loss,
+                                                       float* __restrict__ dlogits, int32_t* __restrict__ n_correct, int B,
+                                                       int C, int64_t ignore_index, int has_ignore, float eps, int reduction,
+                                                       float grad_scale, const float* __restrict__ grad_scale_dev) {
+    if (grad_scale_dev) grad_scale *= grad_scale_dev[0];
+    __shared__ float red[16];
+    __shared__ float redw[16];
+    __shared__ int redc[16];
+    const int b = threadIdx.x;
+    const bool smooth = eps > 0.f;
+    const float a = 1.f - eps, e = eps / (float)C;
+    float li = 0.f, kw = 0.f, lse = 0.f, wy = 1.f, sw = (float)C;
+    int ok = 0, y = 0;
+    bool keep = false;
+    if (b < B) {
+        const float* z = logits + (size_t)b * C;
+        float mx = z[0];
+        int am = 0;
+        for (int c = 1; c < C; ++c)
+            if (z[c] > mx) { mx = z[c]; am = c; }
+        float se = 0.f;
+        for (int c = 0; c < C; ++c) se += expf(z[c] - mx);
+        lse = mx + logf(se);
+        int64_t yl = labels[b];
+        keep = !(has_ignore && yl == ignore_index);
+        if (yl < 0 || yl >= C) yl = 0;
+        y = (int)yl;
+        if (keep) {
+            float t = lse - z[y];
+            if (cw) { wy = cw[y]; t = wy * t; }
+            if (smooth) {
+                float s1 = 0.f;
+                if (cw) {
+                    sw = 0.f;
+                    for (int c = 0; c < C; ++c) { s1 += cw[c] * (lse - z[c]); sw += cw[c]; }
+                } else {
+                    for (int c = 0; c < C; ++c) s1 += lse - z[c];
+                }
+                t = a * t + e * s1;
+            }
+            li = t;
+            kw = wy;
+            ok = (am == y);
+        }
+        if (reduction == 2) loss[b] = li;
+    }
+    float s = wave_sum(li);
+    float ws = wave_sum(kw);
+    int cs = ok;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cs += __shfl_xor(cs, o, 64);
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; redw[threadIdx.x >> 6] = ws; redc[threadIdx.x >> 6] = cs; }
+    __syncthreads();
+    float W = 0.f;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) W += redw[i];      // every thread, the same order
+    if (b < B) {
+        const float* z = logits + (size_t)b * C;
+        float* d = dlogits + (size_t)b * C;
+        if (!keep) {
+            for (int c = 0; c < C; ++c) d[c] = 0.f;
+        } else {
+            const float inv = reduction == 0 ? grad_scale / W : grad_scale;
+            if (!cw && !smooth) {
+                for (int c = 0; c < C; ++c) d[c] = (expf(z[c] - lse) - (c == y ? 1.f : 0.f)) * inv;
+            } else if (!smooth) {
+                for (int c = 0; c < C; ++c) d[c] = (wy * (expf(z[c] - lse) - (c == y ? 1.f : 0.f))) * inv;
+            } else {
+                const float awy = a * wy;
+                for (int c = 0; c < C; ++c) {
+                    const float p = expf(z[c] - lse);
+                    const float wc = cw ? cw[c] : 1.f;
+                    d[c] = (awy * (p - (c == y ? 1.f : 0.f)) + e * (sw * p - wc)) * inv;
+                }
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        int tc = 0;
+        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) { t += red[i]; tc += redc[i]; }
+        if (reduction == 0) *loss = t / W;
+        else if (reduction == 1) *loss = t;
+        if (n_correct) *n_correct = tc;
+    }
+}
+
+// binary cross-entropy with logits and a positive-class weight (F.binary_cross_entropy_with_logits(x, t, pos_weight=)) over
+// one logit per sample: l = (1 - t) softplus(x) + pw t softplus(-x), softplus(+-x) = max(+-x, 0) + log1p(exp(-|x|)) as in
+// focal_kernel; d l / d x = (1 - t) sigmoid(x) - pw t sigmoid(-x), both sigmoids from exp(-|x|) (no 1 - p cancellation).
+__global__ __launch_bounds__(1024) void bce_kernel(const float* __restrict__ logits, int ld, const float* __restrict__ targets,
+                                                   float pos_weight, float* __restrict__ loss, float* __restrict__ dlogits,
+                                                   int32_t* __restrict__ n_correct, int B, int reduction, float grad_scale,
+                                                   const float* __restrict__ grad_scale_dev) {
+    if (grad_scale_dev) grad_scale *= grad_scale_dev[0];
+    __shared__ float red[16];
+    __shared__ int redc[16];
+    const int b = threadIdx.x;
+    const float den = reduction == 0 ? (float)B : 1.f;
+    float li = 0.f;
+    int ok = 0;
+    if (b < B) {
+        const float x = logits[(size_t)b * ld], t = targets[b];
+        const float ex = expf(-fabsf(x));
+        const float l1p = log1pf(ex);
+        const float sp = fmaxf(x, 0.f) + l1p, sn = fmaxf(-x, 0.f) + l1p;      // softplus(x), softplus(-x)
+        const float big = 1.0f / (1.0f + ex), small = ex / (1.0f + ex);
+        const float p = x >= 0.f ? big : small, q = x >= 0.f ? small : big;   // sigmoid(x), sigmoid(-x)
+        const float pt = pos_weight * t;
+        li = (1.f - t) * sp + pt * sn;
+        dlogits[(size_t)b * ld] = ((1.f - t) * p - pt * q) * grad_scale / den;
+        ok = ((x > 0.f) == (t > 0.5f));
+    }
+    float s = wave_sum(li);
+    int cs = ok;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cs += __shfl_xor(cs, o, 64);
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; redc[threadIdx.x >> 6] = cs; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float tt = 0.f;
+        int tc = 0;
+        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) { tt += red[i]; tc += redc[i]; }
+        *loss = tt / den;
+        if (n_correct) *n_correct = tc;
+    }
+}
+
 void add_fwd(LinFwdJobs& L, const float* x, int ldx, const float* W, const float* b, float* y, int ldy, int M, int N,
              int K) {
     LinFwdJobs::J& j = L.j[L.n++];
@@ -364,6 +499,31 @@ extern "C" int mh_focal_fwd_bwd(const float* logits, int ld, const float* target
     const int threads = ((B + 63) / 64) * 64;
     hipLaunchKernelGGL(focal_kernel, dim3(1), dim3(threads), 0, (hipStream_t)stream, logits, ld, targets, loss, dlogits,
                        n_correct, B, alpha, gamma, grad_scale, grad_scale_dev);
+    return mh_launch_status();
+}
+
+extern "C" int mh_ce_opts_fwd_bwd(const float* logits, const int64_t* labels, const float* class_weight, float* loss,
+                                  float* dlogits, int32_t* n_correct, int B, int C, int64_t ignore_index, int has_ignore,
+                                  float label_smoothing, int reduction, float grad_scale, const float* grad_scale_dev,
+                                  mh_stream_t stream) {
+    if (!logits || !labels || !loss || !dlogits) return MH_EINVAL;
+    if (B < 1 || B > 1024 || C < 1) return MH_ESHAPE;
+    if (!(label_smoothing >= 0.f && label_smoothing <= 1.f) || reduction < 0 || reduction > 2) return MH_ESHAPE;
+    const int threads = ((B + 63) / 64) * 64;
+    hipLaunchKernelGGL(ce_opts_kernel, dim3(1), dim3(threads), 0, (hipStream_t)stream, logits, labels, class_weight, loss,
+                       dlogits, n_correct, B, C, ignore_index, has_ignore != 0, label_smoothing, reduction, grad_scale,
+                       grad_scale_dev);
+    return mh_launch_status();
+}
+
+extern "C" int mh_bce_fwd_bwd(const float* logits, int ld, const float* targets, float pos_weight, float* loss,
+                              float* dlogits, int32_t* n_correct, int B, int reduction, float grad_scale,
+                              const float* grad_scale_dev, mh_stream_t stream) {
+    if (!logits || !targets || !loss || !dlogits) return MH_EINVAL;
+    if (B < 1 || B > 1024 || ld < 1 || reduction < 0 || reduction > 1) return MH_ESHAPE;
+    const int threads = ((B + 63) / 64) * 64;
+    hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(threads), 0, (hipStream_t)stream, logits, ld, targets, pos_weight, loss,
+                       dlogits, n_correct, B, reduction, grad_scale, grad_scale_dev);
     return mh_launch_status();
 }
 

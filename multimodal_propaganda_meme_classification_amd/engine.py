@@ -136,6 +136,15 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+class LossOptions(NamedTuple):
+    """The scalar options of the fused step's loss (mh_ce_opts_fwd_bwd); hashable: part of a plan's key.  The class-weight VALUES are not
+    part of it -- they live in one device buffer and may change under a built (or captured) plan -- only whether there are any."""
+    weighted: bool
+    ignore_index: Optional[int]
+    label_smoothing: float
+    reduction: str              # "mean" | "sum"
+
+
 class Plan:
     def __init__(self, B: int, S: int, lib=None):
         self.B, self.S = B, S
@@ -157,6 +166,7 @@ class Plan:
         self.packed = False
         self.dropout_on = False               # some dropout probability is non-zero in this plan
         self.features = False                 # False | True | "sequence": where the plan stops (Engine.plan)
+        self.loss_opts = None                 # the LossOptions the loss launch was built with (None: mh_ce_fwd_bwd)
         self.last_rows = "all"                # "pooled": the blocks behind the last attention run on the B pooled rows only
         self.gather = None                    # data parallel: (local, gathered) tensor pairs exchanged before "bwd_embed_tables"
         self._ln_jobs: Dict[int, list] = {}   # width -> (partials, dgamma, dbeta) of every LayerNorm backward, summed in "bwd_embed"
@@ -183,6 +193,10 @@ class Engine:
         self.word_count = torch.zeros(cfg.text.vocab_size, dtype=torch.int32, device=self.dev)
         # dynamic loss scale read by the fused loss launch (1 = none; a memehip.GradScaler attached to the model owns it)
         self.loss_scale = torch.ones(1, dtype=F32, device=self.dev)
+        # the fused step's loss (model.set_loss_options): None = the plain mean cross-entropy (mh_ce_fwd_bwd); otherwise a LossOptions,
+        # part of every plan's key, and the model-owned class-weight buffer the loss launch of such plans points at
+        self.loss_opts: Optional[LossOptions] = None
+        self.class_weight: Optional[torch.Tensor] = None
         # gradient accumulation over micro-batches (model.set_grad_accumulation): a scratch mirror of the small gradients' run of the
         # flat buffer (n_shadow .. the word table; allocated on first use) and the token ids of every ADDING backward of the
         # current window, whose word-table rows the first backward of the next window has to clear
@@ -290,6 +304,8 @@ class Engine:
         features = features if features == "sequence" else bool(features)
         pack = self.pack_text and features != "sequence"
         key = (B, S, bool(training and has_drop), int(gather_world), pack, features) + (() if last_rows == "pooled" else (last_rows,))
+        if self.loss_opts is not None and not features:     # (no options: the key, the plan and its launches are the plain loss's)
+            key += (self.loss_opts,)
         if key not in self.plans:
             self.plans[key] = self._build(B, S, key[2], key[3], key[4], key[5], last_rows=last_rows)
         return self.plans[key]
@@ -833,8 +849,16 @@ class _PlanBuilder:
         labels, loss = alloc("labels", (B,), I64, zero=True), alloc("loss", (1,), F32, zero=True)
         self.dlogits = alloc("dlogits", (B, Cn), F32, zero=True)
         ncorrect = alloc("ncorrect", (1,), torch.int32, zero=True)
-        pl.loss.c("mh_ce_fwd_bwd", _ptr(logits), _ptr(labels), _ptr(loss), _ptr(self.dlogits), _ptr(ncorrect), B, Cn,
-                  1.0, _ptr(eng.loss_scale))
+        opts = None if pl.features else eng.loss_opts      # (a features plan never runs its loss segment)
+        pl.loss_opts = opts
+        if opts is None:
+            pl.loss.c("mh_ce_fwd_bwd", _ptr(logits), _ptr(labels), _ptr(loss), _ptr(self.dlogits), _ptr(ncorrect), B, Cn,
+                      1.0, _ptr(eng.loss_scale))
+        else:
+            assert not opts.weighted or (eng.class_weight is not None and eng.class_weight.numel() == Cn)
+            pl.loss.c("mh_ce_opts_fwd_bwd", _ptr(logits), _ptr(labels), _ptr(eng.class_weight) if opts.weighted else None, _ptr(loss),
+                      _ptr(self.dlogits), _ptr(ncorrect), B, Cn, opts.ignore_index or 0, int(opts.ignore_index is not None),
+                      opts.label_smoothing, _lib.MH_LOSS_SUM if opts.reduction == "sum" else _lib.MH_LOSS_MEAN, 1.0, _ptr(eng.loss_scale))
 
     # ---- backward -------------------------------------------------------------------------------------------------
     def bwd_head(self):

@@ -29,7 +29,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from .config import Layout, ModelConfig, TextConfig, ImageConfig  # noqa: F401
-from .engine import Engine, Plan
+from .engine import Engine, LossOptions, Plan
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -143,19 +143,70 @@ class _LossFn(torch.autograd.Function):
         return ctx.dl * gout, None, None
 
 
-class CrossEntropyLoss(nn.Module):
-    """nn.CrossEntropyLoss() stand-in (mean reduction) running the fused HIP loss kernel; also
-    exposes ``last_correct`` = #argmax==label of the last call (the reference computes it with
-    torch.max, ...task2C.txt:219-220)."""
+class _LossOptsFn(torch.autograd.Function):
+    """mh_ce_opts_fwd_bwd as an autograd node; with reduction "none" the kernel leaves each row's own derivative and the
+    upstream gradient is multiplied in per row."""
 
-    def __init__(self):
+    @staticmethod
+    def forward(ctx, logits, labels, crit):
+        B, Cn = logits.shape
+        none = crit.reduction == "none"
+        w = crit._workspace(logits.device, B, Cn)
+        ops.ce_opts_fwd_bwd(logits.contiguous(), labels, w["loss"], w["dlogits"], w["ncorrect"], class_weight=crit.weight,
+                            ignore_index=crit.ignore_index, label_smoothing=crit.label_smoothing, reduction=crit.reduction)
+        ctx.dl, ctx.none = w["dlogits"], none
+        return w["loss"].clone() if none else w["loss"][0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        return ctx.dl * (gout.to(F32)[:, None] if ctx.none else gout), None, None
+
+
+def check_loss_options(weight, ignore_index, label_smoothing, reduction, reductions=("mean", "sum", "none")):
+    """Host-side validation shared by CrossEntropyLoss and MultimodalClassifier.set_loss_options; returns the weight as a
+    1-D f32 tensor (or None)."""
+    if reduction not in reductions:
+        raise ValueError("reduction must be one of " + ", ".join(repr(r) for r in reductions) + f", got {reduction!r}")
+    if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, (int, float)) or not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"label_smoothing must be a number in [0, 1], got {label_smoothing!r}")
+    if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, int)):
+        raise ValueError(f"ignore_index must be an int or None (no label is ignored), got {ignore_index!r}")
+    if weight is not None:
+        weight = torch.as_tensor(weight).detach().to(F32)
+        if weight.dim() != 1 or weight.numel() < 1:
+            raise ValueError(f"weight must be a 1-D tensor with one entry per class, got shape {tuple(weight.shape)}")
+        if not bool(torch.isfinite(weight).all()) or bool((weight < 0).any()):
+            raise ValueError("weight must be finite and non-negative")
+    return weight
+
+
+class CrossEntropyLoss(nn.Module):
+    """nn.CrossEntropyLoss stand-in running the fused HIP loss kernels; also exposes ``last_correct`` = #argmax==label of the
+    last call, over the rows that are not ignored (the reference computes it with torch.max, ...task2C.txt:219-220).
+
+    ``CrossEntropyLoss()`` is the reference's criterion (mean over the batch, mh_ce_fwd_bwd).  ``weight`` (one entry per class,
+    e.g. ``balanced_class_weights(labels)`` -- ``nn.CrossEntropyLoss(weight=class_weights)``, Multimodal_example_task2C.py:166),
+    ``ignore_index``, ``label_smoothing`` and ``reduction`` ("mean" / "sum" / "none") have torch's meaning and run
+    mh_ce_opts_fwd_bwd.  ONE difference from torch: ``ignore_index`` defaults to ``None`` -- no label is ignored, and a label
+    outside [0, C) is read as class 0 -- so torch's default of ``-100`` must be asked for: ``CrossEntropyLoss(ignore_index=-100)``.
+    ``weight`` is a non-persistent buffer: it moves with ``.to()`` and is not part of any ``state_dict()``."""
+
+    def __init__(self, weight=None, ignore_index: Optional[int] = None, label_smoothing: float = 0.0, reduction: str = "mean"):
         super().__init__()
+        weight = check_loss_options(weight, ignore_index, label_smoothing, reduction)
+        self.register_buffer("weight", weight, persistent=False)
+        self.ignore_index, self.label_smoothing, self.reduction = ignore_index, float(label_smoothing), reduction
         self._ws: Dict = {}
 
+    @property
+    def _plain(self) -> bool:
+        return self.weight is None and self.ignore_index is None and self.label_smoothing == 0.0 and self.reduction == "mean"
+
     def _workspace(self, device, B, Cn):
-        key = (str(device), B, Cn)
+        key = (str(device), B, Cn, self.reduction == "none")
         if key not in self._ws:
-            self._ws[key] = dict(loss=torch.zeros(1, device=device), dlogits=torch.zeros((B, Cn), device=device),
+            self._ws[key] = dict(loss=torch.zeros(B if self.reduction == "none" else 1, device=device),
+                                 dlogits=torch.zeros((B, Cn), device=device),
                                  ncorrect=torch.zeros(1, dtype=torch.int32, device=device))
         self._last = self._ws[key]
         return self._ws[key]
@@ -167,7 +218,14 @@ class CrossEntropyLoss(nn.Module):
     def forward(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         if not logits.is_cuda:
             raise _lib.MemehipError("CrossEntropyLoss: logits must be on the HIP device (no CPU fallback)")
-        return _LossFn.apply(logits, labels, self)
+        if self._plain:
+            return _LossFn.apply(logits, labels, self)
+        if self.weight is not None:
+            if self.weight.numel() != logits.shape[1]:
+                raise ValueError(f"CrossEntropyLoss: weight has {self.weight.numel()} entries, the logits have {logits.shape[1]} classes")
+            if self.weight.device != logits.device:
+                raise _lib.MemehipError("CrossEntropyLoss: weight is not on the logits' device; move the criterion with .to(device)")
+        return _LossOptsFn.apply(logits, labels, self)
 
 
 class _FocalFn(torch.autograd.Function):
@@ -253,6 +311,74 @@ class SigmoidFocalLoss(nn.Module):
         return _FocalFn.apply(logits, targets, self)
 
 
+class _BceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets, crit):
+        flat = logits.reshape(-1).contiguous()
+        w = crit._workspace(logits.device, flat.numel())
+        ops.bce_fwd_bwd(flat, targets.to(F32).reshape(-1).contiguous(), w["loss"], w["dlogits"], w["ncorrect"],
+                        pos_weight=crit.pos_weight, reduction=crit.reduction)
+        ctx.dl, ctx.shape = w["dlogits"], logits.shape
+        return w["loss"][0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        return (ctx.dl * gout).view(ctx.shape), None, None
+
+
+class BCEWithLogitsLoss(nn.Module):
+    """``nn.BCEWithLogitsLoss(pos_weight=...)`` on one logit per sample (a model built with ``num_classes=1``), running
+    mh_bce_fwd_bwd: the class-weighted alternative to the focal loss for the 1-logit head.  ``pos_weight`` is one number
+    (``n_neg / n_pos`` of the training fold balances the classes); ``reduction`` "mean" or "sum".  Callable as
+    ``criterion(output, labels)``; the ``alpha=`` / ``gamma=`` keywords of the focal call (Multimodal_example_task2C.py:711)
+    are accepted and ignored, so ``kevin.train`` / ``kevin.test`` run with it unchanged."""
+
+    def __init__(self, pos_weight=None, reduction: str = "mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"BCEWithLogitsLoss supports reduction 'mean' or 'sum', got {reduction!r}")
+        if pos_weight is None:
+            pos_weight = 1.0
+        if isinstance(pos_weight, torch.Tensor):
+            if pos_weight.numel() != 1:
+                raise ValueError("BCEWithLogitsLoss: pos_weight must be one number (one logit per sample)")
+            pos_weight = pos_weight.item()
+        pos_weight = float(pos_weight)
+        if not (math.isfinite(pos_weight) and pos_weight >= 0.0):
+            raise ValueError(f"pos_weight must be finite and non-negative, got {pos_weight!r}")
+        self.pos_weight, self.reduction = pos_weight, reduction
+        self._ws: Dict = {}
+
+    _workspace = SigmoidFocalLoss._workspace
+    last_correct = SigmoidFocalLoss.last_correct
+
+    def forward(self, logits, targets, alpha=None, gamma=None, reduction: Optional[str] = None):
+        if reduction is not None and reduction != self.reduction:
+            raise ValueError(f"BCEWithLogitsLoss was built with reduction={self.reduction!r}; the call asks for {reduction!r}")
+        if not logits.is_cuda:
+            raise _lib.MemehipError("BCEWithLogitsLoss: logits must be on the HIP device (no CPU fallback)")
+        if logits.numel() != targets.numel():
+            raise ValueError(f"BCEWithLogitsLoss: one logit per sample: {tuple(logits.shape)} logits for {tuple(targets.shape)} targets")
+        return _BceFn.apply(logits, targets, self)
+
+
+def balanced_class_weights(labels, num_classes: Optional[int] = None):
+    """sklearn's ``compute_class_weight('balanced', classes=arange(C), y=labels)`` on the host (Multimodal_example_task2C.py:136-139):
+    ``n / (n_classes * bincount(labels))`` as a float64 numpy array, ready for ``CrossEntropyLoss(weight=...)``.  A class without
+    a sample is an error, as in sklearn."""
+    import numpy as np
+    y = np.asarray(labels.detach().cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)
+    if y.size == 0 or not np.issubdtype(y.dtype, np.integer) or int(y.min()) < 0:
+        raise ValueError("balanced_class_weights: labels must be a non-empty array of non-negative integers")
+    n_classes = int(y.max()) + 1 if num_classes is None else int(num_classes)
+    if int(y.max()) >= n_classes:
+        raise ValueError(f"balanced_class_weights: label {int(y.max())} with num_classes={n_classes}")
+    counts = np.bincount(y, minlength=n_classes).astype(np.float64)
+    if (counts == 0).any():
+        raise ValueError(f"balanced_class_weights: no sample of class(es) {np.flatnonzero(counts == 0).tolist()}")
+    return y.size / (n_classes * counts)
+
+
 def get_linear_schedule_with_warmup(optimizer, num_warmup_steps: int, num_training_steps: int, last_epoch: int = -1):
     """transformers.get_linear_schedule_with_warmup (Multimodal_example_task2C.py:172-174): lr multiplier rises
     linearly 0 -> 1 over the warm-up steps, then decays linearly to 0 at num_training_steps."""
@@ -299,6 +425,9 @@ class MultimodalClassifier(nn.Module):
         # overwrites when the gradients were cleared since the previous one (_grads_cleared) and adds otherwise.
         self._accum = False
         self._cleared = True
+        # the fused step's loss (set_loss_options): None = the plain mean cross-entropy; the class weights' one device buffer
+        self._loss_opts: Optional[LossOptions] = None
+        self._loss_weight: Optional[torch.Tensor] = None
         if init:
             self.reset_parameters(seed)
         self._attach_grads()
@@ -349,6 +478,8 @@ class MultimodalClassifier(nn.Module):
             self._P = new_p
             self._G = fn(self._G)
             self._SH = torch.zeros(self.layout.n_shadow, dtype=self._T16, device=new_p.device)
+            if self._loss_weight is not None:
+                self._loss_weight = fn(self._loss_weight)
             for name, prm in self._params.items():
                 s = self.layout.spec[name]
                 prm.data = self._P[s.offset:s.offset + s.numel].view(s.shape)
@@ -380,7 +511,33 @@ class MultimodalClassifier(nn.Module):
                                     "(libmemehip has no CPU fallback)")
         if self._engine is None:
             self._engine = Engine(self.config, self.layout, self._P, self._G, self._SH)
+        self._engine.loss_opts, self._engine.class_weight = self._loss_opts, self._loss_weight
         return self._engine
+
+    # ---- the fused step's loss ---------------------------------------------------------------------------------------
+    def set_loss_options(self, weight=None, ignore_index: Optional[int] = None, label_smoothing: float = 0.0, reduction: str = "mean"):
+        """The loss of the fused step (``forward_backward``, ``GraphedStep``): ``CrossEntropyLoss``'s arguments, reduction "mean" or
+        "sum" (the step returns one loss).  With every argument at its default the step runs the plain mean cross-entropy, as
+        built before any call.  The scalar options are part of a launch plan's key: changing them takes effect on the next step
+        (a ``GraphedStep`` captures the new plan).  The class weights live in ONE device buffer owned by the model, which every
+        plan's loss launch reads: new values of the same length are copied into it in place, also under a captured step.
+        The autograd route -- ``criterion(model(...), labels)`` -- takes its options from the criterion, not from here."""
+        weight = check_loss_options(weight, ignore_index, label_smoothing, reduction, reductions=("mean", "sum"))
+        if weight is not None and weight.numel() != self.config.num_classes:
+            raise ValueError(f"weight has {weight.numel()} entries, the model has {self.config.num_classes} classes")
+        if weight is not None:
+            if self._loss_weight is None:       # allocated once and kept (also while no weights are asked for): built plans point at it
+                self._loss_weight = torch.empty(self.config.num_classes, dtype=F32, device=self._P.device)
+            self._loss_weight.copy_(weight)
+        plain = weight is None and ignore_index is None and label_smoothing == 0.0 and reduction == "mean"
+        self._loss_opts = None if plain else LossOptions(weight is not None, ignore_index, float(label_smoothing), reduction)
+        if self._engine is not None:
+            self._engine.loss_opts, self._engine.class_weight = self._loss_opts, self._loss_weight
+        return self
+
+    @property
+    def loss_options(self) -> Optional[LossOptions]:
+        return self._loss_opts
 
     def refresh_shadow(self):
         """bf16 copy of the GEMM matrices (kept in sync by Adam.step(); call after editing weights by hand)."""
@@ -1357,8 +1514,9 @@ class GraphedStep:
             scaler.attach_model(model)
             optimizer._attach_scaler(scaler)
         self.scaler = scaler
+        self._plan_args = (batch, seq_len, True, reducer.world if reducer is not None else 0, last_rows)
         eng = model._get_engine()
-        self.plan = eng.plan(batch, seq_len, True, gather_world=(reducer.world if reducer is not None else 0), last_rows=last_rows)
+        self.plan = eng.plan(*self._plan_args[:3], gather_world=self._plan_args[3], last_rows=last_rows)
         if model.weights_changed():
             model.refresh_shadow()
         from . import ddp as _ddp
@@ -1403,13 +1561,34 @@ class GraphedStep:
         if want_side and mode == "segments":        # (after `ddp_side`: the order in which torch's pool has always handed them out here)
             self.side = torch.cuda.Stream()
         # MEMEHIP_DDP_GROUP is read here and nowhere else; a single GPU has nothing to batch: one segment per bucket
-        group = max(1, int(os.environ.get("MEMEHIP_DDP_GROUP", "2"))) if reducer is not None else 1
-        self.buckets = gradient_buckets(self.plan.bwd, self.plan.bucket_after, group)
+        self._bucket_group = max(1, int(os.environ.get("MEMEHIP_DDP_GROUP", "2"))) if reducer is not None else 1
+        self._bind_plan()
+        self.closed = False
+        _ddp._LIVE_STEPS.add(self)
+
+    def _bind_plan(self):
+        """Everything that is derived from ``self.plan``: the gradient buckets, the early Adam ranges and the schedule."""
+        self.buckets = gradient_buckets(self.plan.bwd, self.plan.bucket_after, self._bucket_group)
         # the ranges whose Adam slice has run by the time the optimizer tail is launched (its ``skip=``)
         self.early = [r for b in self.buckets if b.layers for r in b.rngs] if (self.opt_in_bwd or self.ddp_opt_in_bwd) else []
         self.units, self.groups = self._schedule()
-        self.closed = False
-        _ddp._LIVE_STEPS.add(self)
+
+    def _follow_loss_options(self):
+        """The model's loss options (set_loss_options) are part of the plan's key: when they differ from the ones this step's plan was
+        built with, the step moves to the plan of the new options and drops its captured graphs -- it never replays a capture of the
+        old loss launch.  (New class-weight VALUES alone change neither: they are copied into the buffer the launch reads.)"""
+        if self.model.loss_options == self.plan.loss_opts:
+            return
+        torch.cuda.synchronize()
+        for g, _, _ in reversed(self.graphs or []):
+            g.reset()
+        self.graphs = None
+        old = self.plan
+        eng = self.model._get_engine()
+        self.plan = eng.plan(*self._plan_args[:3], gather_world=self._plan_args[3], last_rows=self._plan_args[4])
+        for k in ("ids", "mask", "image", "labels"):        # the batch load_batch() put into the old plan's input buffers
+            self.plan.buf[k].copy_(old.buf[k])
+        self._bind_plan()
 
     @staticmethod
     def _refuse_accumulation(model):
@@ -1587,6 +1766,7 @@ class GraphedStep:
         if self.closed:
             raise RuntimeError("GraphedStep is closed")
         self._refuse_accumulation(self.model)
+        self._follow_loss_options()
         opt = self.opt
         if opt._flat is None:
             self.model._attach_grads()

@@ -658,6 +658,44 @@ def focal_fwd_bwd(logits, targets, loss, dlogits, n_correct=None, alpha=0.25, ga
                                        float(gamma), float(grad_scale), _p(grad_scale_dev), _stream()), "mh_focal_fwd_bwd")
 
 
+REDUCTIONS = {"mean": _lib.MH_LOSS_MEAN, "sum": _lib.MH_LOSS_SUM, "none": _lib.MH_LOSS_NONE}
+
+
+def ce_opts_fwd_bwd(logits, labels, loss, dlogits, n_correct=None, class_weight=None, ignore_index=None, label_smoothing: float = 0.0,
+                    reduction: str = "mean", grad_scale: float = 1.0, grad_scale_dev=None):
+    """mh_ce_opts_fwd_bwd: F.cross_entropy(weight=, ignore_index=, label_smoothing=, reduction=).  ``ignore_index=None``: no label is
+    ignored.  ``loss`` holds 1 value, or B with reduction "none" (dlogits is then each row's own derivative)."""
+    _chk(logits, F32, "logits"), _chk(labels, I64, "labels"), _chk(loss, F32, "loss"), _chk(dlogits, F32, "dlogits")
+    B, Cn = logits.shape
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
+    assert labels.numel() >= B and dlogits.numel() >= B * Cn and loss.numel() >= (B if reduction == "none" else 1)
+    if n_correct is not None:
+        _chk(n_correct, torch.int32, "n_correct")
+    if class_weight is not None:
+        _chk(class_weight, F32, "class_weight")
+        if class_weight.numel() != Cn:
+            raise ValueError(f"class_weight has {class_weight.numel()} entries for {Cn} classes")
+    check(_lib.load().mh_ce_opts_fwd_bwd(_p(logits), _p(labels), _p(class_weight), _p(loss), _p(dlogits), _p(n_correct), B, Cn,
+                                         0 if ignore_index is None else int(ignore_index), int(ignore_index is not None),
+                                         float(label_smoothing), REDUCTIONS[reduction], float(grad_scale), _p(grad_scale_dev), _stream()),
+          "mh_ce_opts_fwd_bwd")
+
+
+def bce_fwd_bwd(logits, targets, loss, dlogits, n_correct=None, pos_weight: float = 1.0, reduction: str = "mean", grad_scale=1.0,
+                grad_scale_dev=None, ld: int = 1):
+    """mh_bce_fwd_bwd: logits f32 [B] or [B,1] (or column 0 of [B, ld]); targets f32 [B]; dlogits laid out like logits."""
+    _chk(logits, F32, "logits"), _chk(targets, F32, "targets"), _chk(loss, F32, "loss"), _chk(dlogits, F32, "dlogits")
+    B = targets.numel()
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"reduction must be 'mean' or 'sum', got {reduction!r}")
+    assert ld >= 1 and logits.numel() >= (B - 1) * ld + 1 and dlogits.numel() >= (B - 1) * ld + 1
+    if n_correct is not None:
+        _chk(n_correct, torch.int32, "n_correct")
+    check(_lib.load().mh_bce_fwd_bwd(_p(logits), int(ld), _p(targets), float(pos_weight), _p(loss), _p(dlogits), _p(n_correct), B,
+                                     REDUCTIONS[reduction], float(grad_scale), _p(grad_scale_dev), _stream()), "mh_bce_fwd_bwd")
+
+
 def sumsq(g, workspace, out):
     _chk(g, F32, "g"), _chk(workspace, F32, "workspace"), _chk(out, F32, "out")
     assert workspace.numel() >= 1024
