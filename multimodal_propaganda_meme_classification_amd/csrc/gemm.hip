@@ -341,7 +341,8 @@ __global__ __launch_bounds__(512, 4) void gemm_kernel(const GemmGroup g) {
     // (static s_setprio(1) for waves 4-7 -- the younger half of the workgroup, MI355X_MICROARCH.md "two waves per SIMD" item 4 -- measured:
     //  10.12-10.18 ms per step against 10.09-10.11, same box, three alternations: nothing)
     f32x4 acc[NI][NJ];
-    k_loop<LA, LB>(
+    // (SCOPED = true: without it the K-strided fragment reads drained the next stage's DMA at the top of every K step, gemm_tile.h)
+    k_loop<LA, LB, true>(
         acc, smem, nk, wave, lane,
         [&](int kt, char* st) {
             dma_tile<LA>(ra, P.lda, m0, kbeg + kt * BK, wave, lane, st);

@@ -72,6 +72,18 @@ MH_DEV h16x8 read_frag(const char* lds, int rb, int kk, int lane) {
     }
 }
 
+// The same read with an alias scope on it.  While an LDS-DMA is pending, hipcc puts `s_waitcnt vmcnt(0)` in front of every LDS read that
+// carries no alias information: the plain ds_read_b128 loads carry their type's, the ds_read_tr16_b64 builtin carries none.  In k_loop
+// the DMA of K tile kt + 1 is issued at the top of step kt, so the K-strided fragment reads of tile kt waited for it to land -- the two
+// stages ran one after the other in every launch with a K-strided operand (dgrad, wgrad), one memory round trip per K step.  Inlining
+// through a __restrict__ parameter attaches a scope to the builtin's call, and the wait goes away (tools/isa_loadchain.py: the loop
+// reads `D D D D w0 |` instead of `D D D D w0 ... w0 |`).  The wait was never needed: a stage is read only after the barrier that
+// follows the vmcnt(0) of the step that filled it.
+template <int KMAJOR>
+MH_DEV h16x8 read_frag_scoped(const char* __restrict__ lds, int rb, int kk, int lane) {
+    return read_frag<KMAJOR>(lds, rb, kk, lane);
+}
+
 // f32 staging tile [rows][128]: the accumulator layout makes the four 16-lane groups of a wave write rows r, r+4, r+8,
 // r+12 of the SAME 16 columns -- with 512-B rows that is the same 16 banks four times.  The 16-column block index is
 // therefore XOR-ed with (row >> 2) & 3: the four groups land on four different 16-bank quarters (conflict-free), and a
@@ -121,7 +133,8 @@ struct NoHook {
 // acc = this wave's NI x NJ accumulators over nk K tiles.  issue(kt, stage) starts the LDS-DMA of K tile kt into `stage` (A image at
 // stage, B image at stage + BM * BK * 2); two stages alternate, the next one issued before the MFMAs of the current one, ONE barrier
 // per K tile.  a_hook(fa) runs after each 32-deep k-step's MFMAs with its A fragments; landed() right after the first stage's barrier.
-template <int LA, int LB, class Issue, class AHook = NoHook, class Landed = NoHook>
+// SCOPED: fragment reads through read_frag_scoped (gemm_kernel; conv_gemm_kernel keeps the plain ones until it has its own A/B).
+template <int LA, int LB, bool SCOPED = false, class Issue, class AHook = NoHook, class Landed = NoHook>
 MH_DEV void k_loop(f32x4 (&acc)[NI][NJ], char* smem, int nk, int wave, int lane, Issue issue, AHook a_hook = {}, Landed landed = {}) {
     const int wm0 = wave_m0(wave), wn0 = wave_n0(wave);
 #pragma unroll
@@ -141,9 +154,9 @@ MH_DEV void k_loop(f32x4 (&acc)[NI][NJ], char* smem, int nk, int wave, int lane,
         for (int kk = 0; kk < 2; ++kk) {
             h16x8 fa[NI], fb[NJ];
 #pragma unroll
-            for (int i = 0; i < NI; ++i) fa[i] = read_frag<LA>(la, wm0 + i * 16, kk, lane);
+            for (int i = 0; i < NI; ++i) fa[i] = SCOPED ? read_frag_scoped<LA>(la, wm0 + i * 16, kk, lane) : read_frag<LA>(la, wm0 + i * 16, kk, lane);
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) fb[j] = read_frag<LB>(lb, wn0 + j * 16, kk, lane);
+            for (int j = 0; j < NJ; ++j) fb[j] = SCOPED ? read_frag_scoped<LB>(lb, wn0 + j * 16, kk, lane) : read_frag<LB>(lb, wn0 + j * 16, kk, lane);
 #pragma unroll
             for (int i = 0; i < NI; ++i)
 #pragma unroll
