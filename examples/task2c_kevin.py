@@ -27,6 +27,10 @@ convnext.ConvNeXtTiny through its differentiable tower() under FineTuneMLP(768, 
 underflows in fp16's folded weight (a released checkpoint's 0.1 ... 1 does not).
 --caption-model roberta: the caption tower is the submitted model's ``english_text_model = "roberta-base"`` (:81) --
 TextConfig.roberta_base (position ids from the input ids) with the RoBERTa tokenizers' special ids.
+--caption-repetition-penalty P / --caption-no-repeat-ngram-size N / --caption-min-new-tokens M: generate() settings of the caption
+stage (BlipCaptioner.generate; kevin.blip_caption_fn passes the same keywords through).  The defaults are neutral: the reference's
+caption stage.  With any of them set, a small random BLIP captions the synthetic images with them and the caption tower reads
+those ids.
 """
 import argparse
 import os
@@ -47,6 +51,9 @@ def main():
                     help="N > 1: every step accumulates the gradients of N micro-batches (the batch in N parts, loss / N)")
     ap.add_argument("--criterion", choices=("focal", "bce"), default="focal")
     ap.add_argument("--pos-weight", default="1", help="with --criterion bce: a number, or 'balanced' = n_neg / n_pos of the training labels")
+    ap.add_argument("--caption-repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--caption-no-repeat-ngram-size", type=int, default=0)
+    ap.add_argument("--caption-min-new-tokens", type=int, default=0)
     args = ap.parse_args()
     small, roberta, resnet = not args.full, args.caption_model == "roberta", args.image_model == "resnet18"
     convnext = args.image_model == "convnext_tiny"
@@ -78,6 +85,25 @@ def main():
     mask = (torch.arange(S)[None] < lens[:, None]).long()
     image = torch.randn((B, 3, ic.image_size, ic.image_size), generator=g)
     labels = (torch.rand(B, generator=g) < 0.28).float().to(device)
+    caption_kw = dict(repetition_penalty=args.caption_repetition_penalty, no_repeat_ngram_size=args.caption_no_repeat_ngram_size,
+                      min_new_tokens=args.caption_min_new_tokens)
+    if caption_kw != dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
+        # the caption stage (ImageCaptioning, :195-256) with these generate() settings: a random BLIP of the small towers' size writes
+        # the caption ids the caption tower reads (no checkpoint or tokenizer offline, so the ids stand for themselves)
+        if not small:
+            ap.error("the --caption-* generate settings run the synthetic caption stage of the small configuration (omit --full)")
+        blip = memehip.BlipCaptioner.from_config(dict(
+            text_config=dict(vocab_size=cc.vocab_size, hidden_size=128, encoder_hidden_size=128, intermediate_size=256, num_hidden_layers=2,
+                             num_attention_heads=2, max_position_embeddings=64, bos_token_id=cc.vocab_size - 2, sep_token_id=102,
+                             pad_token_id=0),
+            vision_config=dict(hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=2,
+                               image_size=ic.image_size, patch_size=16)), device=device)
+        for p in blip.parameters():
+            torch.nn.init.normal_(p, std=0.1)
+        ids = blip.generate(image.to(device), torch.tensor([[101, 7, 8, 9, 102]] * B), max_new_tokens=S - 8, **caption_kw).cpu()
+        ids = ids[:, 4:]                                   # the generated part
+        cap[:, :ids.shape[1]] = ids.clamp(min=5)
+        print(f"caption stage: generate({caption_kw}) wrote {ids.shape[1]} tokens per image; first row {ids[0, :12].tolist()}")
     cap, cap_mask = cap * mask, mask
     if roberta:         # captions through the tokenizer: <s> words </s> <pad>...; the position ids follow the pad pattern
         tok = memehip.HashTokenizer.roberta(cc.vocab_size)

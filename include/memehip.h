@@ -869,7 +869,33 @@ int mh_accum_spans_f32(const MhSpanJob* jobs /*host*/, int n_jobs, mh_stream_t s
  *   The sequences (int32 [B*K][cap]) and src are permuted by parent in place; src[row][t] becomes the parent's row.
  *   Start: run_scores {0, -1e9, ...} per image, fin_scores -1e9, fin_flags 0, fin_len 0, heur 1, state 0, run_seq = fin_seq =
  *   the prompt padded with pad_id, next_ids the prompt's first token.  V >= 2K; logits must be finite or -inf.
+ *
+ * Logits processors (MhLogitsProcess; mh_greedy_step_processed / mh_beam_step_processed are the two calls above plus one, and the
+ * two calls above are these with the neutral settings {1, 0, 0, 0}, which launch the kernels without any processing).  They are
+ * transformers' own, in _get_logits_processor's order, over the row's history: its cur_len = t + 1 tokens so far, prompt included
+ * (greedy: out_ids[b][0..t]; beams: run_seq[row][0..t], which already follows the row's parent).  Nothing is processed inside the
+ * prompt (t + 1 < prompt_len).
+ *   1. repetition_penalty p (RepetitionPenaltyLogitsProcessor): every distinct id of the history gets s = s < 0 ? s * p : s / p,
+ *      once however often it occurs.  p finite and > 0; 1 is neutral.
+ *   2. no_repeat_ngram_size n (NoRepeatNGramLogitsProcessor): wherever the last n - 1 tokens occur earlier in the history, the
+ *      token that followed them becomes -inf (n = 1: every token seen).  Nothing is banned while cur_len < n.  0 is neutral.
+ *   3. min_length (MinLengthLogitsProcessor): eos_id is -inf while cur_len < min_length (the prompt counts).
+ *   4. min_new_tokens (MinNewTokensLengthLogitsProcessor): eos_id is -inf while cur_len - prompt_len < min_new_tokens.
+ *   Greedy: they act on the raw f32 logits, before the argmax (an all -inf row picks 0).  Beams: they act on the row's f32
+ *   log-softmax -- the log-sum-exp is taken over the unprocessed logits, the penalty therefore acts on values <= 0 -- before the
+ *   beam's running score is added; -inf + score stays -inf.  Ties keep their rule.  The minimum lengths are tested against the
+ *   device step counter, so a captured step replays correctly.
+ *   Limits when any setting is not neutral (MH_ESHAPE otherwise): V <= MH_PROCESS_MAX_VOCAB (two bitmaps of V bits in 8 KB of
+ *   LDS), ld_out / cap <= MH_PROCESS_MAX_HISTORY (the history in 4 KB of LDS), and for beams V >= 2K + cap + 1: at most one ban
+ *   per history position plus eos, so every row keeps 2K finite candidates.  Settings outside their domain: MH_EINVAL.
+ *   The work added is proportional to the history (cur_len * n / 256 comparisons per thread); no pass over V is added.
  * ------------------------------------------------------------------------------------------ */
+#define MH_PROCESS_MAX_VOCAB 32768
+#define MH_PROCESS_MAX_HISTORY 1024
+typedef struct MhLogitsProcess {
+    float repetition_penalty;
+    int no_repeat_ngram_size, min_length, min_new_tokens;
+} MhLogitsProcess;
 typedef struct MhBeamState {
     int64_t* next_ids;   /* [B*K] the running beams' new tokens: the next step's input ids */
     int32_t* parents;    /* [B*K] the beam (0..K-1 of its image) each running beam continues */
@@ -898,6 +924,12 @@ int mh_decode_embed(const int64_t* ids /*[B]*/, const int32_t* t_dev, const floa
 int mh_greedy_step(const float* logits, int ldl, int V, int B, int64_t* out_ids, int ld_out, int64_t* next_ids,
                    int32_t* finished /*[B]*/, int32_t* state /*[4]*/, int prompt_len, int64_t eos_id, int64_t pad_id,
                    mh_stream_t stream);
+int mh_greedy_step_processed(const float* logits, int ldl, int V, int B, int64_t* out_ids, int ld_out, int64_t* next_ids,
+                             int32_t* finished /*[B]*/, int32_t* state /*[4]*/, int prompt_len, int64_t eos_id, int64_t pad_id,
+                             const MhLogitsProcess* process, mh_stream_t stream);
+int mh_beam_step_processed(const float* logits, int ldl, int V, int B, int K, const MhBeamState* st, int cap, int prompt_len,
+                           float length_penalty, int early_stopping, int64_t eos_id, const MhLogitsProcess* process,
+                           mh_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * SVM (svm.hip): sklearn.svm.SVC(C, kernel='linear') of the organizers' baselines (baselines/subtask_2c.py:61,85,

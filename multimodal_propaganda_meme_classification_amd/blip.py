@@ -23,6 +23,10 @@ Launch plan (activations are 16-bit row matrices, ``compute_dtype`` selects the 
   heuristic, all on the device), cross-attention reads one k / v copy per image (``kv_group = K``), and the self-attention cache
   stays in place: an int32 ancestry table [B * K][cap], permuted by ``mh_beam_step``, tells ``mh_attn_decode`` which physical row
   holds each earlier position of a beam.
+* Logits processors (``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``min_new_tokens``) run inside the two
+  selection kernels (``mh_greedy_step_processed`` / ``mh_beam_step_processed``): the row's history is staged into LDS and turned
+  into two bitmaps over the vocabulary, which the kernels' existing passes over the logits look up.  The settings are baked into
+  the captured step (the minimum lengths are compared with the device step counter), so other settings re-capture it.
 """
 from __future__ import annotations
 
@@ -298,17 +302,22 @@ class BlipCaptioner(nn.Module):
         ops.gemm_grouped([ops.Gemm(x1, wdec, st["logits"], B, Vp, D, D, D, Vp, bias=bdec)], False, False)
         if beam is None:
             ops.greedy_step(st["logits"], tc["vocab_size"], st["out_ids"], st["next_ids"], st["finished"], st["sv"], st["P"],
-                            tc["sep_token_id"], tc["pad_token_id"])
+                            tc["sep_token_id"], tc["pad_token_id"], process=st["process"])
         else:
-            ops.beam_step(st["logits"], tc["vocab_size"], beam, st["P"], st["length_penalty"], st["early_stopping"], tc["sep_token_id"])
+            ops.beam_step(st["logits"], tc["vocab_size"], beam, st["P"], st["length_penalty"], st["early_stopping"], tc["sep_token_id"],
+                          process=st["process"])
 
-    def _prepare(self, pixel_values, prompt, cap, num_beams=1, length_penalty=1.0, early_stopping=False):
-        """vision tower, cross k / v of every layer, and the step's state for this prompt (int64 [B, P] on the device)."""
+    def _prepare(self, pixel_values, prompt, cap, num_beams=1, length_penalty=1.0, early_stopping=False, process=None):
+        """vision tower, cross k / v of every layer, and the step's state for this prompt (int64 [B, P] on the device).
+        process: an ``ops.logits_process`` (None: no logits processors, the plain selection kernels)."""
         img = self.vision_forward(pixel_values)
         B, P = prompt.shape
         st = self._state(B, cap, pixel_values.device, num_beams)
         st["P"], st["length_penalty"], st["early_stopping"] = P, float(length_penalty), early_stopping
-        st["key"] = (P, num_beams, float(length_penalty), early_stopping)      # what a captured step has baked in
+        st["process"] = None if ops.process_is_neutral(process) else process
+        pkey = None if st["process"] is None else (process.repetition_penalty, process.no_repeat_ngram_size, process.min_length,
+                                                   process.min_new_tokens)
+        st["key"] = (P, num_beams, float(length_penalty), early_stopping, pkey)      # what a captured step has baked in
         D = self.text_cfg["hidden_size"]
         gs = [ops.Gemm(img, lw["wckv"], ckv, img.shape[0], 2 * D, img.shape[1], img.shape[1], img.shape[1], 2 * D, bias=lw["bckv"])
               for lw, ckv in zip(self._pack["txt"], st["ckv"])]
@@ -334,8 +343,9 @@ class BlipCaptioner(nn.Module):
 
     def _run(self, st, steps: int, graph: bool, poll_every: int, record=None, trace=None):
         """``steps`` decode steps (stops early once every row has finished, checked every ``poll_every`` steps).  ``record``: a
-        list that receives each step's logits; ``trace`` (beam search): a list that receives, per step, a dict of copies of the
-        logits the step used and of the beam state after it (``ops.beam_state``'s tensors)."""
+        list that receives each step's logits; ``trace``: a list that receives, per step, a dict of copies of the logits the step
+        used and of the beam state after it (``ops.beam_state``'s tensors), or for greedy decoding of ``next_ids`` (the chosen
+        tokens), ``finished`` and ``state``."""
         done = st["sv"] if st["beam"] is None else st["beam"]["state"]
         for i in range(steps):
             if i == 0 or not graph:
@@ -350,7 +360,10 @@ class BlipCaptioner(nn.Module):
             if record is not None:
                 record.append(st["logits"][:, :self.text_cfg["vocab_size"]].clone())
             if trace is not None:
-                snap = {n: v.clone() for n, v in st["beam"].items() if isinstance(v, torch.Tensor) and not n.startswith("cand_")}
+                if st["beam"] is None:      # greedy: the tokens the step chose, its finished flags and state words after it
+                    snap = dict(next_ids=st["next_ids"].clone(), finished=st["finished"].clone(), state=st["sv"].clone())
+                else:
+                    snap = {n: v.clone() for n, v in st["beam"].items() if isinstance(v, torch.Tensor) and not n.startswith("cand_")}
                 snap["logits"] = st["logits"][:, :self.text_cfg["vocab_size"]].clone()
                 trace.append(snap)
             if i + 1 < steps and (i + 1) % poll_every == 0 and int(done[3]) != 0:
@@ -390,27 +403,41 @@ class BlipCaptioner(nn.Module):
         a tie open, the lower flat index ``beam * vocab_size + token`` wins (the lower position in the later selections).  The loop
         ends once no image's finished beams can change any more (transformers may run further steps; the result is the same).
 
+        Logits processors, transformers' own in ``_get_logits_processor``'s order, inside the device step (the captured graph
+        included): ``repetition_penalty`` (finite, > 0; every distinct token of the row so far, prompt included, is penalised once),
+        ``no_repeat_ngram_size``, ``min_length`` (counts the prompt) and ``min_new_tokens`` (integers >= 0).  Greedy decoding
+        applies them to the raw f32 logits, beam search to the row's log-softmax before the beam's score is added, as transformers
+        does.  With the neutral values (1, 0, 0, 0) the step is exactly the one without them.  Beam search with a processor needs
+        ``vocab_size >= 2 * num_beams + prompt + max_new_tokens + 1``, so that the bans leave every beam its candidates.
+
+        ``num_return_sequences = n`` (beam search only, ``1 <= n <= num_beams``): the n best finished beams of every image, best
+        first, as ``[B * n, L]`` rows ordered [image][rank], cut to the prompt plus the longest generated length among the returned
+        rows.  A slot that holds no finished beam (the search closed before n beams finished) yields the prompt followed by the
+        padding, with length 0.
+
         ``graph=False`` runs the same launches without the hipGraph.  Refused with ``ValueError``: ``num_beams`` outside 1..8,
-        ``num_return_sequences != 1``, sampling, ``repetition_penalty != 1``, ``no_repeat_ngram_size``, ``min_length`` /
-        ``min_new_tokens``, ``interpolate_pos_encoding``, prompt attention masks with zeros, and ``num_beams > 1`` for a model or
-        batch that is not on the HIP device (greedy calls there raise ``MemehipError``: there is no CPU path at all)."""
+        ``num_return_sequences`` outside 1..num_beams, sampling, ``interpolate_pos_encoding``, prompt attention masks with zeros,
+        and ``num_beams > 1`` or any logits processor for a model or batch that is not on the HIP device (plain greedy calls there
+        raise ``MemehipError``: there is no CPU path at all)."""
         if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= 8:
             raise ValueError("num_beams must be an integer from 1 (greedy) to 8")
-        if num_return_sequences != 1:
-            raise ValueError("num_return_sequences != 1 is not implemented (the best beam of every image is returned)")
+        nrs = num_return_sequences
+        if isinstance(nrs, bool) or not isinstance(nrs, int) or nrs < 1:
+            raise ValueError("num_return_sequences must be an integer >= 1")
+        if nrs > num_beams:
+            raise ValueError("num_return_sequences must be <= num_beams (more than one sequence needs beam search: there is no sampling)")
         if not isinstance(early_stopping, bool) and early_stopping != "never":
             raise ValueError("early_stopping must be False, True or 'never'")
         if do_sample:
             raise ValueError("sampling is not implemented (greedy decoding and beam search only)")
-        if num_beams > 1 and not (isinstance(pixel_values, torch.Tensor) and pixel_values.is_cuda and next(self.parameters()).is_cuda):
+        process = ops.logits_process(repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens)      # ValueError if invalid
+        on_device = isinstance(pixel_values, torch.Tensor) and pixel_values.is_cuda and next(self.parameters()).is_cuda
+        if num_beams > 1 and not on_device:
             # (the argument is refused, as before beam search existed: the search lives in the device step and nowhere else)
             raise ValueError("beam search (num_beams > 1) exists only in the HIP decode step: move the model and batch with .to(device)")
-        if repetition_penalty != 1.0:
-            raise ValueError("repetition_penalty != 1 is not implemented")
-        if no_repeat_ngram_size:
-            raise ValueError("no_repeat_ngram_size is not implemented")
-        if min_length or min_new_tokens:
-            raise ValueError("min_length / min_new_tokens > 0 are not implemented")
+        if not ops.process_is_neutral(process) and not on_device:
+            raise ValueError("repetition_penalty, no_repeat_ngram_size, min_length and min_new_tokens exist only in the HIP decode step: "
+                             "move the model and batch with .to(device)")
         if interpolate_pos_encoding:
             raise ValueError("interpolate_pos_encoding is not implemented: pixel_values must have the config's image_size")
         if int(max_new_tokens) < 1 or int(poll_every) < 1:
@@ -430,13 +457,15 @@ class BlipCaptioner(nn.Module):
         if num_beams > 1:
             if self.text_cfg["vocab_size"] < 2 * num_beams:
                 raise ValueError("beam search needs vocab_size >= 2 * num_beams")
-            st = self._prepare(pixel_values, prompt, cap, num_beams, length_penalty, early_stopping)
+            if not ops.process_is_neutral(process) and self.text_cfg["vocab_size"] < 2 * num_beams + cap + 1:
+                raise ValueError("beam search with logits processors needs vocab_size >= 2 * num_beams + prompt + max_new_tokens + 1")
+            st = self._prepare(pixel_values, prompt, cap, num_beams, length_penalty, early_stopping, process)
             self._run(st, P - 1 + int(max_new_tokens), graph, int(poll_every), trace=_trace)
             bs = st["beam"]
-            best_len = bs["fin_len"].view(-1, num_beams)[:, 0]
-            return bs["fin_seq"].view(-1, num_beams, cap)[:, 0, :P + int(best_len.max())].to(I64)
-        st = self._prepare(pixel_values, prompt, cap)
-        self._run(st, P - 1 + int(max_new_tokens), graph, int(poll_every))
+            lens = bs["fin_len"].view(-1, num_beams)[:, :nrs]
+            return bs["fin_seq"].view(-1, num_beams, cap)[:, :nrs, :P + int(lens.max())].reshape(-1, P + int(lens.max())).to(I64)
+        st = self._prepare(pixel_values, prompt, cap, process=process)
+        self._run(st, P - 1 + int(max_new_tokens), graph, int(poll_every), trace=_trace)
         sv = st["sv"].cpu()
         length = int(sv[3]) if int(sv[3]) else min(cap, int(sv[0]) + 1)
         return st["out_ids"][:, :length].clone()

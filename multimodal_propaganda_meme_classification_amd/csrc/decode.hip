@@ -6,6 +6,8 @@
 //   mh_greedy_step   row argmax of the LM head's f32 logits + the greedy bookkeeping of transformers' generate
 //   mh_beam_step     beam search over the same logits (2 <= K <= 8 beams per image): log-softmax + the row's top 2K, then per image
 //                    the ordered top 2K of K*V candidates and the running / finished bookkeeping of transformers' _beam_search
+//   mh_greedy_step_processed / mh_beam_step_processed   the same two with transformers' repetition penalty, n-gram ban and minimum
+//                    lengths applied inside the selection kernels (instantiations of their own: the plain ones are unchanged)
 //
 // Beams: the rows are [image][beam].  Cross-attention k / v stay one copy per image (kv_group rows share it).  The self-attention
 // cache does not move when beams are re-ordered: an ancestry table src[row][position] names the physical cache row that holds the
@@ -227,10 +229,61 @@ MH_DEV bool arg_better(float v, int i, float bv, int bi) {
     return v > bv || (v == bv && i < bi);
 }
 
+// ---- logits processors (transformers' RepetitionPenalty, NoRepeatNGram, MinLength and MinNewTokensLength, in that order) ----------
+// Both selection kernels stream a row of V logits with one workgroup.  The processed forms first stage the row's history (the L
+// tokens so far, prompt included) into LDS and build two bitmaps of V bits there: `seen` (every history token: penalised once, however
+// often it occurs) and `banned` (the token after every earlier occurrence of the last n - 1 tokens, and eos while the sequence is
+// under either minimum length).  That costs O(L * n / 256) per thread and no pass over the vocabulary; the streaming loops then read
+// one word of each bitmap per 16-byte chunk (a chunk starts at a multiple of 4, so its four bits share a word).
+constexpr int PROC_MAX_V = MH_PROCESS_MAX_VOCAB;         // 2 bitmaps * 4 KB of static LDS
+constexpr int PROC_MAX_HIST = MH_PROCESS_MAX_HISTORY;    // + 4 KB for the history
+
+struct ProcArgs {
+    float penalty;
+    int ngram, min_length, min_new_tokens;
+    int eos;      // -1: outside [0, V)
+};
+
+struct ProcLds {
+    uint32_t seen[PROC_MAX_V / 32], banned[PROC_MAX_V / 32];
+    int hist[PROC_MAX_HIST];
+};
+
+// hist: the row's tokens 0..L-1 (int64 for the greedy output rows, int32 for the beams' sequences), L <= PROC_MAX_HIST, V <= PROC_MAX_V.
+// Called by the whole workgroup; the bitmaps are complete when it returns.  An id outside [0, V) has no logit and sets no bit.
+template <typename Tok>
+MH_DEV void proc_build(ProcLds& p, const Tok* hist, int L, int V, int prompt_len, const ProcArgs& a) {
+    const int tid = threadIdx.x, n = a.ngram, eos = a.eos;
+    for (int w = tid; w < (V + 31) / 32; w += 256) p.seen[w] = p.banned[w] = 0u;
+    for (int j = tid; j < L; j += 256) p.hist[j] = (int)hist[j];
+    __syncthreads();
+    for (int j = tid; j < L; j += 256) {
+        const int id = p.hist[j];
+        if ((unsigned)id >= (unsigned)V) continue;
+        atomicOr(&p.seen[id >> 5], 1u << (id & 31));
+        if (n > 0 && j >= n - 1) {           // the window that ends at j: do its first n - 1 tokens equal the last n - 1 of the row?
+            bool match = true;
+            for (int k = 1; k < n && match; ++k) match = p.hist[j - k] == p.hist[L - k];
+            if (match) atomicOr(&p.banned[id >> 5], 1u << (id & 31));
+        }
+    }
+    // (L is read from the device step counter by the caller: the launch is replayed from a graph)
+    if (tid == 0 && (unsigned)eos < (unsigned)V && (L < a.min_length || L - prompt_len < a.min_new_tokens))
+        atomicOr(&p.banned[eos >> 5], 1u << (eos & 31));
+    __syncthreads();
+}
+
+// one value: penalise (s < 0 ? s * p : s / p, each one correctly rounded f32 operation), then ban
+MH_DEV float proc_apply(float v, uint32_t seen, uint32_t banned, int i, float penalty) {
+    if ((seen >> i) & 1u) v = v < 0.f ? __fmul_rn(v, penalty) : __fdiv_rn(v, penalty);
+    return ((banned >> i) & 1u) ? -INFINITY : v;
+}
+
 // state words: [0] t (the position this step consumed), [1] arrival counter (0 between launches), [2] rows finished,
 // [3] output length once every row has finished (0 before)
-__global__ void __launch_bounds__(256) greedy_step_kernel(const float* logits, int ldl, int V, int64_t* out_ids, int ld_out, int64_t* next_ids,
-                                                          int32_t* finished, int32_t* state, int prompt_len, int64_t eos, int64_t pad) {
+template <bool PROC>
+MH_DEV void greedy_step_body(const float* logits, int ldl, int V, int64_t* out_ids, int ld_out, int64_t* next_ids, int32_t* finished,
+                             int32_t* state, int prompt_len, int64_t eos, int64_t pad, const ProcArgs& pa, ProcLds* pl) {
     __shared__ float shv[4];
     __shared__ int shi[4];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -242,8 +295,14 @@ __global__ void __launch_bounds__(256) greedy_step_kernel(const float* logits, i
     int bi = 0x7fffffff;
     if (gen) {
         const float* row = logits + (int64_t)b * ldl;
+        if constexpr (PROC) proc_build(*pl, out_ids + (int64_t)b * ld_out, min(col, ld_out), V, prompt_len, pa);
         for (int c = tid * 4; c < V; c += 256 * 4) {
-            const f32x4 x = *reinterpret_cast<const f32x4*>(row + c);
+            f32x4 x = *reinterpret_cast<const f32x4*>(row + c);
+            if constexpr (PROC) {
+                const uint32_t sw = pl->seen[c >> 5] >> (c & 31), bw = pl->banned[c >> 5] >> (c & 31);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) x[i] = proc_apply(x[i], sw, bw, i, pa.penalty);
+            }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 if (c + i < V && arg_better(x[i], c + i, bv, bi)) {
@@ -298,6 +357,18 @@ __global__ void __launch_bounds__(256) greedy_step_kernel(const float* logits, i
     }
 }
 
+__global__ void __launch_bounds__(256) greedy_step_kernel(const float* logits, int ldl, int V, int64_t* out_ids, int ld_out, int64_t* next_ids,
+                                                          int32_t* finished, int32_t* state, int prompt_len, int64_t eos, int64_t pad) {
+    greedy_step_body<false>(logits, ldl, V, out_ids, ld_out, next_ids, finished, state, prompt_len, eos, pad, ProcArgs{}, nullptr);
+}
+
+__global__ void __launch_bounds__(256) greedy_step_processed_kernel(const float* logits, int ldl, int V, int64_t* out_ids, int ld_out,
+                                                                    int64_t* next_ids, int32_t* finished, int32_t* state, int prompt_len,
+                                                                    int64_t eos, int64_t pad, ProcArgs pa) {
+    __shared__ ProcLds pl;
+    greedy_step_body<true>(logits, ldl, V, out_ids, ld_out, next_ids, finished, state, prompt_len, eos, pad, pa, &pl);
+}
+
 // ---- beam search ------------------------------------------------------------------------------------------------------------------
 // One order everywhere: the larger f32 value first, then the lower index (the flat candidate index beam * V + token in the image's
 // top 2K, the position in the later selections).  torch.topk leaves ties open; this is the rule they get here.
@@ -316,15 +387,18 @@ MH_DEV void lse_merge(float& m, float& s, float om, float os) {
 // ((x - max) - log(sum)) + score, the oracle's f32 operations in its order.  The image's top 2K is a subset of the union of these.
 // The second pass re-reads the row (122 KB at V = 30524, from L2) because the order is taken on the rounded accumulated value: two
 // logits that round to one value tie, and the tie goes to the lower index.
-template <int N>
-__global__ void __launch_bounds__(256) beam_row_kernel(const float* logits, int ldl, int V, const float* run_scores, const int32_t* state,
-                                                       int prompt_len, int cap, float* cand_val, int32_t* cand_idx) {
+// PROC: the processors act on the log-probability (x - max) - log(sum), before the score is added; the log-sum-exp is taken over
+// the unprocessed row.  The history is the row's own run_seq: mh_beam_step permuted it by parent at the end of the previous step.
+template <int N, bool PROC>
+MH_DEV void beam_row_body(const float* logits, int ldl, int V, const float* run_scores, const int32_t* state, int prompt_len, int cap,
+                          float* cand_val, int32_t* cand_idx, const int32_t* run_seq, const ProcArgs& pa, ProcLds* pl) {
     __shared__ float shm[4], shs[4];
     __shared__ int shi[4];
     const int r = blockIdx.x, tid = threadIdx.x;
     const int col = state[0] + 1;
     if (col < prompt_len || col >= cap) return;           // inside the prompt, or past the end: no candidates are needed
     const float* row = logits + (int64_t)r * ldl;
+    if constexpr (PROC) proc_build(*pl, run_seq + (int64_t)r * cap, col, V, prompt_len, pa);
     float m = -INFINITY, s = 0.f;
     for (int c = tid * 4; c < V; c += 256 * 4) {
         const f32x4 x = *reinterpret_cast<const f32x4*>(row + c);
@@ -362,9 +436,17 @@ __global__ void __launch_bounds__(256) beam_row_kernel(const float* logits, int 
     }
     for (int c = tid * 4; c < V; c += 256 * 4) {
         const f32x4 x = *reinterpret_cast<const f32x4*>(row + c);
+        f32x4 lp;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lp[i] = (x[i] - m) - lse;
+        if constexpr (PROC) {
+            const uint32_t sw = pl->seen[c >> 5] >> (c & 31), bw = pl->banned[c >> 5] >> (c & 31);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) lp[i] = proc_apply(lp[i], sw, bw, i, pa.penalty);
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float f = ((x[i] - m) - lse) + score;
+            const float f = lp[i] + score;
             if (c + i < V && beam_better(f, c + i, lv[N - 1], li[N - 1])) {
                 lv[N - 1] = f;
                 li[N - 1] = c + i;
@@ -418,6 +500,20 @@ __global__ void __launch_bounds__(256) beam_row_kernel(const float* logits, int 
         }
         pv = bv, pi = bi;
     }
+}
+
+template <int N>
+__global__ void __launch_bounds__(256) beam_row_kernel(const float* logits, int ldl, int V, const float* run_scores, const int32_t* state,
+                                                       int prompt_len, int cap, float* cand_val, int32_t* cand_idx) {
+    beam_row_body<N, false>(logits, ldl, V, run_scores, state, prompt_len, cap, cand_val, cand_idx, nullptr, ProcArgs{}, nullptr);
+}
+
+template <int N>
+__global__ void __launch_bounds__(256) beam_row_processed_kernel(const float* logits, int ldl, int V, const float* run_scores,
+                                                                 const int32_t* state, int prompt_len, int cap, float* cand_val,
+                                                                 int32_t* cand_idx, const int32_t* run_seq, ProcArgs pa) {
+    __shared__ ProcLds pl;
+    beam_row_body<N, true>(logits, ldl, V, run_scores, state, prompt_len, cap, cand_val, cand_idx, run_seq, pa, &pl);
 }
 
 MH_DEV int pick8(const int (&a)[BEAM_MAX], int p) {
@@ -629,29 +725,78 @@ extern "C" int mh_decode_embed(const int64_t* ids, const int32_t* t_dev, const f
     return mh_launch_status();
 }
 
-extern "C" int mh_greedy_step(const float* logits, int ldl, int V, int B, int64_t* out_ids, int ld_out, int64_t* next_ids,
-                              int32_t* finished, int32_t* state, int prompt_len, int64_t eos_id, int64_t pad_id, mh_stream_t stream) {
+namespace {
+
+const MhLogitsProcess PROC_NEUTRAL = {1.0f, 0, 0, 0};
+
+// MH_EINVAL for settings outside their domain; *on: does any processor act?
+int proc_settings(const MhLogitsProcess* p, int V, int64_t eos_id, ProcArgs* pa, bool* on) {
+    if (!p) return MH_EINVAL;
+    if (!(p->repetition_penalty > 0.f) || p->repetition_penalty > 3.0e38f || p->no_repeat_ngram_size < 0 || p->min_length < 0 ||
+        p->min_new_tokens < 0)
+        return MH_EINVAL;
+    pa->penalty = p->repetition_penalty;
+    pa->ngram = p->no_repeat_ngram_size;
+    pa->min_length = p->min_length;
+    pa->min_new_tokens = p->min_new_tokens;
+    pa->eos = (eos_id >= 0 && eos_id < V) ? (int)eos_id : -1;
+    *on = p->repetition_penalty != 1.0f || p->no_repeat_ngram_size > 0 || p->min_length > 0 || p->min_new_tokens > 0;
+    return MH_OK;
+}
+
+}  // namespace
+
+extern "C" int mh_greedy_step_processed(const float* logits, int ldl, int V, int B, int64_t* out_ids, int ld_out, int64_t* next_ids,
+                                        int32_t* finished, int32_t* state, int prompt_len, int64_t eos_id, int64_t pad_id,
+                                        const MhLogitsProcess* process, mh_stream_t stream) {
     if (!logits || !out_ids || !next_ids || !finished || !state) return MH_EINVAL;
+    ProcArgs pa;
+    bool on;
+    if (const int st = proc_settings(process, V, eos_id, &pa, &on)) return st;
     if (B < 1 || V < 1 || ldl < V || ldl % 4 || prompt_len < 1 || ld_out <= prompt_len) return MH_ESHAPE;
-    hipLaunchKernelGGL(greedy_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ldl, V, out_ids, ld_out, next_ids, finished,
-                       state, prompt_len, eos_id, pad_id);
+    if (!on) {
+        hipLaunchKernelGGL(greedy_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ldl, V, out_ids, ld_out, next_ids,
+                           finished, state, prompt_len, eos_id, pad_id);
+        return mh_launch_status();
+    }
+    if (V > PROC_MAX_V || ld_out > PROC_MAX_HIST) return MH_ESHAPE;      // the bitmaps / the history do not fit their LDS
+    hipLaunchKernelGGL(greedy_step_processed_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ldl, V, out_ids, ld_out, next_ids,
+                       finished, state, prompt_len, eos_id, pad_id, pa);
     return mh_launch_status();
 }
 
-extern "C" int mh_beam_step(const float* logits, int ldl, int V, int B, int K, const MhBeamState* st, int cap, int prompt_len,
-                            float length_penalty, int early_stopping, int64_t eos_id, mh_stream_t stream) {
+extern "C" int mh_greedy_step(const float* logits, int ldl, int V, int B, int64_t* out_ids, int ld_out, int64_t* next_ids,
+                              int32_t* finished, int32_t* state, int prompt_len, int64_t eos_id, int64_t pad_id, mh_stream_t stream) {
+    return mh_greedy_step_processed(logits, ldl, V, B, out_ids, ld_out, next_ids, finished, state, prompt_len, eos_id, pad_id, &PROC_NEUTRAL,
+                                    stream);
+}
+
+extern "C" int mh_beam_step_processed(const float* logits, int ldl, int V, int B, int K, const MhBeamState* st, int cap, int prompt_len,
+                                      float length_penalty, int early_stopping, int64_t eos_id, const MhLogitsProcess* process,
+                                      mh_stream_t stream) {
     if (!logits || !st || !st->next_ids || !st->parents || !st->run_scores || !st->run_seq || !st->fin_seq || !st->fin_scores ||
         !st->fin_flags || !st->fin_len || !st->heur || !st->state || !st->cand_val || !st->cand_idx)
         return MH_EINVAL;
+    ProcArgs pa;
+    bool on;
+    if (const int ps = proc_settings(process, V, eos_id, &pa, &on)) return ps;
     if (B < 1 || K < 2 || K > BEAM_MAX || V < 2 * K || (int64_t)K * V > 0x7fffffff || ldl < V || ldl % 4 || prompt_len < 1 ||
         cap <= prompt_len || early_stopping < 0 || early_stopping > 2 || (int64_t)B * K * cap > 0x7fffffff)
         return MH_ESHAPE;
+    // processed: the bitmaps and the history fit their LDS, and the bans (at most one per history position, plus eos) leave every
+    // row 2K finite candidates
+    if (on && (V > PROC_MAX_V || cap > PROC_MAX_HIST || V < 2 * K + cap + 1)) return MH_ESHAPE;
     hipStream_t s = (hipStream_t)stream;
     const int R = B * K;
 #define MH_BEAM_ROW(KK)                                                                                                               \
     case KK:                                                                                                                          \
-        hipLaunchKernelGGL(beam_row_kernel<2 * KK>, dim3(R), dim3(256), 0, s, logits, ldl, V, (const float*)st->run_scores,           \
-                           (const int32_t*)st->state, prompt_len, cap, st->cand_val, st->cand_idx);                                   \
+        if (on)                                                                                                                       \
+            hipLaunchKernelGGL(beam_row_processed_kernel<2 * KK>, dim3(R), dim3(256), 0, s, logits, ldl, V,                           \
+                               (const float*)st->run_scores, (const int32_t*)st->state, prompt_len, cap, st->cand_val, st->cand_idx,  \
+                               (const int32_t*)st->run_seq, pa);                                                                      \
+        else                                                                                                                          \
+            hipLaunchKernelGGL(beam_row_kernel<2 * KK>, dim3(R), dim3(256), 0, s, logits, ldl, V, (const float*)st->run_scores,       \
+                               (const int32_t*)st->state, prompt_len, cap, st->cand_val, st->cand_idx);                               \
         break;
     switch (K) {
         MH_BEAM_ROW(2) MH_BEAM_ROW(3) MH_BEAM_ROW(4) MH_BEAM_ROW(5) MH_BEAM_ROW(6) MH_BEAM_ROW(7) MH_BEAM_ROW(8)
@@ -663,4 +808,9 @@ extern "C" int mh_beam_step(const float* logits, int ldl, int V, int B, int K, c
     a.length_penalty = length_penalty;
     hipLaunchKernelGGL(beam_image_kernel, dim3(B), dim3(256), 0, s, a);
     return mh_launch_status();
+}
+
+extern "C" int mh_beam_step(const float* logits, int ldl, int V, int B, int K, const MhBeamState* st, int cap, int prompt_len,
+                            float length_penalty, int early_stopping, int64_t eos_id, mh_stream_t stream) {
+    return mh_beam_step_processed(logits, ldl, V, B, K, st, cap, prompt_len, length_penalty, early_stopping, eos_id, &PROC_NEUTRAL, stream);
 }

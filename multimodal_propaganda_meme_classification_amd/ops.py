@@ -823,15 +823,51 @@ def decode_embed(ids, t_dev, word, pos, gamma, beta, eps, y):
     return y
 
 
-def greedy_step(logits, V, out_ids, next_ids, finished, state, prompt_len, eos_id, pad_id):
-    """mh_greedy_step over f32 logits [B, ldl] (ldl >= V): see include/memehip.h."""
+def logits_process(repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, min_new_tokens=0):
+    """The settings of greedy_step / beam_step's ``process`` (MhLogitsProcess in include/memehip.h), validated: the penalty a finite
+    number > 0, the other three integers >= 0.  The defaults are neutral."""
+    import math
+    p = repetition_penalty
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not math.isfinite(p) or not p > 0:
+        raise ValueError(f"repetition_penalty must be a finite number > 0, got {p!r}")
+    ints = dict(no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, min_new_tokens=min_new_tokens)
+    for name, v in ints.items():
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 31:
+            raise ValueError(f"{name} must be an integer >= 0, got {v!r}")
+    return _lib.MhLogitsProcess(float(p), *ints.values())
+
+
+def process_is_neutral(process) -> bool:
+    if process is not None and not isinstance(process, _lib.MhLogitsProcess):
+        raise TypeError("process is a logits_process(...) or None")
+    return process is None or (process.repetition_penalty == 1.0 and process.no_repeat_ngram_size == 0 and process.min_length == 0
+                               and process.min_new_tokens == 0)
+
+
+def _check_processed(status, what, limits):
+    """the processed entry points refuse a shape outside their limits with MH_ESHAPE: a ValueError that names the limits"""
+    if status == _lib.MH_ESHAPE:
+        raise ValueError(f"{what}: with logits processors {limits}")
+    check(status, what)
+
+
+def greedy_step(logits, V, out_ids, next_ids, finished, state, prompt_len, eos_id, pad_id, process=None):
+    """mh_greedy_step over f32 logits [B, ldl] (ldl >= V): see include/memehip.h.  process: a logits_process() (None or neutral
+    settings: the plain entry point), applied to the raw logits before the argmax."""
     _chk(logits, F32, "logits"), _chk(out_ids, I64, "out_ids"), _chk(next_ids, I64, "next_ids")
     _i32(finished, "finished"), _i32(state, "state")
     B, ldl = logits.shape
     if out_ids.dim() != 2 or out_ids.shape[0] != B or next_ids.numel() < B or finished.numel() < B or state.numel() < 4 or V > ldl:
         raise ValueError("greedy_step: shapes disagree")
-    check(_lib.load().mh_greedy_step(_p(logits), ldl, int(V), B, _p(out_ids), out_ids.shape[1], _p(next_ids), _p(finished), _p(state),
-                                     int(prompt_len), int(eos_id), int(pad_id), _stream()), "mh_greedy_step")
+    if process_is_neutral(process):
+        check(_lib.load().mh_greedy_step(_p(logits), ldl, int(V), B, _p(out_ids), out_ids.shape[1], _p(next_ids), _p(finished), _p(state),
+                                         int(prompt_len), int(eos_id), int(pad_id), _stream()), "mh_greedy_step")
+        return
+    _check_processed(_lib.load().mh_greedy_step_processed(_p(logits), ldl, int(V), B, _p(out_ids), out_ids.shape[1], _p(next_ids),
+                                                          _p(finished), _p(state), int(prompt_len), int(eos_id), int(pad_id),
+                                                          C.byref(process), _stream()), "mh_greedy_step_processed",
+                     f"V <= {_lib.MH_PROCESS_MAX_VOCAB} and at most {_lib.MH_PROCESS_MAX_HISTORY} output columns are supported "
+                     f"(V = {int(V)}, {out_ids.shape[1]} columns)")
 
 
 BEAM_NEG = -1.0e9
@@ -860,8 +896,9 @@ def beam_state(B, K, cap, prompt, pad_id, device, src=True):
     return st
 
 
-def beam_step(logits, V, st, prompt_len, length_penalty, early_stopping, eos_id):
-    """mh_beam_step over f32 logits [B * K, ldl] (ldl >= V) on a beam_state: see include/memehip.h."""
+def beam_step(logits, V, st, prompt_len, length_penalty, early_stopping, eos_id, process=None):
+    """mh_beam_step over f32 logits [B * K, ldl] (ldl >= V) on a beam_state: see include/memehip.h.  process: a logits_process()
+    (None or neutral settings: the plain entry point), applied to each row's log-softmax before its running score is added."""
     _chk(logits, F32, "logits")
     if not isinstance(early_stopping, bool) and early_stopping != "never":
         raise ValueError("beam_step: early_stopping is False, True or 'never'")
@@ -872,8 +909,15 @@ def beam_step(logits, V, st, prompt_len, length_penalty, early_stopping, eos_id)
         if st[n] is not None and getattr(st["_c"], n) != st[n].data_ptr():
             raise ValueError(f"beam_step: state tensor {n!r} was replaced after beam_state()")
     es = 1 if early_stopping is True else (2 if early_stopping == "never" else 0)
-    check(_lib.load().mh_beam_step(_p(logits), logits.shape[1], int(V), B, K, C.byref(st["_c"]), cap, int(prompt_len), float(length_penalty),
-                                   es, int(eos_id), _stream()), "mh_beam_step")
+    if process_is_neutral(process):
+        check(_lib.load().mh_beam_step(_p(logits), logits.shape[1], int(V), B, K, C.byref(st["_c"]), cap, int(prompt_len),
+                                       float(length_penalty), es, int(eos_id), _stream()), "mh_beam_step")
+        return
+    _check_processed(_lib.load().mh_beam_step_processed(_p(logits), logits.shape[1], int(V), B, K, C.byref(st["_c"]), cap, int(prompt_len),
+                                                        float(length_penalty), es, int(eos_id), C.byref(process), _stream()),
+                     "mh_beam_step_processed",
+                     f"2K + cap + 1 <= V <= {_lib.MH_PROCESS_MAX_VOCAB} and cap <= {_lib.MH_PROCESS_MAX_HISTORY} are needed "
+                     f"(V = {int(V)}, K = {K}, cap = {cap}: every row must keep 2K candidates that are not banned)")
 
 
 # ---------------------------------------------------------------------------------------------

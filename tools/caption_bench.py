@@ -7,6 +7,9 @@ a 5-token prompt shaped like the processor's "[CLS] a meme of [SEP]", --batch im
 --max-new-tokens (128, the reference's).  Random weights rarely emit eos, so all steps usually run: the steps actually run are
 reported next to every rate.  Prints one JSON line; --out also writes it to a file.
 
+--repetition-penalty / --no-repeat-ngram-size / --min-length / --min-new-tokens: a further run, ours_graph_processed, with these
+generate() settings joins the alternation (the other runs stay without them), and its time over the plain graph run's is reported.
+
   python tools/caption_bench.py --out profiles/r05_caption_bench.json
   rocprofv3 --kernel-trace --stats -d DIR -o caption -- python tools/caption_bench.py --runs 1 --no-hf      (kernel table)
 """
@@ -62,8 +65,15 @@ def main():
     ap.add_argument("--dtype", choices=("fp16", "bf16"), default="fp16")
     ap.add_argument("--no-hf", action="store_true", help="skip transformers' generate (e.g. under a profiler)")
     ap.add_argument("--num-beams", type=int, default=1, help="beam search with this many beams on both sides (1: greedy)")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--no-repeat-ngram-size", type=int, default=0)
+    ap.add_argument("--min-length", type=int, default=0)
+    ap.add_argument("--min-new-tokens", type=int, default=0)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    proc = dict(repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size, min_length=args.min_length,
+                min_new_tokens=args.min_new_tokens)
+    processed = proc != dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, min_new_tokens=0)
 
     import __graft_entry__ as g
     g.build()
@@ -83,7 +93,10 @@ def main():
     pix = torch.randn(B, 3, 384, 384, generator=torch.Generator().manual_seed(args.seed + 1)).to(dev)
     prompt = torch.tensor([[101, 1037, 2033, 1997, 102]] * B)
 
-    runs = {"ours_graph": [], "ours_eager": [], "hf_fp16": []}
+    # with logits-processor settings the graph run WITH them joins the alternation; the other runs stay without (the baseline)
+    runs = {"ours_graph": [], "ours_graph_processed": [], "ours_eager": [], "hf_fp16": []}
+    if not processed:
+        del runs["ours_graph_processed"]
     steps = {}
     for r in range(args.runs + 1):
         for name in runs:
@@ -91,6 +104,8 @@ def main():
                 continue
             if name == "hf_fp16":
                 dt, out = timed(lambda: hf.generate(pixel_values=pix.half(), input_ids=prompt.clone().to(dev), max_new_tokens=N, num_beams=K))
+            elif name == "ours_graph_processed":
+                dt, out = timed(lambda: ours.generate(pix, prompt.clone(), max_new_tokens=N, num_beams=K, **proc))
             else:
                 dt, out = timed(lambda: ours.generate(pix, prompt.clone(), max_new_tokens=N, graph=(name == "ours_graph"), num_beams=K))
             steps[name] = int(out.shape[1]) - (prompt.shape[1] - 1)          # new tokens in the output
@@ -106,15 +121,20 @@ def main():
     def rewind():          # beam search: time steps inside the caption (past max_length the beam step has nothing to select)
         if st["beam"] is not None:
             t_dev[0] = prompt.shape[1] - 1
-    rewind()
-    torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n_rep):
-        st["graph"].replay()
-    e1.record()
-    torch.cuda.synchronize()
-    step_graph_ms = e0.elapsed_time(e1) / n_rep
+
+    def graph_step_ms(**kw):          # the captured step of a generate() with these settings (a call re-captures it when they differ)
+        ours.generate(pix, prompt.clone(), max_new_tokens=N, num_beams=K, **kw)
+        rewind()
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n_rep):
+            st["graph"].replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n_rep
+    step_graph_processed_ms = graph_step_ms(**proc) if processed else None
+    step_graph_ms = graph_step_ms()
     rewind()
     e0.record()
     for _ in range(10):
@@ -149,6 +169,10 @@ def main():
     res["vision_tower_ms"] = round(1000 * sorted(vis)[1], 3)
     res["decode_step_ms_graph"] = round(step_graph_ms, 4)
     res["decode_step_ms_eager"] = round(step_eager_ms, 4)
+    if processed:
+        res["logits_processors"] = proc
+        res["decode_step_ms_graph_processed"] = round(step_graph_processed_ms, 4)
+        res["processed_over_plain_time"] = round(stat(runs["ours_graph_processed"])["median_s"] / stat(runs["ours_graph"])["median_s"], 4)
     res["launches_per_token"] = launches
     res["decode_steps_per_batch"] = prompt.shape[1] - 2 + steps["ours_graph"]
     line = json.dumps(res)
