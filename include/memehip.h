@@ -952,6 +952,39 @@ int mh_beam_step_processed(const float* logits, int ldl, int V, int B, int K, co
                            float length_penalty, int early_stopping, int64_t eos_id, const MhLogitsProcess* process,
                            mh_stream_t stream);
 
+/* Sampling (generate(do_sample=True)).  mh_sample_step is mh_greedy_step with a draw in place of the argmax: one launch per step,
+ * one workgroup per row over f32 logits [B][ldl] (columns >= V are never read as candidates), the same out_ids / next_ids /
+ * finished / state words, the same prompt column (c < prompt_len: the prompt's next token), finished row (pad_id), eos handling and
+ * arrival counter.  Per generating row, in transformers' order (_get_logits_processor: processors, then the warpers):
+ *   1. process (NULL or neutral: none): the four logits processors above, on the raw logits, as mh_greedy_step_processed.
+ *   2. temperature: x = x / temperature, one correctly rounded f32 division (skipped when it is 1).
+ *   3. top_k > 0 (TopKLogitsWarper): keep every i with x_i >= the k-th largest value; ties at the threshold are all kept
+ *      (transformers removes `scores < kth`).  top_k = 0 or >= V: no filter.
+ *   4. top_p < 1 (TopPLogitsWarper, min_tokens_to_keep 1), over the softmax of the top-k survivors with total mass Z: keep i iff the
+ *      mass of the survivors with a strictly larger value is < top_p * Z.  Without ties this is transformers' ascending cumulative
+ *      sum with `<= 1 - top_p` removed.  Where equal f32 values straddle the boundary, torch.sort leaves the choice open: this rule
+ *      keeps them all.  The masses of this step are exact integer sums of exp(x - max) * 2^40, truncated: within 2^-25 of Z.
+ *   5. draw: u = (h >> 8) * 2^-24 with h = hash(hash(hash(hash(rng[0] ^ 0x9E3779B9) + rng[1]) + row) + column), 32-bit arithmetic,
+ *      hash the counter hash of the dropout sites; rng: device uint32[4] {seed_lo, seed_hi, -, -}, read by the kernel, so a
+ *      captured launch serves every seed; column = t + 1.  The token is the first kept index, in ascending index order, whose
+ *      inclusive prefix mass exceeds u * Z_kept; if rounding leaves none, the last kept index whose value is not -inf -- never an
+ *      unkept one.  If the row's maximum is not finite (a NaN, +inf, or an all -inf row: Z_kept would not be a positive finite
+ *      number), the token is mh_greedy_step's.  u_out (NULL or f32 [B]) receives every row's u.
+ *   Deterministic: no floating-point atomics; every f32 mass is a fixed-order sum in which no term passes through more than 46
+ *   additions (contract: 256), so it lies within 256 * 2^-24 = 2^-16 of the exact mass relative to Z; the same logits, settings and
+ *   seed give the same token on every run, launched directly or replayed from a graph.
+ *   Limits (MH_ESHAPE otherwise): V <= MH_PROCESS_MAX_VOCAB, with or without processors; temperature finite and > 0; top_k >= 0;
+ *   0 < top_p <= 1; with processors their own limits.  sampling or rng NULL, or processor settings outside their domain: MH_EINVAL. */
+typedef struct MhSampling {
+    float temperature;
+    int top_k;
+    float top_p;
+} MhSampling;
+int mh_sample_step(const float* logits, int ldl, int V, int B, int64_t* out_ids, int ld_out, int64_t* next_ids,
+                   int32_t* finished /*[B]*/, int32_t* state /*[4]*/, int prompt_len, int64_t eos_id, int64_t pad_id,
+                   const MhSampling* sampling, const uint32_t* rng /*device u32[4]*/, float* u_out /*[B] or NULL*/,
+                   const MhLogitsProcess* process /*NULL or neutral: none*/, mh_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * SVM (svm.hip): sklearn.svm.SVC(C, kernel='linear') of the organizers' baselines (baselines/subtask_2c.py:61,85,
  * subtask_2b.py), i.e. libsvm's SMO solver for the C-SVC dual

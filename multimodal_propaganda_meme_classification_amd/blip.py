@@ -1,4 +1,4 @@
-"""BLIP image captioning (``BlipForConditionalGeneration.generate``, greedy or beam search) on the HIP kernels: the caption tower of Kevin's model.
+"""BLIP image captioning (``BlipForConditionalGeneration.generate``: greedy, beam search or sampling) on the HIP kernels: the caption tower of Kevin's model.
 
 The reference captions every image of every split inside ``MultimodalDataset.__init__`` (``Multimodal_example_task2C.py:195-256``):
 ``Salesforce/blip-image-captioning-large`` in fp16, the prompt ``"a meme of"``, batches of 64, ``generate(..., max_new_tokens=128)``.
@@ -27,6 +27,11 @@ Launch plan (activations are 16-bit row matrices, ``compute_dtype`` selects the 
   selection kernels (``mh_greedy_step_processed`` / ``mh_beam_step_processed``): the row's history is staged into LDS and turned
   into two bitmaps over the vocabulary, which the kernels' existing passes over the logits look up.  The settings are baked into
   the captured step (the minimum lengths are compared with the device step counter), so other settings re-capture it.
+* Sampling (``do_sample=True``) replaces ``mh_greedy_step`` by ``mh_sample_step``: processors, temperature, top-k and top-p as
+  transformers orders them, then one multinomial draw per row, all in one workgroup per row and in fixed-order sums.  The draw's
+  uniform is a counter hash of (seed, row, column); the seed lives in device memory, so the captured step serves every seed, while
+  the temperature, top-k and top-p are baked in.  ``num_return_sequences = n`` runs B * n rows, [image][k], over one copy of each
+  image's cross-attention k / v (``kv_group = n``).
 """
 from __future__ import annotations
 
@@ -97,8 +102,8 @@ class _TextLayer(nn.Module):
 
 
 class BlipCaptioner(nn.Module):
-    """``BlipForConditionalGeneration`` (vision tower + text decoder + LM head) for greedy and beam-search captioning on the HIP
-    kernels."""
+    """``BlipForConditionalGeneration`` (vision tower + text decoder + LM head) for greedy, beam-search and sampled captioning on the
+    HIP kernels."""
 
     def __init__(self, text: dict, vision: dict, compute_dtype: str = "fp16"):
         super().__init__()
@@ -247,9 +252,10 @@ class BlipCaptioner(nn.Module):
         return y
 
     # ---- decoder state and one step -------------------------------------------------------------------------------------------
-    def _state(self, B: int, cap: int, device, K: int = 1):
-        """buffers of the decode step for B images of K beams: R = B * K rows, cross k / v one copy per image"""
-        key = (B, cap, str(device), K)
+    def _state(self, B: int, cap: int, device, K: int = 1, nseq: int = 1):
+        """buffers of the decode step for B images of K beams, or of nseq sampled sequences (K = 1): R = B * K * nseq rows, cross
+        k / v one copy per image"""
+        key = (B, cap, str(device), K, nseq)
         if key in self._states:
             return self._states[key]
         tc, T16 = self.text_cfg, self._T16()
@@ -257,21 +263,23 @@ class BlipCaptioner(nn.Module):
         Ni = (self.vision_cfg["image_size"] // self.vision_cfg["patch_size"]) ** 2 + 1
         Vp = self._pack["head"][3].shape[0]
         e = lambda *s, dt=T16: torch.empty(s, dtype=dt, device=device)
-        R = B * K
+        R = B * K * nseq
+        rows = R if K == 1 else B          # rows of the greedy / sampled selection (beam search keeps its own state)
         ns_self, ns_cross = ops.decode_splits(R, H, cap), ops.decode_splits(R, H, Ni)
-        st = dict(B=B, K=K, R=R, cap=cap, Ni=Ni, ns_self=ns_self, ns_cross=ns_cross,
+        st = dict(B=B, K=K, G=K * nseq, R=R, cap=cap, Ni=Ni, ns_self=ns_self, ns_cross=ns_cross,
                   cache=[torch.zeros((R, cap, 2 * D), dtype=T16, device=device) for _ in range(nl)],
                   ckv=[e(B * Ni, 2 * D) for _ in range(nl)],
                   x=e(R, D), x1=e(R, D), s=e(R, D), ctx=e(R, D), q=e(R, D), qkv=e(R, 3 * D), ffn=e(R, I), h=e(R, D),
                   mean=e(R, dt=F32), rstd=e(R, dt=F32), logits=e(R, Vp, dt=F32),
                   ws=e(R * H * max(ns_self, ns_cross, 1) * 66, dt=F32),
-                  out_ids=e(B, cap, dt=I64), next_ids=e(R, dt=I64), finished=e(B, dt=I32), sv=e(4, dt=I32), graph=None, beam=None)
+                  out_ids=e(rows, cap, dt=I64), next_ids=e(R, dt=I64), finished=e(rows, dt=I32), sv=e(4, dt=I32), graph=None, beam=None,
+                  rng=torch.zeros(4, dtype=I32, device=device), u=torch.zeros(R, dtype=F32, device=device))
         self._states = {key: st}          # one live batch shape at a time (the caches are large)
         return st
 
     def _step(self, st):
         pk, tc = self._pack, self.text_cfg
-        B, cap, Ni, K = st["R"], st["cap"], st["Ni"], st["K"]       # B: rows of the step ([image][beam] under beam search)
+        B, cap, Ni, G = st["R"], st["cap"], st["Ni"], st["G"]       # B: rows of the step ([image][beam] or [image][sequence]), G per image
         D, H, eps = tc["hidden_size"], tc["num_attention_heads"], tc["layer_norm_eps"]
         beam = st["beam"]
         t = st["sv"][0:1] if beam is None else beam["state"][0:1]
@@ -289,7 +297,7 @@ class BlipCaptioner(nn.Module):
             ops.linear_fwd(ctx, lw["wo"], bias=lw["bo"], residual=x, out=s)
             ops.layernorm_fwd(s, *lw["ln1"], eps, y=x1, mean=mean, rstd=rstd)
             ops.linear_fwd(x1, lw["wcq"], bias=lw["bcq"], out=q)
-            ops.attn_decode(q, kf, kf[D:], ctx, B, H, Ni, D, Ni * 2 * D, 2 * D, D, nsplit=st["ns_cross"], workspace=ws, kv_group=K)
+            ops.attn_decode(q, kf, kf[D:], ctx, B, H, Ni, D, Ni * 2 * D, 2 * D, D, nsplit=st["ns_cross"], workspace=ws, kv_group=G)
             ops.linear_fwd(ctx, lw["wco"], bias=lw["bco"], residual=x1, out=s)
             ops.layernorm_fwd(s, *lw["ln2"], eps, y=x1, mean=mean, rstd=rstd)
             ops.linear_fwd(x1, lw["wi"], bias=lw["bi"], gelu=True, out=ffn)
@@ -300,24 +308,32 @@ class BlipCaptioner(nn.Module):
         ops.layernorm_fwd(h, *lnh, eps, y=x1, mean=mean, rstd=rstd)
         Vp = wdec.shape[0]
         ops.gemm_grouped([ops.Gemm(x1, wdec, st["logits"], B, Vp, D, D, D, Vp, bias=bdec)], False, False)
-        if beam is None:
+        if beam is None and st["sampling"] is not None:
+            ops.sample_step(st["logits"], tc["vocab_size"], st["out_ids"], st["next_ids"], st["finished"], st["sv"], st["P"],
+                            tc["sep_token_id"], tc["pad_token_id"], st["sampling"], st["rng"], u_out=st["u"], process=st["process"])
+        elif beam is None:
             ops.greedy_step(st["logits"], tc["vocab_size"], st["out_ids"], st["next_ids"], st["finished"], st["sv"], st["P"],
                             tc["sep_token_id"], tc["pad_token_id"], process=st["process"])
         else:
             ops.beam_step(st["logits"], tc["vocab_size"], beam, st["P"], st["length_penalty"], st["early_stopping"], tc["sep_token_id"],
                           process=st["process"])
 
-    def _prepare(self, pixel_values, prompt, cap, num_beams=1, length_penalty=1.0, early_stopping=False, process=None):
+    def _prepare(self, pixel_values, prompt, cap, num_beams=1, length_penalty=1.0, early_stopping=False, process=None, sampling=None,
+                 nseq=1, seed=0):
         """vision tower, cross k / v of every layer, and the step's state for this prompt (int64 [B, P] on the device).
-        process: an ``ops.logits_process`` (None: no logits processors, the plain selection kernels)."""
+        process: an ``ops.logits_process`` (None: no logits processors, the plain selection kernels).  sampling: an ``ops.sampling``
+        (None: greedy decoding or beam search) for nseq sequences per image, rows [image][sequence], drawn under ``seed``."""
         img = self.vision_forward(pixel_values)
         B, P = prompt.shape
-        st = self._state(B, cap, pixel_values.device, num_beams)
+        st = self._state(B, cap, pixel_values.device, num_beams, nseq)
+        st["sampling"] = sampling
         st["P"], st["length_penalty"], st["early_stopping"] = P, float(length_penalty), early_stopping
         st["process"] = None if ops.process_is_neutral(process) else process
         pkey = None if st["process"] is None else (process.repetition_penalty, process.no_repeat_ngram_size, process.min_length,
                                                    process.min_new_tokens)
-        st["key"] = (P, num_beams, float(length_penalty), early_stopping, pkey)      # what a captured step has baked in
+        skey = None if sampling is None else (sampling.temperature, sampling.top_k, sampling.top_p)
+        # what a captured step has baked in: the decoding mode and its settings, not the seed (the step reads it from st["rng"])
+        st["key"] = (P, num_beams, float(length_penalty), early_stopping, pkey, skey)
         D = self.text_cfg["hidden_size"]
         gs = [ops.Gemm(img, lw["wckv"], ckv, img.shape[0], 2 * D, img.shape[1], img.shape[1], img.shape[1], 2 * D, bias=lw["bckv"])
               for lw, ckv in zip(self._pack["txt"], st["ckv"])]
@@ -335,8 +351,10 @@ class BlipCaptioner(nn.Module):
                         st["beam"][n].copy_(v)
             return st
         st["out_ids"].fill_(self.text_cfg["pad_token_id"])
-        st["out_ids"][:, :P] = prompt
-        st["next_ids"].copy_(prompt[:, 0])
+        st["out_ids"][:, :P] = prompt.repeat_interleave(nseq, 0) if nseq > 1 else prompt
+        st["next_ids"].copy_(st["out_ids"][:, 0])
+        if sampling is not None:
+            ops.set_sample_rng(st["rng"], seed)
         st["finished"].zero_()
         st["sv"].zero_()
         return st
@@ -345,7 +363,7 @@ class BlipCaptioner(nn.Module):
         """``steps`` decode steps (stops early once every row has finished, checked every ``poll_every`` steps).  ``record``: a
         list that receives each step's logits; ``trace``: a list that receives, per step, a dict of copies of the logits the step
         used and of the beam state after it (``ops.beam_state``'s tensors), or for greedy decoding of ``next_ids`` (the chosen
-        tokens), ``finished`` and ``state``."""
+        tokens), ``finished`` and ``state``, and for a sampled run also of ``u``, the uniforms the step drew with."""
         done = st["sv"] if st["beam"] is None else st["beam"]["state"]
         for i in range(steps):
             if i == 0 or not graph:
@@ -360,8 +378,10 @@ class BlipCaptioner(nn.Module):
             if record is not None:
                 record.append(st["logits"][:, :self.text_cfg["vocab_size"]].clone())
             if trace is not None:
-                if st["beam"] is None:      # greedy: the tokens the step chose, its finished flags and state words after it
+                if st["beam"] is None:      # greedy / sampled: the tokens the step chose, its finished flags and state words after it
                     snap = dict(next_ids=st["next_ids"].clone(), finished=st["finished"].clone(), state=st["sv"].clone())
+                    if st["sampling"] is not None:
+                        snap["u"] = st["u"].clone()                # the uniforms the step drew with
                 else:
                     snap = {n: v.clone() for n, v in st["beam"].items() if isinstance(v, torch.Tensor) and not n.startswith("cand_")}
                 snap["logits"] = st["logits"][:, :self.text_cfg["vocab_size"]].clone()
@@ -387,7 +407,8 @@ class BlipCaptioner(nn.Module):
     @torch.no_grad()
     def generate(self, pixel_values: torch.Tensor, input_ids: Optional[torch.Tensor] = None, attention_mask=None,
                  max_new_tokens: int = 20, *, graph: bool = True, poll_every: int = 8, num_beams: int = 1, length_penalty: float = 1.0,
-                 early_stopping=False, num_return_sequences: int = 1, do_sample: bool = False,
+                 early_stopping=False, num_return_sequences: int = 1, do_sample: bool = False, temperature: float = 1.0,
+                 top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None,
                  repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_length: int = 0, min_new_tokens: int = 0,
                  interpolate_pos_encoding: bool = False, _trace=None) -> torch.LongTensor:
         """``BlipForConditionalGeneration.generate(pixel_values, input_ids, attention_mask, max_new_tokens=...)``:
@@ -410,28 +431,50 @@ class BlipCaptioner(nn.Module):
         does.  With the neutral values (1, 0, 0, 0) the step is exactly the one without them.  Beam search with a processor needs
         ``vocab_size >= 2 * num_beams + prompt + max_new_tokens + 1``, so that the bans leave every beam its candidates.
 
-        ``num_return_sequences = n`` (beam search only, ``1 <= n <= num_beams``): the n best finished beams of every image, best
+        ``num_return_sequences = n`` with beam search (``1 <= n <= num_beams``): the n best finished beams of every image, best
         first, as ``[B * n, L]`` rows ordered [image][rank], cut to the prompt plus the longest generated length among the returned
         rows.  A slot that holds no finished beam (the search closed before n beams finished) yields the prompt followed by the
         padding, with length 0.
 
+        Sampling (``do_sample=True``, ``num_beams=1``; defaults ``temperature=1.0``, ``top_k=50`` -- transformers' default generation
+        config --, ``top_p=1.0``, ``seed=None``): the greedy loop with ``mh_sample_step`` in place of the argmax, inside the device
+        step.  Per row, in transformers' order: the logits processors, ``x / temperature`` (finite, > 0), top-k (an integer >= 0; 0:
+        off; ties at the k-th value are all kept), top-p (in (0, 1]; a token is kept iff the mass of the survivors with a strictly
+        larger value is below ``top_p`` of the total, so equal values at the boundary are all kept), then one multinomial draw over
+        what is kept.  The uniform of a draw is a counter hash of (seed, row, column): the same seed gives the same captions on every
+        run, with or without the graph, and a captured step serves every seed (it reads the seed from device memory).  ``seed``: an
+        int is used as given (its low 64 bits); ``None`` draws 64 bits from torch's default CPU generator, so ``torch.manual_seed``
+        makes a call reproducible.  The stream is not torch.multinomial's: tokens are not those of transformers' sampled ``generate``.
+        ``num_return_sequences = n >= 1`` with sampling (``B * n <= 1024``): n captions per image as ``[B * n, L]`` rows ordered
+        [image][k]; the vision tower runs once per image, and row ``image * n + k`` is the row of the hash, so the n captions differ
+        (and differ from n single calls, whose rows are ``image``).  Without ``do_sample`` the three settings are checked and ignored.
+
         ``graph=False`` runs the same launches without the hipGraph.  Refused with ``ValueError``: ``num_beams`` outside 1..8,
-        ``num_return_sequences`` outside 1..num_beams, sampling, ``interpolate_pos_encoding``, prompt attention masks with zeros,
-        and ``num_beams > 1`` or any logits processor for a model or batch that is not on the HIP device (plain greedy calls there
-        raise ``MemehipError``: there is no CPU path at all)."""
+        ``num_return_sequences`` above num_beams without sampling, ``do_sample=True`` with ``num_beams > 1`` (no beam sampling), values
+        of the sampling settings outside their domains, ``interpolate_pos_encoding``, prompt attention masks with zeros, and
+        ``num_beams > 1``, sampling or any logits processor for a model or batch that is not on the HIP device (plain greedy calls
+        there raise ``MemehipError``: there is no CPU path at all)."""
         if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= 8:
             raise ValueError("num_beams must be an integer from 1 (greedy) to 8")
         nrs = num_return_sequences
         if isinstance(nrs, bool) or not isinstance(nrs, int) or nrs < 1:
             raise ValueError("num_return_sequences must be an integer >= 1")
-        if nrs > num_beams:
-            raise ValueError("num_return_sequences must be <= num_beams (more than one sequence needs beam search: there is no sampling)")
+        if not isinstance(do_sample, bool):
+            raise ValueError("do_sample must be True or False")
+        if do_sample and num_beams > 1:
+            raise ValueError("do_sample=True needs num_beams=1 (beam sampling is not implemented)")
+        if nrs > num_beams and not do_sample:
+            raise ValueError("num_return_sequences must be <= num_beams (more than one sequence needs beam search or do_sample=True)")
         if not isinstance(early_stopping, bool) and early_stopping != "never":
             raise ValueError("early_stopping must be False, True or 'never'")
-        if do_sample:
-            raise ValueError("sampling is not implemented (greedy decoding and beam search only)")
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
+            raise ValueError("seed must be an integer or None")
+        sampling = ops.sampling(temperature, top_k, top_p)                                                      # ValueError if invalid
+        sampling = sampling if do_sample else None              # (the three are validated, then ignored, without do_sample)
         process = ops.logits_process(repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens)      # ValueError if invalid
         on_device = isinstance(pixel_values, torch.Tensor) and pixel_values.is_cuda and next(self.parameters()).is_cuda
+        if do_sample and not on_device:
+            raise ValueError("sampling (do_sample=True) exists only in the HIP decode step: move the model and batch with .to(device)")
         if num_beams > 1 and not on_device:
             # (the argument is refused, as before beam search existed: the search lives in the device step and nowhere else)
             raise ValueError("beam search (num_beams > 1) exists only in the HIP decode step: move the model and batch with .to(device)")
@@ -464,7 +507,16 @@ class BlipCaptioner(nn.Module):
             bs = st["beam"]
             lens = bs["fin_len"].view(-1, num_beams)[:, :nrs]
             return bs["fin_seq"].view(-1, num_beams, cap)[:, :nrs, :P + int(lens.max())].reshape(-1, P + int(lens.max())).to(I64)
-        st = self._prepare(pixel_values, prompt, cap, process=process)
+        if sampling is None:
+            st = self._prepare(pixel_values, prompt, cap, process=process)
+        else:
+            if prompt.shape[0] * nrs > 1024:
+                raise ValueError("sampling: batch * num_return_sequences must be <= 1024")
+            if self.text_cfg["vocab_size"] > _lib.MH_PROCESS_MAX_VOCAB:
+                raise ValueError(f"sampling needs vocab_size <= {_lib.MH_PROCESS_MAX_VOCAB}")
+            if seed is None:
+                seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=I64).item())      # torch's default CPU generator
+            st = self._prepare(pixel_values, prompt, cap, process=process, sampling=sampling, nseq=nrs, seed=seed)
         self._run(st, P - 1 + int(max_new_tokens), graph, int(poll_every), trace=_trace)
         sv = st["sv"].cpu()
         length = int(sv[3]) if int(sv[3]) else min(cap, int(sv[0]) + 1)

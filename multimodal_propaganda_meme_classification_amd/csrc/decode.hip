@@ -8,6 +8,8 @@
 //                    the ordered top 2K of K*V candidates and the running / finished bookkeeping of transformers' _beam_search
 //   mh_greedy_step_processed / mh_beam_step_processed   the same two with transformers' repetition penalty, n-gram ban and minimum
 //                    lengths applied inside the selection kernels (instantiations of their own: the plain ones are unchanged)
+//   mh_sample_step   the greedy step with a temperature / top-k / top-p filtered multinomial draw in place of the argmax (with the
+//                    processors first when any is set), one counter-hash uniform per (seed, row, column)
 //
 // Beams: the rows are [image][beam].  Cross-attention k / v stay one copy per image (kv_group rows share it).  The self-attention
 // cache does not move when beams are re-ordered: an ancestry table src[row][position] names the physical cache row that holds the
@@ -367,6 +369,385 @@ __global__ void __launch_bounds__(256) greedy_step_processed_kernel(const float*
                                                                     int64_t eos, int64_t pad, ProcArgs pa) {
     __shared__ ProcLds pl;
     greedy_step_body<true>(logits, ldl, V, out_ids, ld_out, next_ids, finished, state, prompt_len, eos, pad, pa, &pl);
+}
+
+// ---- sampling (transformers' TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper, then one multinomial draw) ---------------
+// One workgroup per row, the greedy step's contract.  Wave w owns the contiguous quarter [w * Q, (w + 1) * Q) of the row and reads it
+// 256 values per trip (lane l the four values at 4 l of the trip: coalesced 16-byte loads), so the index order is (wave, trip, lane,
+// element) and every prefix sum below follows it.  The row is re-read from L2 in each pass (122 KB at V = 30524), and every pass
+// recomputes v = canon(fdiv_rn(proc_apply(x), temperature)) with the same correctly rounded operations (canon: -0 becomes +0, so that
+// equal values have equal keys).  Passes:
+//   1. m = the row's maximum and greedy's arg_better winner.  m not finite (a NaN, +inf, or an all -inf row): Z would not be a positive
+//      finite number, and the winner is the token.  Past this point every v is finite or -inf and e = expf(v - m) lies in [0, 1].
+//   2. top-k (0 < top_k < V): radix select of the k-th largest order-preserving uint key, 8 bits per pass: 256 integer counts in LDS.
+//      Kept: key >= that key, ties at the threshold included (TopKLogitsWarper removes `scores < kth`).
+//   3. top-p (top_p < 1): radix select by mass over the top-k survivors.  The masses are integers, e * 2^40 truncated into uint64, so a
+//      bin's mass is an exact, order-independent sum of LDS integer atomics (no floating-point atomic anywhere).  A value is kept iff
+//      the survivors' mass strictly above it is < top_p * Z, compared in double.  Equal values share a key, so equal values that
+//      straddle the boundary are all kept (torch.sort leaves that choice open).  Truncation loses < 2^-40 per value, < 2^-25 of Z
+//      over 32768 values (Z >= 2^40 in these units: the maximum contributes e = 1).
+//   4. the draw, in f32: u = (h >> 8) * 2^-24, target = u * Z_kept, and the token is the first kept index whose inclusive prefix mass
+//      exceeds the target; if rounding leaves none, the last kept index with a finite value.  Summation chains: a lane's four values
+//      (3 additions), the trip's scan or sum across the wave's 64 lanes (6), the wave's running total over its trips (at most 32 at
+//      V = 32768), the three earlier waves (3) and the two additions that join these parts: at most 46 f32 additions on any term's
+//      way into any mass, inside the 256 the contract allows, so every mass is within 256 * 2^-24 = 2^-16 of its exact value
+//      relative to Z.  All of it runs in a fixed order: the same logits, settings and seed give the same token on every run.
+// Histogram bins are kept in SMP_COPIES copies selected by lane & 7 (logits share their high key bits, so the first pass of a select
+// sends most values to a few bins; the copies cut that LDS conflict by eight) and summed, as integers, when a pass ends.
+constexpr int SMP_COPIES = 8;
+constexpr float SMP_FX = 1099511627776.0f;      // 2^40
+
+struct SampleArgs {
+    float temperature, top_p;
+    int top_k;
+};
+
+struct SampleLds {
+    unsigned long long mass[256 * SMP_COPIES];
+    uint32_t cnt[256 * SMP_COPIES];
+    unsigned long long w64[4], pick_above;
+    uint32_t w32[4], pick_bin, pick_need;
+    float wf[4];
+    int wi[4], wj[4];
+};
+
+MH_DEV uint32_t sample_key(float x) {            // larger float <=> larger key (x is finite, +-inf or canonical zero)
+    const uint32_t u = __float_as_uint(x);
+    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
+// uniform of (row, col) under the seed words: (h >> 8) * 2^-24 in [0, 1)
+MH_DEV float sample_uniform(const uint32_t* rng, uint32_t row, uint32_t col) {
+    uint32_t h = mh_hash32(rng[0] ^ 0x9E3779B9u);
+    h = mh_hash32(h + rng[1]);
+    h = mh_hash32(h + row);
+    h = mh_hash32(h + col);
+    return (float)(h >> 8) * 5.9604644775390625e-08f;
+}
+
+// The raw logits of SMP_AHEAD consecutive trips of a lane (columns c0 + 256 u .. + 3), loaded together: a wave has one quarter of
+// the row to itself, so a pass is bound by the latency of its loads unless several are in flight.  A trip at or past `end` reads
+// column `safe` instead (a multiple of 4 below `end`: an address inside the row; the caller drops the values).
+constexpr int SMP_AHEAD = 4;
+
+MH_DEV void sample_fetch(const float* row, int c0, int end, int safe, f32x4 (&raw)[SMP_AHEAD]) {
+#pragma unroll
+    for (int u = 0; u < SMP_AHEAD; ++u) {
+        const int c = c0 + 256 * u;
+        raw[u] = *reinterpret_cast<const f32x4*>(row + (c < end ? c : safe));
+    }
+}
+
+// the four processed, tempered values of the raw logits x at columns c .. c + 3 (c a multiple of 4 below V)
+template <bool PROC>
+MH_DEV void sample_load4(f32x4 x, int c, const ProcLds* pl, const ProcArgs& pa, float temperature, float (&v)[4]) {
+    if constexpr (PROC) {
+        const uint32_t sw = pl->seen[c >> 5] >> (c & 31), bw = pl->banned[c >> 5] >> (c & 31);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = proc_apply(x[i], sw, bw, i, pa.penalty);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float y = temperature != 1.f ? __fdiv_rn(x[i], temperature) : x[i];
+        v[i] = y == 0.f ? 0.f : y;
+    }
+}
+
+template <typename T>
+MH_DEV T wave_incl_scan(T v, unsigned lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T n = __shfl_up(v, o, 64);
+        if (lane >= (unsigned)o) v += n;
+    }
+    return v;
+}
+
+// inclusive scan over the 256 threads in thread order (integers: exact), and the total
+template <typename T>
+MH_DEV T block_incl_scan(T v, T* sh, T& total) {
+    const int w = threadIdx.x >> 6;
+    const unsigned lane = threadIdx.x & 63;
+    v = wave_incl_scan(v, lane);
+    __syncthreads();
+    if (lane == 63) sh[w] = v;
+    __syncthreads();
+    T off = 0;
+    for (int i = 0; i < w; ++i) off += sh[i];
+    total = sh[0] + sh[1] + sh[2] + sh[3];
+    return v + off;
+}
+
+// One histogram pass: the values whose key agrees with pfx above bit shift + 8 and is >= floor_key, binned by key bits
+// shift .. shift + 7.  MASS: the bins receive e * 2^40, else 1.  Complete (and synchronised) when it returns.
+template <bool PROC, bool MASS>
+MH_DEV void sample_hist(SampleLds& L, const float* row, int V, int Q, const ProcLds* pl, const ProcArgs& pa, float temperature, float m,
+                        uint32_t pfx, int shift, uint32_t floor_key) {
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    for (int i = tid; i < 256 * SMP_COPIES; i += 256) {
+        if constexpr (MASS) L.mass[i] = 0ull;
+        else L.cnt[i] = 0u;
+    }
+    __syncthreads();
+    const int end = min((w + 1) * Q, V);
+    for (int c0 = w * Q + lane * 4; c0 < end; c0 += 256 * SMP_AHEAD) {
+        f32x4 raw[SMP_AHEAD];
+        sample_fetch(row, c0, end, c0, raw);
+#pragma unroll
+        for (int u = 0; u < SMP_AHEAD; ++u) {
+            const int c = c0 + 256 * u;
+            if (c >= end) break;
+            float v[4];
+            sample_load4<PROC>(raw[u], c, pl, pa, temperature, v);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint32_t key = sample_key(v[i]);
+                if (c + i < V && key >= floor_key && (shift == 24 || ((key ^ pfx) >> (shift + 8)) == 0u)) {
+                    const int slot = (int)((key >> shift) & 255u) * SMP_COPIES + (lane & (SMP_COPIES - 1));
+                    if constexpr (MASS) atomicAdd(&L.mass[slot], (unsigned long long)(expf(v[i] - m) * SMP_FX));
+                    else atomicAdd(&L.cnt[slot], 1u);
+                }
+            }
+        }
+    }
+    __syncthreads();
+}
+
+template <bool PROC>
+MH_DEV void sample_step_body(const float* logits, int ldl, int V, int64_t* out_ids, int ld_out, int64_t* next_ids, int32_t* finished,
+                             int32_t* state, int prompt_len, int64_t eos, int64_t pad, const SampleArgs& sa, const uint32_t* rng,
+                             float* u_out, const ProcArgs& pa, ProcLds* pl, SampleLds& L) {
+    const int b = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
+    const unsigned lane = tid & 63;
+    const int t = state[0];
+    const int col = t + 1;
+    const bool fin = finished[b] != 0;
+    const bool gen = col >= prompt_len && !fin;
+    const float u = sample_uniform(rng, (uint32_t)b, (uint32_t)col);
+    int tok_s = 0;
+    if (gen) {
+        const float* row = logits + (int64_t)b * ldl;
+        const float T = sa.temperature;
+        const int Q = ((V + 3) / 4 + 255) & ~255;              // a wave's span: whole trips of 256
+        const int base0 = w * Q, end = min((w + 1) * Q, V);    // (wave-uniform)
+        if constexpr (PROC) proc_build(*pl, out_ids + (int64_t)b * ld_out, min(col, ld_out), V, prompt_len, pa);
+
+        // 1. maximum and greedy's winner
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int c0 = base0 + (int)lane * 4; c0 < end; c0 += 256 * SMP_AHEAD) {
+            f32x4 raw[SMP_AHEAD];
+            sample_fetch(row, c0, end, c0, raw);
+#pragma unroll
+            for (int u = 0; u < SMP_AHEAD; ++u) {
+                const int c = c0 + 256 * u;
+                if (c >= end) break;
+                float v[4];
+                sample_load4<PROC>(raw[u], c, pl, pa, T, v);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (c + i < V && arg_better(v[i], c + i, bv, bi)) {
+                        bv = v[i];
+                        bi = c + i;
+                    }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (arg_better(ov, oi, bv, bi)) {
+                bv = ov;
+                bi = oi;
+            }
+        }
+        if (lane == 0) {
+            L.wf[w] = bv;
+            L.wi[w] = bi;
+        }
+        __syncthreads();
+        bv = L.wf[0], bi = L.wi[0];
+        for (int ww = 1; ww < 4; ++ww)
+            if (arg_better(L.wf[ww], L.wi[ww], bv, bi)) {
+                bv = L.wf[ww];
+                bi = L.wi[ww];
+            }
+        const float m = bv;
+        tok_s = bi < V ? bi : 0;
+        __syncthreads();                                         // (wf / wi are written again below)
+
+        if (fabsf(m) <= 3.402823466e38f) {                       // finite (uniform over the workgroup: every thread holds the same m)
+            // 2. top-k: the k-th largest key
+            uint32_t kkey = 0u;
+            if (sa.top_k > 0 && sa.top_k < V) {
+                uint32_t pfx = 0u, need = (uint32_t)sa.top_k;
+                for (int shift = 24; shift >= 0; shift -= 8) {
+                    sample_hist<PROC, false>(L, row, V, Q, pl, pa, T, m, pfx, shift, 0u);
+                    const int bin = 255 - tid;                   // thread order = descending bins
+                    uint32_t cb = 0u;
+#pragma unroll
+                    for (int i = 0; i < SMP_COPIES; ++i) cb += L.cnt[bin * SMP_COPIES + i];
+                    uint32_t total;
+                    const uint32_t incl = block_incl_scan(cb, L.w32, total), excl = incl - cb;
+                    if (excl < need && need <= incl) {
+                        L.pick_bin = (uint32_t)bin;
+                        L.pick_need = need - excl;
+                    }
+                    __syncthreads();
+                    pfx |= (L.pick_bin & 255u) << shift;
+                    need = L.pick_need;
+                }
+                kkey = pfx;
+            }
+            // 3. top-p: the lowest key whose mass strictly above is < top_p * Z
+            uint32_t tkey = kkey;
+            if (sa.top_p < 1.f) {
+                uint32_t pfx = 0u;
+                unsigned long long above = 0ull;
+                double pz = 0.0;
+                for (int shift = 24; shift >= 0; shift -= 8) {
+                    sample_hist<PROC, true>(L, row, V, Q, pl, pa, T, m, pfx, shift, kkey);
+                    const int bin = 255 - tid;
+                    unsigned long long mb = 0ull;
+#pragma unroll
+                    for (int i = 0; i < SMP_COPIES; ++i) mb += L.mass[bin * SMP_COPIES + i];
+                    unsigned long long total;
+                    const unsigned long long incl = block_incl_scan(mb, L.w64, total) + above, excl = incl - mb;
+                    if (shift == 24) pz = (double)sa.top_p * (double)total;
+                    // the bin in which the mass from the top first reaches top_p * Z: it holds the threshold
+                    if ((double)excl < pz && !((double)incl < pz)) {
+                        L.pick_bin = (uint32_t)bin;
+                        L.pick_above = excl;
+                    }
+                    __syncthreads();
+                    pfx |= (L.pick_bin & 255u) << shift;
+                    above = L.pick_above;
+                }
+                tkey = pfx;
+            }
+            // 4. the draw.  First the kept mass: per trip the wave's tree sum, accumulated trip by trip, then the four waves in order
+            float run = 0.f;
+            for (int cb0 = base0; cb0 < end; cb0 += 256 * SMP_AHEAD) {
+                f32x4 raw[SMP_AHEAD];
+                sample_fetch(row, cb0 + (int)lane * 4, end, base0, raw);
+#pragma unroll
+                for (int u = 0; u < SMP_AHEAD; ++u) {
+                    const int cb = cb0 + 256 * u;                // (wave-uniform trips: the shuffles below need every lane)
+                    if (cb >= end) break;
+                    const int c = cb + (int)lane * 4;
+                    float e[4] = {0.f, 0.f, 0.f, 0.f};
+                    if (c < end) {
+                        float v[4];
+                        sample_load4<PROC>(raw[u], c, pl, pa, T, v);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) e[i] = (c + i < V && sample_key(v[i]) >= tkey) ? expf(v[i] - m) : 0.f;
+                    }
+                    run += wave_sum(((e[0] + e[1]) + e[2]) + e[3]);
+                }
+            }
+            if (lane == 0) L.wf[w] = run;
+            __syncthreads();
+            const float woff = w == 0 ? 0.f : (w == 1 ? L.wf[0] : (w == 2 ? L.wf[0] + L.wf[1] : (L.wf[0] + L.wf[1]) + L.wf[2]));
+            const float Z = ((L.wf[0] + L.wf[1]) + L.wf[2]) + L.wf[3];
+            if (Z > 0.f && Z < INFINITY) {
+                const float target = __fmul_rn(u, Z);
+                // then the same walk again: inclusive prefix of a value = (waves before + trips before) + (lanes before + the lane's own)
+                int first = 0x7fffffff, last = -1;
+                run = 0.f;
+                for (int cb0 = base0; cb0 < end; cb0 += 256 * SMP_AHEAD) {
+                    f32x4 raw[SMP_AHEAD];
+                    sample_fetch(row, cb0 + (int)lane * 4, end, base0, raw);
+#pragma unroll
+                    for (int u = 0; u < SMP_AHEAD; ++u) {
+                        const int cb = cb0 + 256 * u;
+                        if (cb >= end) break;
+                        const int c = cb + (int)lane * 4;
+                        float e[4] = {0.f, 0.f, 0.f, 0.f};
+                        bool kept[4] = {false, false, false, false};
+                        if (c < end) {
+                            float v[4];
+                            sample_load4<PROC>(raw[u], c, pl, pa, T, v);
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                kept[i] = c + i < V && sample_key(v[i]) >= tkey && v[i] != -INFINITY;
+                                e[i] = kept[i] ? expf(v[i] - m) : 0.f;
+                            }
+                        }
+                        const float s0 = e[0], s1 = s0 + e[1], s2 = s1 + e[2], s3 = s2 + e[3];
+                        const float incl = wave_incl_scan(s3, lane);
+                        float before = __shfl_up(incl, 1, 64);
+                        if (lane == 0) before = 0.f;
+                        const float base = woff + run;
+                        const float pre[4] = {base + (before + s0), base + (before + s1), base + (before + s2), base + (before + s3)};
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (kept[i]) {
+                                last = c + i;
+                                if (pre[i] > target && first == 0x7fffffff) first = c + i;
+                            }
+                        run += wave_sum(s3);
+                    }
+                }
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) {
+                    first = min(first, __shfl_xor(first, o, 64));
+                    last = max(last, __shfl_xor(last, o, 64));
+                }
+                if (lane == 0) {
+                    L.wi[w] = first;
+                    L.wj[w] = last;
+                }
+                __syncthreads();
+                first = min(min(L.wi[0], L.wi[1]), min(L.wi[2], L.wi[3]));
+                last = max(max(L.wj[0], L.wj[1]), max(L.wj[2], L.wj[3]));
+                if (first < V) tok_s = first;
+                else if (last >= 0) tok_s = last;
+            }
+        }
+    }
+    if (tid == 0) {
+        if (u_out) u_out[b] = u;
+        if (col < ld_out) {
+            int64_t tok;
+            if (col < prompt_len) {
+                tok = out_ids[(int64_t)b * ld_out + col];         // still inside the prompt: its next token
+            } else if (fin) {
+                tok = pad;
+            } else {
+                tok = tok_s;
+                if (tok == eos) {
+                    finished[b] = 1;
+                    const int nf = __hip_atomic_fetch_add(&state[2], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (nf == gridDim.x - 1) __hip_atomic_store(&state[3], col + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+            out_ids[(int64_t)b * ld_out + col] = tok;
+            next_ids[b] = tok;
+        }
+        // the greedy step's arrival protocol: the last workgroup to arrive advances t and re-arms the counter
+        const int arrived = __hip_atomic_fetch_add(&state[1], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        if (arrived == gridDim.x - 1) {
+            __hip_atomic_store(&state[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&state[0], t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) sample_step_kernel(const float* logits, int ldl, int V, int64_t* out_ids, int ld_out, int64_t* next_ids,
+                                                          int32_t* finished, int32_t* state, int prompt_len, int64_t eos, int64_t pad,
+                                                          SampleArgs sa, const uint32_t* rng, float* u_out) {
+    __shared__ SampleLds L;
+    sample_step_body<false>(logits, ldl, V, out_ids, ld_out, next_ids, finished, state, prompt_len, eos, pad, sa, rng, u_out, ProcArgs{},
+                            nullptr, L);
+}
+
+__global__ void __launch_bounds__(256) sample_step_processed_kernel(const float* logits, int ldl, int V, int64_t* out_ids, int ld_out,
+                                                                    int64_t* next_ids, int32_t* finished, int32_t* state, int prompt_len,
+                                                                    int64_t eos, int64_t pad, SampleArgs sa, const uint32_t* rng,
+                                                                    float* u_out, ProcArgs pa) {
+    __shared__ SampleLds L;
+    __shared__ ProcLds pl;
+    sample_step_body<true>(logits, ldl, V, out_ids, ld_out, next_ids, finished, state, prompt_len, eos, pad, sa, rng, u_out, pa, &pl, L);
 }
 
 // ---- beam search ------------------------------------------------------------------------------------------------------------------
@@ -769,6 +1150,31 @@ extern "C" int mh_greedy_step(const float* logits, int ldl, int V, int B, int64_
                               int32_t* finished, int32_t* state, int prompt_len, int64_t eos_id, int64_t pad_id, mh_stream_t stream) {
     return mh_greedy_step_processed(logits, ldl, V, B, out_ids, ld_out, next_ids, finished, state, prompt_len, eos_id, pad_id, &PROC_NEUTRAL,
                                     stream);
+}
+
+extern "C" int mh_sample_step(const float* logits, int ldl, int V, int B, int64_t* out_ids, int ld_out, int64_t* next_ids,
+                              int32_t* finished, int32_t* state, int prompt_len, int64_t eos_id, int64_t pad_id, const MhSampling* sampling,
+                              const uint32_t* rng, float* u_out, const MhLogitsProcess* process, mh_stream_t stream) {
+    if (!logits || !out_ids || !next_ids || !finished || !state || !sampling || !rng) return MH_EINVAL;
+    ProcArgs pa;
+    bool on;
+    if (const int st = proc_settings(process ? process : &PROC_NEUTRAL, V, eos_id, &pa, &on)) return st;
+    if (B < 1 || V < 1 || ldl < V || ldl % 4 || prompt_len < 1 || ld_out <= prompt_len) return MH_ESHAPE;
+    if (V > PROC_MAX_V || (on && ld_out > PROC_MAX_HIST)) return MH_ESHAPE;
+    if (!(sampling->temperature > 0.f) || sampling->temperature > 3.0e38f || sampling->top_k < 0 || !(sampling->top_p > 0.f) ||
+        sampling->top_p > 1.f)
+        return MH_ESHAPE;
+    SampleArgs sa;
+    sa.temperature = sampling->temperature;
+    sa.top_p = sampling->top_p;
+    sa.top_k = sampling->top_k;
+    if (on)
+        hipLaunchKernelGGL(sample_step_processed_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ldl, V, out_ids, ld_out,
+                           next_ids, finished, state, prompt_len, eos_id, pad_id, sa, rng, u_out, pa);
+    else
+        hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ldl, V, out_ids, ld_out, next_ids,
+                           finished, state, prompt_len, eos_id, pad_id, sa, rng, u_out);
+    return mh_launch_status();
 }
 
 extern "C" int mh_beam_step_processed(const float* logits, int ldl, int V, int B, int K, const MhBeamState* st, int cap, int prompt_len,

@@ -86,12 +86,15 @@ class BlipImageCaptioning:
     ``BlipProcessor`` (image preprocessing, prompt tokens and decoding; there is no tokenizer or hub access here) and the captioner
     holding the ``blip-image-captioning-large`` weights (``BlipCaptioner.from_config(cfg, device=...)`` +
     ``load_state_dict(BlipForConditionalGeneration state_dict)``).  ``generate_kwargs`` go to ``BlipCaptioner.generate`` as they
-    are: ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``min_new_tokens`` (none of them set: the reference's
-    captions).  ``image_pipeline`` (``DeviceImagePipeline.blip()`` or ``.from_processor(processor)``): the images are resized and
+    are: ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``min_new_tokens``, and for sampled captions ``do_sample``,
+    ``temperature``, ``top_k``, ``top_p`` and ``seed`` (none of them set: the reference's captions; with a fixed ``seed`` every batch
+    draws with the same uniforms per row and column, with ``seed=None`` each batch takes a fresh seed from torch's CPU generator).
+    Still one caption per image.  ``image_pipeline`` (``DeviceImagePipeline.blip()`` or ``.from_processor(processor)``): the images are resized and
     normalised on the device, bit for bit as ``BlipImageProcessor`` does it on the host one image at a time, and the processor is asked
     for the prompt tokens and the decoding only."""
 
-    _GENERATE_KWARGS = ("repetition_penalty", "no_repeat_ngram_size", "min_length", "min_new_tokens")
+    _GENERATE_KWARGS = ("repetition_penalty", "no_repeat_ngram_size", "min_length", "min_new_tokens", "do_sample", "temperature", "top_k",
+                        "top_p", "seed")
 
     def __init__(self, processor, captioner, max_new_tokens: int = 128, graph: bool = True, num_beams: int = 1,
                  length_penalty: float = 1.0, early_stopping=False, image_pipeline: Optional[DeviceImagePipeline] = None,
@@ -123,7 +126,8 @@ def blip_caption_fn(processor, captioner, prompt: str = "a meme of", batch_size:
                     early_stopping=False, image_pipeline: Optional[DeviceImagePipeline] = None, **generate_kwargs) -> Callable:
     """``caption_fn(paths) -> list of str`` for ``KevinMultimodalDataset``: the reference's ``precompute_captions`` (:235-251) --
     images opened as RGB in batches of ``batch_size`` and captioned with ``prompt`` -- on ``BlipImageCaptioning``, which receives
-    ``generate_kwargs`` (``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``min_new_tokens``) and ``image_pipeline``."""
+    ``generate_kwargs`` (``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``min_new_tokens``; ``do_sample``,
+    ``temperature``, ``top_k``, ``top_p`` and ``seed`` for sampled captions, still one per image) and ``image_pipeline``."""
     cap = BlipImageCaptioning(processor, captioner, max_new_tokens=max_new_tokens, num_beams=num_beams, length_penalty=length_penalty,
                               early_stopping=early_stopping, image_pipeline=image_pipeline, **generate_kwargs)
     if image_loader is None:

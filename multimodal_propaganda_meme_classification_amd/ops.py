@@ -870,6 +870,69 @@ def greedy_step(logits, V, out_ids, next_ids, finished, state, prompt_len, eos_i
                      f"(V = {int(V)}, {out_ids.shape[1]} columns)")
 
 
+def sampling(temperature=1.0, top_k=0, top_p=1.0):
+    """The settings of sample_step's ``sampling`` (MhSampling in include/memehip.h), validated: the temperature a finite number > 0,
+    top_k an integer >= 0 (0: no top-k filter), top_p a number in (0, 1].  The defaults are neutral: a draw from the whole softmax."""
+    import math
+    for name, v in (("temperature", temperature), ("top_p", top_p)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+    if not temperature > 0 or not C.c_float(temperature).value > 0 or math.isinf(C.c_float(temperature).value):
+        raise ValueError(f"temperature must be > 0 (and a finite float32), got {temperature!r}")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k < 2 ** 31:
+        raise ValueError(f"top_k must be an integer >= 0, got {top_k!r}")
+    if not 0 < top_p <= 1 or not C.c_float(top_p).value > 0:
+        raise ValueError(f"top_p must lie in (0, 1], got {top_p!r}")
+    return _lib.MhSampling(float(temperature), top_k, float(top_p))
+
+
+def sampling_is_neutral(sampling) -> bool:
+    if not isinstance(sampling, _lib.MhSampling):
+        raise TypeError("sampling is a sampling(...)")
+    return sampling.temperature == 1.0 and sampling.top_k == 0 and sampling.top_p == 1.0
+
+
+def sample_rng(seed: int, device) -> torch.Tensor:
+    """device int32 [4] {seed_lo, seed_hi, 0, 0}: the seed words of sample_step (the low 64 bits of ``seed``)"""
+    t = torch.zeros(4, dtype=torch.int32, device=device)
+    return set_sample_rng(t, seed)
+
+
+def set_sample_rng(rng: torch.Tensor, seed: int) -> torch.Tensor:
+    """writes the low 64 bits of ``seed`` into rng[0:2] (a buffer a captured step reads keeps its address)"""
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"seed must be an integer, got {seed!r}")
+    words = [(seed >> s) & 0xffffffff for s in (0, 32)]
+    rng[:2].copy_(torch.tensor([w - (1 << 32) if w >= 1 << 31 else w for w in words], dtype=torch.int32))
+    return rng
+
+
+def sample_step(logits, V, out_ids, next_ids, finished, state, prompt_len, eos_id, pad_id, sampling, rng, u_out=None, process=None):
+    """mh_sample_step over f32 logits [B, ldl] (ldl >= V): the greedy step with a temperature / top-k / top-p filtered multinomial
+    draw in place of the argmax; see include/memehip.h.  sampling: a sampling(); rng: device int32 [4] (sample_rng); u_out: None or
+    device f32 [B], receives each row's uniform; process: a logits_process() applied first (None or neutral: none)."""
+    _chk(logits, F32, "logits"), _chk(out_ids, I64, "out_ids"), _chk(next_ids, I64, "next_ids")
+    _i32(finished, "finished"), _i32(state, "state")
+    if not isinstance(sampling, _lib.MhSampling):
+        raise TypeError("sampling is a sampling(...)")
+    B, ldl = logits.shape
+    if out_ids.dim() != 2 or out_ids.shape[0] != B or next_ids.numel() < B or finished.numel() < B or state.numel() < 4 or V > ldl:
+        raise ValueError("sample_step: shapes disagree")
+    if u_out is not None and (_chk(u_out, F32, "u_out").numel() < B):
+        raise ValueError("sample_step: u_out holds fewer than B values")
+    neutral = process_is_neutral(process)
+    status = _lib.load().mh_sample_step(_p(logits), ldl, int(V), B, _p(out_ids), out_ids.shape[1], _p(next_ids), _p(finished), _p(state),
+                                        int(prompt_len), int(eos_id), int(pad_id), C.byref(sampling), _rng(rng), _p(u_out),
+                                        None if neutral else C.byref(process), _stream())
+    if status == _lib.MH_ESHAPE and int(V) > _lib.MH_PROCESS_MAX_VOCAB:
+        raise ValueError(f"mh_sample_step: V <= {_lib.MH_PROCESS_MAX_VOCAB} is supported (V = {int(V)})")
+    if neutral:
+        check(status, "mh_sample_step")
+    else:
+        _check_processed(status, "mh_sample_step", f"V <= {_lib.MH_PROCESS_MAX_VOCAB} and at most {_lib.MH_PROCESS_MAX_HISTORY} output "
+                         f"columns are supported (V = {int(V)}, {out_ids.shape[1]} columns)")
+
+
 BEAM_NEG = -1.0e9
 
 

@@ -10,6 +10,10 @@ reported next to every rate.  Prints one JSON line; --out also writes it to a fi
 --repetition-penalty / --no-repeat-ngram-size / --min-length / --min-new-tokens: a further run, ours_graph_processed, with these
 generate() settings joins the alternation (the other runs stay without them), and its time over the plain graph run's is reported.
 
+--do-sample (with --temperature / --top-k / --top-p, generate()'s defaults 1.0 / 50 / 1.0): two further runs join the alternation,
+ours_graph_sampled and transformers' fp16 generate(do_sample=True) with the same settings (hf_fp16_sampled); the sampled run's time
+over the greedy graph run's and the sampled step's time are reported.  Greedy decoding only (--num-beams 1).
+
   python tools/caption_bench.py --out profiles/r05_caption_bench.json
   rocprofv3 --kernel-trace --stats -d DIR -o caption -- python tools/caption_bench.py --runs 1 --no-hf      (kernel table)
 """
@@ -69,11 +73,19 @@ def main():
     ap.add_argument("--no-repeat-ngram-size", type=int, default=0)
     ap.add_argument("--min-length", type=int, default=0)
     ap.add_argument("--min-new-tokens", type=int, default=0)
+    ap.add_argument("--do-sample", action="store_true", help="add sampled runs (ours and transformers') with the settings below")
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=50)
+    ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     proc = dict(repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size, min_length=args.min_length,
                 min_new_tokens=args.min_new_tokens)
     processed = proc != dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, min_new_tokens=0)
+
+    samp = dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
+    if args.do_sample and args.num_beams != 1:
+        ap.error("--do-sample needs --num-beams 1")
 
     import __graft_entry__ as g
     g.build()
@@ -97,12 +109,18 @@ def main():
     runs = {"ours_graph": [], "ours_graph_processed": [], "ours_eager": [], "hf_fp16": []}
     if not processed:
         del runs["ours_graph_processed"]
+    if args.do_sample:
+        runs.update({"ours_graph_sampled": [], "hf_fp16_sampled": []})
     steps = {}
     for r in range(args.runs + 1):
         for name in runs:
-            if name == "hf_fp16" and hf is None:
+            if name.startswith("hf_fp16") and hf is None:
                 continue
-            if name == "hf_fp16":
+            if name == "hf_fp16_sampled":
+                dt, out = timed(lambda: hf.generate(pixel_values=pix.half(), input_ids=prompt.clone().to(dev), max_new_tokens=N, **samp))
+            elif name == "ours_graph_sampled":
+                dt, out = timed(lambda: ours.generate(pix, prompt.clone(), max_new_tokens=N, seed=args.seed + r, **samp))
+            elif name == "hf_fp16":
                 dt, out = timed(lambda: hf.generate(pixel_values=pix.half(), input_ids=prompt.clone().to(dev), max_new_tokens=N, num_beams=K))
             elif name == "ours_graph_processed":
                 dt, out = timed(lambda: ours.generate(pix, prompt.clone(), max_new_tokens=N, num_beams=K, **proc))
@@ -134,6 +152,7 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / n_rep
     step_graph_processed_ms = graph_step_ms(**proc) if processed else None
+    step_graph_sampled_ms = graph_step_ms(seed=args.seed, **samp) if args.do_sample else None
     step_graph_ms = graph_step_ms()
     rewind()
     e0.record()
@@ -173,6 +192,10 @@ def main():
         res["logits_processors"] = proc
         res["decode_step_ms_graph_processed"] = round(step_graph_processed_ms, 4)
         res["processed_over_plain_time"] = round(stat(runs["ours_graph_processed"])["median_s"] / stat(runs["ours_graph"])["median_s"], 4)
+    if args.do_sample:
+        res["sampling"] = {k: v for k, v in samp.items() if k != "do_sample"}
+        res["decode_step_ms_graph_sampled"] = round(step_graph_sampled_ms, 4)
+        res["sampled_over_greedy_time"] = round(stat(runs["ours_graph_sampled"])["median_s"] / stat(runs["ours_graph"])["median_s"], 4)
     res["launches_per_token"] = launches
     res["decode_steps_per_batch"] = prompt.shape[1] - 2 + steps["ours_graph"]
     line = json.dumps(res)
