@@ -477,6 +477,10 @@ int mh_bn1d_fwd(const float* x, int ldx, const float* gamma, const float* beta, 
 int mh_bn1d_bwd(const float* dy, int lddy, const float* x, int ldx, const float* y, int ldy, const float* gamma,
                 const float* save_mean, const float* save_rstd, float* dx, int lddx, float* dgamma, float* dbeta, int B,
                 int F, int relu, mh_stream_t stream);
+/* Row L2 normalisation (BinaryHead's l2_norm, example_scripts/Untitled-2.py:164-167): y[b][:] = x[b][:] / ||x[b]||_2 (no eps, as
+ * the reference), norm[b] = ||x[b]||_2;  bwd: dx = (g - xhat (xhat . g)) / norm with xhat = the forward's y.  f32 [B][D], B <= 65535. */
+int mh_l2norm_fwd(const float* x, float* y, float* norm, int B, int D, mh_stream_t stream);
+int mh_l2norm_bwd(const float* g, const float* xhat, const float* norm, float* dx, int B, int D, mh_stream_t stream);
 int mh_ce_fwd_bwd(const float* logits, const int64_t* labels, float* loss, float* dlogits,
                   int32_t* n_correct, int B, int C, float grad_scale,
                   const float* grad_scale_dev /*device f32[1] or NULL: the dynamic loss scale, multiplied into grad_scale*/,
@@ -759,6 +763,39 @@ int mh_dwconv_nhwc_wgrad(const void* x, const void* dy, float* dw, float* dbias,
                          float scale, int accum, mh_stream_t stream);
 int mh_layer_scale_bwd(const float* W, const float* b, const float* gamma, const float* dWp, const float* dbp, float* dW, float* db,
                        float* dgamma, int C, int K, int accum, mh_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Grouped 3x3 convolution (groupconv.hip): conv2 of a ResNeXt bottleneck (torchvision resnext50_32x4d, the image model of
+ * example_scripts/Untitled-2.py:210-237: 32 groups of 4 / 8 / 16 / 32 channels), nn.Conv2d(C, C, 3, stride, padding=1, groups=groups,
+ * bias=False) on NHWC 16-bit activations [B*H*W][C].  One wave owns 16 output channels and contracts, on mfma_f32_16x16x32, over the
+ * channels of the groups those belong to only (Cg <= 16: 16 channels, two taps per K step; Cg == 32: 32 channels, one tap per step).
+ * One geometry rule for every entry point: g->C == g->Cout == C, C % 32 == 0, Cg = C / groups in {4, 8, 16, 32}, KH == KW == 3,
+ * pad == 1, stride 1 or 2, any B, H, W >= 1; g->ldk is not read; B*H*W < 2^24 and every tensor < 2 GiB.  Ho = (H - 1) / stride + 1.
+ * Anything else: MH_ESHAPE.  A NULL pointer, a 16-bit tensor or packed weight not on a 16-byte boundary, an f32 tensor not on a 4-byte
+ * boundary: MH_EINVAL.  In both cases nothing is written.
+ *   mh_gconv_packed_elems: 16-bit elements of the packed weight (0: C / groups is refused) = 2 * (C / 16) * NS * 512, NS = 5 (Cg <= 16)
+ *                   or 9 (Cg == 32).
+ *   mh_gconv_weight_pack: w f32 [C][Cg][3][3] (the nn.Conv2d weight) -> wk, TWO images [2][C / 16][NS][64][8] of ready MFMA
+ *                   fragments: element j of lane l of K step s of 16-channel block cb is M[row = 16 cb + (l & 15)][k = 8 (l >> 4) + j],
+ *                   k -> (tap, contraction channel): Cg <= 16: tap = 2 s + (k >> 4), channel 16 cb + (k & 15); Cg == 32: tap = s,
+ *                   channel 32 (cb / 2) + k; tap = 3 kh + kw.  Image 0 (forward): row = output channel, contraction = input channel;
+ *                   image 1 (dgrad): row = input channel, contraction = output channel.  Channel pairs of two groups and tap 9 hold 0.
+ *   mh_gconv_fwd:   y[B*Ho*Wo][C], rounded once from the f32 accumulators.  bn_part (or NULL): f32 [2][C][ceil(B*Ho*Wo / 128)], per 128-row
+ *                   tile the column sums of y and y^2 of the values AS STORED -- what mh_bn2d_fwd_parts reads.
+ *   mh_gconv_dgrad: dx[B*H*W][C] from dy[B*Ho*Wo][C], a gather per input pixel over the taps that reach it (stride 2: those of its
+ *                   parity): no col2im panel, no scatter, every element of dx written exactly once.  No BatchNorm epilogue.
+ *   mh_gconv_wgrad: dw f32 [C][Cg][3][3] = (accumulate ? dw : 0) + alpha * sum over the B*Ho*Wo pixels of dy x^T per tap -- the nn.Conv2d
+ *                   weight's layout, so it can BE an f32 .grad.  workspace: f32, >= mh_gconv_wgrad_workspace_elems(g, groups) elements
+ *                   (0: refused): workgroups leave per-chunk partials [chunk][C][Cg][9], a second kernel sums them in chunk order -- no
+ *                   atomics, the same bits on every run.
+ * ------------------------------------------------------------------------------------------ */
+int mh_gconv_packed_elems(int C, int groups);
+int mh_gconv_weight_pack(const float* w, void* wk, int C, int groups, mh_stream_t stream);
+int mh_gconv_fwd(const void* x, const void* wk, void* y, float* bn_part, const MhConvGeom* g, int groups, mh_stream_t stream);
+int mh_gconv_dgrad(const void* dy, const void* wk, void* dx, const MhConvGeom* g, int groups, mh_stream_t stream);
+int mh_gconv_wgrad_workspace_elems(const MhConvGeom* g, int groups);
+int mh_gconv_wgrad(const void* dy, const void* x, float* dw, float* workspace, int accumulate, float alpha, const MhConvGeom* g, int groups,
+                   mh_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimizer (torch.optim.Adam / AdamW, Multimodal_example_task2C.txt:249,217; HF Trainer

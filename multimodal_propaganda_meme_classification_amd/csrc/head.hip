@@ -644,3 +644,40 @@ extern "C" int mh_bn1d_bwd(const float* dy, int lddy, const float* x, int ldx, c
                        gamma, save_mean, save_rstd, dx, lddx, dgamma, dbeta, B, F, relu);
     return mh_launch_status();
 }
+
+// ---- row L2 normalisation (BinaryHead's l2_norm, example_scripts/Untitled-2.py:164-167: x / ||x||_2, no eps) ----------------------------
+// One wave per row; the row is read twice (sum of squares in lane-strided order + the fixed butterfly of wave_sum, then the division).
+namespace {
+__global__ __launch_bounds__(64) void l2norm_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, float* __restrict__ norm, int D) {
+    const float* xr = x + (size_t)blockIdx.x * D;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < D; i += 64) s += xr[i] * xr[i];
+    const float n = sqrtf(wave_sum(s));
+    for (int i = threadIdx.x; i < D; i += 64) y[(size_t)blockIdx.x * D + i] = xr[i] / n;
+    if (threadIdx.x == 0) norm[blockIdx.x] = n;
+}
+// dx = (g - xhat (xhat . g)) / ||x||
+__global__ __launch_bounds__(64) void l2norm_bwd_kernel(const float* __restrict__ g, const float* __restrict__ xhat,
+                                                        const float* __restrict__ norm, float* __restrict__ dx, int D) {
+    const float* gr = g + (size_t)blockIdx.x * D;
+    const float* hr = xhat + (size_t)blockIdx.x * D;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < D; i += 64) s += gr[i] * hr[i];
+    const float dot = wave_sum(s), n = norm[blockIdx.x];
+    for (int i = threadIdx.x; i < D; i += 64) dx[(size_t)blockIdx.x * D + i] = (gr[i] - hr[i] * dot) / n;
+}
+}  // namespace
+
+extern "C" int mh_l2norm_fwd(const float* x, float* y, float* norm, int B, int D, mh_stream_t stream) {
+    if (!x || !y || !norm) return MH_EINVAL;
+    if (B < 1 || D < 1 || B > 65535) return MH_ESHAPE;
+    hipLaunchKernelGGL(l2norm_fwd_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, x, y, norm, D);
+    return mh_launch_status();
+}
+
+extern "C" int mh_l2norm_bwd(const float* g, const float* xhat, const float* norm, float* dx, int B, int D, mh_stream_t stream) {
+    if (!g || !xhat || !norm || !dx) return MH_EINVAL;
+    if (B < 1 || D < 1 || B > 65535) return MH_ESHAPE;
+    hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, g, xhat, norm, dx, D);
+    return mh_launch_status();
+}

@@ -4,6 +4,7 @@ Each function is one ``torch.autograd.Function`` whose forward and backward are 
 
 * ``linear`` / ``linear_bn_act`` -- ``nn.Linear`` and ``nn.Linear -> nn.BatchNorm1d (-> ReLU)`` of Kevin's head
   (Multimodal_example_task2C.py:599-612,641-643); the latter is ONE launch forward when the batch fits a 64-row tile;
+* ``l2_normalize`` -- the row normalisation of the Subtask-2B zoo's ``BinaryHead`` (example_scripts/Untitled-2.py:164-179);
 * ``softmax_gate`` -- ConcatAttention3's ``softmax(., dim=1) * concatenated`` (:495-496);
 * ``max_pool`` / ``masked_mean_pool`` / ``attention_pool`` / ``conv1d_relu_max_pool`` -- the pooling branches of
   ``LLMWithClassificationHead`` (:362-392).
@@ -189,6 +190,34 @@ def softmax_gate(gate_in, features):
     """softmax(gate_in, dim=1) * features  (ConcatAttention3, Multimodal_example_task2C.py:495-496)"""
     _dev(gate_in, features)
     return _SoftmaxGateFn.apply(gate_in, features)
+
+
+class _L2NormFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x2 = _f(x)
+        B, D = x2.shape
+        y, norm = torch.empty_like(x2), torch.empty(B, dtype=F32, device=x2.device)
+        check(_lib.load().mh_l2norm_fwd(x2.data_ptr(), y.data_ptr(), norm.data_ptr(), B, D, _stream()), "mh_l2norm_fwd")
+        ctx.save_for_backward(y, norm)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, norm = ctx.saved_tensors
+        g = _f(dy)
+        dx = torch.empty_like(y)
+        check(_lib.load().mh_l2norm_bwd(g.data_ptr(), y.data_ptr(), norm.data_ptr(), dx.data_ptr(), y.shape[0], y.shape[1], _stream()),
+              "mh_l2norm_bwd")
+        return dx
+
+
+def l2_normalize(x):
+    """x / ||x||_2 per row of [B, D] (``l2_norm`` of example_scripts/Untitled-2.py:164-167; no eps, as there)"""
+    _dev(x)
+    if x.dim() != 2:
+        raise ValueError("l2_normalize expects [B, D] features")
+    return _L2NormFn.apply(x)
 
 
 class _Mca3Fn(torch.autograd.Function):

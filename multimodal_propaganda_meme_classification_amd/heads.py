@@ -295,7 +295,8 @@ class KevinMultimodalClassifier(_Composite):
     ``Linear(512, 512)`` admits): the image tower is ``resnet.ResNet18 / ResNet34`` (``image_model``; its 512-d ``features`` are what
     timm's ``reset_classifier(0)`` leaves) under ``FineTuneMLP(512, proj)``, the text tower a ``TextEncoder`` of its own
     (``text_model``), as in ``OrganizersMultimodalClassifier``; ``towers`` is then None.  ``resnet_layers`` / ``resnet_width``: the
-    tower's ``layers=`` / ``width=`` overrides (tests).
+    tower's ``layers=`` / ``width=`` overrides (tests).  ``image="resnext50_32x4d"`` (Kevin's Subtask-2B zoo, example_scripts/Untitled-2.py:210-237):
+    the same branch over ``resnet.ResNeXt50_32x4d`` -- 2048 features under ``FineTuneMLP(2048, proj)``.
 
     ``image="convnext_tiny"``: the organizers' own image backbone (baselines/extract_feat.py) under the submitted model's head --
     ``timm.create_model(image_model)`` takes any backbone name, and ``FineTuneMLP`` is sized from the tower here.  The image tower is
@@ -321,8 +322,8 @@ class KevinMultimodalClassifier(_Composite):
         self.fusion_method = fusion_method
         if isinstance(image, str):
             from .resnet import RESNETS
-            if image not in ("resnet18", "resnet34", "convnext_tiny"):
-                raise ValueError(f"image must be an ImageConfig, 'resnet18' or 'resnet34', or 'convnext_tiny', got {image!r}")
+            if image not in ("resnet18", "resnet34", "resnext50_32x4d", "convnext_tiny"):
+                raise ValueError(f"image must be an ImageConfig, 'resnext50_32x4d', 'resnet18' or 'resnet34', or 'convnext_tiny', got {image!r}")
             self.towers = None
             self.text_model = TextEncoder(tc, pool="cls", compute_dtype=compute_dtype, seed=seed, grad_stream_scale=grad_stream_scale)
             if image == "convnext_tiny":
@@ -486,3 +487,39 @@ class KevinMultimodalClassifier(_Composite):
         image_output = self.image_fine_tune(v)
         fused_output = self.fusion_layer(text_output, image_output, caption_output)
         return self.output_fc(fused_output).squeeze(1)
+
+
+class BinaryHead(nn.Module):
+    """``BinaryHead`` of example_scripts/Untitled-2.py:170-179: ``fc(l2_norm(fea)) * s`` with ``fc = Sequential(Linear(emb_size, num_class))``."""
+
+    def __init__(self, num_class: int = 2, emb_size: int = 2048, s: float = 16.0):
+        super().__init__()
+        self.s = s
+        self.fc = nn.Sequential(nn.Linear(emb_size, num_class))
+
+    def forward(self, fea: torch.Tensor) -> torch.Tensor:
+        return fused.linear(fused.l2_normalize(fea), self.fc[0].weight, self.fc[0].bias) * self.s
+
+
+class ResNeXt50_32x4d_BH(nn.Module):
+    """``ResNeXt50_32x4d_BH`` of Kevin's Subtask-2B image zoo (example_scripts/Untitled-2.py:210-237): the ResNeXt-50 32x4d features
+    (``net``: ``resnet.ResNeXt50_32x4d(num_classes=0)``, torchvision's keys -- timm's are not mapped) -> ``fea_bn = BatchNorm1d(2048)``
+    with a frozen bias -> ``binary_head`` (L2-normalised features, ``Linear(2048, 2)``, times ``s = 1``) -> logits [B, 2].  The reference's
+    unused ``dropout`` and ``fc`` members are kept under their names so that everything but the backbone has its state_dict keys."""
+    name = "ResNeXt50_32x4d_BH"
+
+    def __init__(self, compute_dtype: str = "fp16", seed: int = 0, **tower_kw):
+        super().__init__()
+        from .model import BatchNorm1d
+        from .resnet import ResNeXt50_32x4d
+        self.model_arch = "resnext50_32x4d"
+        self.net = ResNeXt50_32x4d(num_classes=0, compute_dtype=compute_dtype, seed=seed, **tower_kw)
+        torch.manual_seed(seed + 1)
+        self.fea_bn = BatchNorm1d(self.net.feature_dim)
+        self.fea_bn.bias.requires_grad_(False)
+        self.binary_head = BinaryHead(2, emb_size=self.net.feature_dim, s=1)
+        self.dropout = nn.Dropout(p=0.2)
+        self.fc = nn.Linear(in_features=self.net.feature_dim, out_features=2)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.binary_head(self.fea_bn(self.net.features(x)))

@@ -17,6 +17,10 @@ submodules only HOLD the parameters and running statistics; the arithmetic runs 
   ``dgrad_route`` names (``mh_conv_dgrad``; the strided 1x1 downsamples keep the dgrad GEMM + ``mh_col2im_nhwc`` -- except next to a
   basic block's 3x3 / 2 conv1, where ``pairs_with`` sends both gradients through one ``mh_conv_dgrad_pair`` launch), BatchNorm
   backward; ``ResNet50.options`` (``TowerOptions``) holds its A/B switches;
+* ``ResNeXt50_32x4d`` (torchvision ``resnext50_32x4d``, Kevin's Subtask-2B zoo: example_scripts/Untitled-2.py:210-237) is the same walk: a
+  bottleneck's grouped 3x3 (``_Conv.grouped``) packs with ``mh_gconv_weight_pack`` and runs ``mh_gconv_fwd`` (BatchNorm partials in its
+  epilogue too) / ``mh_gconv_dgrad`` / ``mh_gconv_wgrad`` (straight into the f32 ``.grad``); ``dgrad_route`` names that route ``GROUPED``, so
+  it takes no BatchNorm epilogue and no pairing by the existing rules;
 * the 16-bit gradient stream carries ``grad_stream_scale`` (8192 for fp16), removed where parameter gradients are produced.
 
 ``_ConvTower`` holds that machinery -- ONE forward and ONE backward walk over (conv, BatchNorm) units; a family (``_ResNet``: torchvision's
@@ -41,7 +45,7 @@ from .model import CrossEntropyLoss
 
 F32 = torch.float32
 WGRAD_TILES = 256      # split-K tile target of an ungrouped weight gradient (512 / 384 / 256 / 192: 7.78 / 7.74 / 7.74 / 7.72 ms per step; 256 halves the slabs)
-GEMM, IMPLICIT, COL2IM = "gemm", "implicit", "gemm + col2im"      # the input-gradient routes
+GEMM, IMPLICIT, COL2IM, GROUPED = "gemm", "implicit", "gemm + col2im", "grouped"      # the input-gradient routes
 
 
 @dataclass(frozen=True)
@@ -59,7 +63,10 @@ class TowerOptions:
 def dgrad_route(cv, H, W, opts: TowerOptions) -> str:
     """The input-gradient route of `cv` (a _Conv: geometry only) on an H x W input.  GEMM: a 1x1 / stride 1 is the plain GEMM.
     IMPLICIT: mh_conv_dgrad -- stride 1, or k x k (k > 1) / stride 2 on an even image as four parity-class problems in one launch
-    (3 layers of ResNet-50; round 4).  COL2IM: dgrad GEMM into a per-tap panel + mh_col2im_nhwc (the 3 strided 1x1 downsamples)."""
+    (3 layers of ResNet-50; round 4).  COL2IM: dgrad GEMM into a per-tap panel + mh_col2im_nhwc (the 3 strided 1x1 downsamples).
+    GROUPED: mh_gconv_dgrad, a grouped 3x3 (ResNeXt's conv2) -- a gather per input pixel with no BatchNorm epilogue and no pairing."""
+    if cv.grouped:
+        return GROUPED
     if cv.direct and cv.cout % 64:
         return GEMM
     parity = cv.stride == 2 and cv.kh > 1 and H % 2 == 0 and W % 2 == 0 and opts.strided_dgrad
@@ -114,10 +121,17 @@ class _Conv:
         self.cout, self.cin = mod.out_channels, mod.in_channels
         self.kh, self.kw = mod.kernel_size
         self.stride, self.pad = mod.stride[0], mod.padding[0]
+        self.groups = mod.groups
         self.cp = cin_pad or self.cin                      # channels of the NHWC input (3 -> 8 for the stem)
         k = self.kh * self.kw * self.cp
         self.ldk = (k + 63) // 64 * 64                     # GEMM contraction (multiple of 64)
         self.direct = self.kh == 1 and self.kw == 1 and self.stride == 1 and self.ldk == self.cp
+
+    @property
+    def grouped(self) -> bool:
+        """THE route property: a grouped convolution (ResNeXt's 3x3 conv2) packs with mh_gconv_weight_pack and runs mh_gconv_fwd / dgrad /
+        wgrad; it never enters the dense pack jobs, the deferred weight-gradient queue or dgrad_route's three dense routes."""
+        return self.groups > 1
 
     def out_hw(self, H, W):
         return (H + 2 * self.pad - self.kh) // self.stride + 1, (W + 2 * self.pad - self.kw) // self.stride + 1
@@ -136,6 +150,10 @@ class _Conv:
         y = torch.empty((M, self.cout), dtype=T16, device=x.device)
         part = torch.empty((2, self.cout, (M + 127) // 128), dtype=F32, device=x.device) if want_stats else None
         geom = self.geom(B, H, W)
+        if self.grouped:
+            check(lib.mh_gconv_fwd(x.data_ptr(), wk.data_ptr(), y.data_ptr(), None if part is None else part.data_ptr(), geom, self.groups,
+                                   _stream()), "mh_gconv_fwd")
+            return y, part, Ho, Wo
         sp = int(lib.mh_conv_splitk(geom, 0))          # > 1: a few-tile, long-contraction layer is cut into K chunks (f32 slabs)
         ws = torch.empty((sp, M, self.cout), dtype=F32, device=x.device) if sp > 1 else None
         check(lib.mh_conv_fwd(x.data_ptr(), wk.data_ptr(), y.data_ptr(), None if part is None else part.data_ptr(),
@@ -147,8 +165,24 @@ class _Conv:
         want = max(1, min(64, -(-target // tiles), M // 256))
         return max(1, lib.mh_gemm_ksplit_for(int(M), int(want)))
 
+    def _grouped_backward(self, lib, dy, x, wk, B, H, W, gscale, grads, need_dx, below, pair):
+        """The grouped route: the weight gradient straight into _grad_target (the nn.Conv2d layout, f32: no slabs, no finishing job), the
+        input gradient by mh_gconv_dgrad."""
+        if below is not None or pair is not None:
+            raise _lib.MemehipError(f"the {GROUPED} input gradient has no BatchNorm epilogue and does not pair")
+        geom = self.geom(B, H, W)
+        g, acc = _grad_target(self.mod.weight, grads)
+        ws = torch.empty(int(lib.mh_gconv_wgrad_workspace_elems(geom, self.groups)), dtype=F32, device=dy.device)
+        check(lib.mh_gconv_wgrad(dy.data_ptr(), x.data_ptr(), g.data_ptr(), ws.data_ptr(), int(acc), 1.0 / gscale, geom, self.groups, _stream()),
+              "mh_gconv_wgrad")
+        if not need_dx:
+            return None, None
+        dx = torch.empty((B * H * W, self.cp), dtype=dy.dtype, device=dy.device)
+        check(lib.mh_gconv_dgrad(dy.data_ptr(), wk.data_ptr(), dx.data_ptr(), geom, self.groups, _stream()), "mh_gconv_dgrad")
+        return dx, None
+
     def backward(self, lib, dy, x, wk, B, H, W, Ho, Wo, gscale, wjobs, opts, need_dx=True, wq=None, below=None, addend=None, y_mask=None,
-                 pair=None):
+                 pair=None, grads=None):
         """dy [M, cout] 16-bit -> (dx [B*H*W, cp] 16-bit or None, the statistics partials of `below` or None).  The weight gradient
         (implicit GEMM over x, mh_conv_wgrad) is deferred into `wq` (flush_wgrads) or launched here; its split-K slabs are queued in
         `wjobs` (summed, un-packed and added to .grad for all convolutions at once at the end of the backward).  The input gradient
@@ -157,6 +191,8 @@ class _Conv:
         `pair` (pairs_with): (ds, dy2, wk2) -- the 1x1 / 2 downsample that reads the same x, its dy and packed weight: dx is the sum of both
         input gradients, from one mh_conv_dgrad_pair launch."""
         M, dev = B * Ho * Wo, dy.device
+        if self.grouped:
+            return self._grouped_backward(lib, dy, x, wk, B, H, W, gscale, grads, need_dx, below, pair)
         if wq is not None:
             wq.append((self, dy, x, B, H, W, Ho, Wo))
         else:
@@ -344,16 +380,18 @@ class Tape:
 
 
 class Bottleneck(nn.Module):
-    """torchvision.models.resnet.Bottleneck (v1.5: the stride sits on the 3x3 convolution): parameter holder."""
+    """torchvision.models.resnet.Bottleneck (v1.5: the stride sits on the 3x3 convolution): parameter holder.  ``groups`` / ``base_width``:
+    ResNeXt's grouped conv2 over ``width = int(planes * base_width / 64) * groups`` channels."""
     expansion = 4
 
-    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: bool = False):
+    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: bool = False, groups: int = 1, base_width: int = 64):
         super().__init__()
-        self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
-        self.conv2 = nn.Conv2d(planes, planes, 3, stride=stride, padding=1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
-        self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
+        width = int(planes * base_width / 64) * groups      # torchvision's rule; the defaults give width = planes (ResNet-50)
+        self.conv1 = nn.Conv2d(inplanes, width, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1, groups=groups, bias=False)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.conv3 = nn.Conv2d(width, planes * 4, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * 4)
         self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes * 4, 1, stride=stride, bias=False), nn.BatchNorm2d(planes * 4)) if downsample else None
         self.stride = stride
@@ -482,10 +520,15 @@ class _ConvTower(nn.Module):
     def _pack_all_weights(self, lib, T16):
         """f32 [Cout][Cin][kh][kw] -> 16-bit [Cout][(kh,kw,c)] for every convolution: one buffer, mh_conv_weight_pack_batched
         launches of <= 64 jobs."""
-        convs = [u.conv for u in self._units]
+        convs = [u.conv for u in self._units if not u.conv.grouped]
         total = sum(c.cout * c.ldk for c in convs)
-        buf = torch.empty(total, dtype=T16, device=self._stem_unit.conv.mod.weight.device)
+        dev = self._stem_unit.conv.mod.weight.device
+        buf = torch.empty(total, dtype=T16, device=dev)
         packed, off = {}, 0
+        for c in (u.conv for u in self._units if u.conv.grouped):      # the grouped route's own fragment images
+            wk = torch.empty(int(lib.mh_gconv_packed_elems(c.cout, c.groups)), dtype=T16, device=dev)
+            check(lib.mh_gconv_weight_pack(c.mod.weight.data_ptr(), wk.data_ptr(), c.cout, c.groups, _stream()), "mh_gconv_weight_pack")
+            packed[id(c.mod)] = wk
         for i in range(0, len(convs), _lib.MH_CONV_MAX_JOBS):
             chunk = convs[i:i + _lib.MH_CONV_MAX_JOBS]
             jobs = (_lib.MhConvPackJob * len(chunk))()
@@ -528,7 +571,7 @@ class _ConvTower(nn.Module):
                 below = None
             dxin, part = rec.conv.backward(lib, dz, rec.x, rec.wk, B, rec.H, rec.W, rec.Ho, rec.Wo, self.gscale, wjobs, opts, need_dx,
                                            wq=wq, below=below, addend=addend, y_mask=below.y if block_out else None,
-                                           pair=None if pair is None else (pair[0].conv, pair[1], pair[0].wk))
+                                           pair=None if pair is None else (pair[0].conv, pair[1], pair[0].wk), grads=grads)
             if wq is not None and len(wq) >= group:
                 flush_wgrads(lib, wq, wjobs, self.gscale)
             return dxin, dres, part, dz
@@ -593,6 +636,7 @@ class _ResNet(_ConvTower):
     ``options``: the backward's TowerOptions."""
     block = None
     default_layers = None
+    groups, width_per_group = 1, 64      # (Bottleneck only: ResNeXt)
 
     def __init__(self, num_classes: int = 1000, compute_dtype: str = "fp16", layers=None, width: int = 64,
                  grad_stream_scale: float = 0.0, seed: int = 0, options: TowerOptions = TowerOptions()):
@@ -604,7 +648,12 @@ class _ResNet(_ConvTower):
         self.bn1 = nn.BatchNorm2d(width)
         outs = [width * m * block.expansion for m in (1, 2, 4, 8)]
         stages = list(zip(layers, [width] + outs[:-1], outs, (1, 2, 2, 2)))      # (blocks, in, out, stride); four `layerN` at the most
-        built = stage_blocks(stages, lambda cin, cout, stride, shortcut: block(cin, cout // block.expansion, stride, downsample=shortcut))
+        extra = dict(groups=self.groups, base_width=self.width_per_group) if self.groups > 1 else {}
+        for _, _, cout, _ in stages if extra else ():
+            cg = int(cout // block.expansion * self.width_per_group / 64)
+            if cg not in (4, 8, 16, 32):
+                raise ValueError(f"{type(self).__name__}: width={width} gives grouped convolutions of {cg} channels per group; the kernels have 4, 8, 16 and 32")
+        built = stage_blocks(stages, lambda cin, cout, stride, shortcut: block(cin, cout // block.expansion, stride, downsample=shortcut, **extra))
         for li, blocks in enumerate(built, 1):
             setattr(self, f"layer{li}", nn.Sequential(*blocks))
         inplanes = stages[-1][2]
@@ -635,7 +684,15 @@ class ResNet34(_ResNet):
     block, default_layers = BasicBlock, (3, 4, 6, 3)
 
 
-RESNETS = {"resnet50": ResNet50, "resnet18": ResNet18, "resnet34": ResNet34}
+class ResNeXt50_32x4d(_ResNet):
+    """torchvision ``resnext50_32x4d`` (Kevin's Subtask-2B image zoo, example_scripts/Untitled-2.py:210-237): ResNet-50's tree with every
+    bottleneck's 3x3 a 32-group convolution over 128 / 256 / 512 / 1024 channels (4 / 8 / 16 / 32 per group), 2048-d features;
+    25 028 904 parameters with the 1000-way ``fc``.  The grouped layers run on mh_gconv_* (csrc/groupconv.hip)."""
+    block, default_layers = Bottleneck, (3, 4, 6, 3)
+    groups, width_per_group = 32, 4
+
+
+RESNETS = {"resnet50": ResNet50, "resnet18": ResNet18, "resnet34": ResNet34, "resnext50_32x4d": ResNeXt50_32x4d}
 
 
 # ---- transformers' ResNet (models/resnet/modeling_resnet.py): the same network under transformers' module names ----------------------
@@ -769,7 +826,7 @@ class HFResNetForImageClassification(nn.Module):
 class ResNetClassifier(nn.Module):
     """The ResNet-50 surface of BASELINE config 2 under the Subtask-2B Trainer protocol (ResNet_example_task2B.py:206-221):
     ``model(pixel_values=..., labels=...)`` -> ``(loss, logits)``; without labels ``logits``.  ``arch``: "resnet50" (default) | "resnet18" |
-    "resnet34", torchvision's keys.  The model the 2B example itself builds (a ``ResNetConfig``) is ``HFResNetForImageClassification``."""
+    "resnet34" | "resnext50_32x4d", torchvision's keys.  The model the 2B example itself builds (a ``ResNetConfig``) is ``HFResNetForImageClassification``."""
 
     def __init__(self, num_labels: int = 2, compute_dtype: str = "fp16", arch: str = "resnet50", **kw):
         super().__init__()
