@@ -4,11 +4,19 @@ Part A -- the grouped 3x3 kernels alone (mh_gconv_packed_elems / mh_gconv_weight
   mh_gconv_wgrad_workspace_elems / mh_gconv_wgrad) against ``F.conv2d(..., groups=...)`` and its autograd in float64 on the CPU:
   exact on integer operands (bit for bit, BatchNorm partials included), no leakage between groups, random operands inside the bound of
   an f32 sum taken in any order (2^-p |ref| for the one output rounding + n 2^-24 sum|terms|), a weight gradient that is the same bits
-  on every call, and refusals that write nothing.
+  on every call, and refusals that write nothing.  The small cases give every weight-gradient workgroup ONE unit of 32 pixels; the
+  ``walk_*`` cases give it two or three, as every grouped layer of the benchmarked tower does (batch 32, 224 px: 2 to 13), so the loop's
+  prefetch, its closing barrier and the accumulators carried across units run here with a ragged last chunk -- for every Cg at both
+  strides, all three unit shapes, C = 288 (four bundles and a half, Cg = 32 included), an odd x even stride-2 image and several forward /
+  dgrad tiles.  The regime is read from the library (workspace / (C Cg 9) = chunks, against the unit count of every unit shape), not
+  restated; a guard walks the real tower and asserts that every (Cg, stride, walks) it launches is among the cases; and a batch split
+  in two accumulating launches (other chunk boundaries) must give the bits of the one launch.
 Part B -- ``ResNeXt50_32x4d(layers=(1, 1, 1, 1))`` forward + backward against the float64 composition of
   tests/test_basic_resnet_gpu.py part B extended to bottlenecks with groups: the same 16-bit storage points (straight-through), the
   same bars.  Then gradient accumulation, the classifier under the fused Adam, Kevin's three-tower model and ``ResNeXt50_32x4d_BH``
   (with mh_l2norm_fwd / mh_l2norm_bwd alone) over the new tower."""
+import importlib.util
+import os
 from functools import lru_cache
 
 import numpy as np
@@ -33,11 +41,33 @@ CASES = {
     "cg16_s2": (2, 3, 3, 32, 2, 2),            # Cg = 16
     "cg32_two_tiles": (3, 9, 9, 64, 2, 1),     # Cg = 32, 243 rows: a second, partial 128-row tile for bn_part
     "layer1_s2": (2, 8, 8, 128, 32, 2),        # the first ResNeXt layer's own grouping
-    # beyond the issue's list: one wide row, where the weight gradient takes its 1 x 32 unit shape (every case above takes 2 x 16 or 4 x 8)
+    # beyond the issue's list: one wide row, where the weight gradient takes its 1 x 32 unit shape (every case above takes 2 x 16 or 4 x 8);
+    # every case down to here: one unit per workgroup
     "wide_s1": (1, 1, 40, 32, 8, 1),
     "wide_s2": (1, 2, 80, 32, 8, 2),
+    # The walk: more units than workgroups asked for (512 / bundles), so a workgroup loops over `per` >= 2 units and the last chunk is
+    # ragged -- the only way the benchmarked tower runs this kernel.  unit, per, chunks (units): what the plan gives today; the test pins
+    # only chunks < units of every unit shape (test_gconv_cases_pin_their_walk_regime).
+    #                                                  Cg, stride   unit   per  chunks (units)   further edge
+    "walk_cg4_s1": (7, 17, 17, 288, 72, 1),          #  4, 1        4 x 8   2   53 (105)   C = 288: four bundles + half a bundle; 16 forward tiles
+    "walk_cg8_s2": (7, 17, 66, 288, 36, 2),          #  8, 2        4 x 8   2   53 (105)   odd x even image; 62 dgrad tiles
+    "walk_cg16_s1": (7, 5, 66, 288, 18, 1),          # 16, 1        2 x 16  2   53 (105)   2 x 16 with the Cg <= 16 body
+    "walk_cg32_s2": (7, 9, 130, 288, 9, 2),          # 32, 2        2 x 16  2   53 (105)   <true, 2>, <9, *> at stride 2, half a bundle with Cg = 32
+    "walk_cg32_s1": (7, 17, 17, 288, 9, 1),          # 32, 1        4 x 8   2   53 (105)   loads issued at the top of each unit (the Cg = 32 route)
+    "walk_row_cg4_s1": (3, 1, 733, 512, 128, 1),     #  4, 1        1 x 32  2   35 (69)    a one-row image, ragged last segment
+    "walk_row_cg32_s2": (3, 1, 660, 1024, 32, 2),    # 32, 2        1 x 32  2   17 (33)    the 195-pixel halo, the largest one
+    "walk_three": (10, 13, 16, 1024, 256, 1),        #  4, 1        2 x 16  3   24 (70)    three units per workgroup, the last chunk one
+    # the two (Cg, stride) pairs of the real tower (layer2's later blocks, layer3's first) that the eight above leave out:
+    # test_gconv_cases_cover_what_the_benchmarked_tower_launches asks for them
+    "walk_cg8_s1": (7, 17, 17, 288, 36, 1),          #  8, 1        4 x 8   2   53 (105)
+    "walk_cg16_s2": (7, 9, 130, 288, 18, 2),         # 16, 2        2 x 16  2   53 (105)   2 x 16 at stride 2 with the Cg <= 16 body (7 halo chunks prefetched)
+    # the one stride-2 image parity left (odd x odd, even x even and odd x even are above): even x odd, one unit per workgroup
+    "cg8_even_odd_s2": (2, 6, 9, 64, 8, 2),
 }
+OLD_CASES = [c for c in CASES if not c.startswith("walk_")]
+WALK_CASES = [c for c in CASES if c.startswith("walk_")]
 CASE = pytest.mark.parametrize("case", list(CASES))
+UNIT_SHAPES = ((4, 8), (2, 16), (1, 32))          # rows x columns of the 32 output pixels of a weight-gradient unit
 
 
 @pytest.fixture(scope="module")
@@ -83,11 +113,14 @@ def _conv_refs(x, w, dy, groups, stride):
 
 
 class _Run:
-    """the device side of one case: operands (float64 tensors holding 16-bit values) -> the four launches"""
+    """the device side of one case: operands (float64 tensors holding 16-bit values) -> the four launches; the batch is x's (the case's, or a
+    part of it)"""
 
     def __init__(self, pkg, T16, case, x, w, dy):
         self.pkg, self.lib, self.T16 = pkg, _lib(pkg, T16), T16
-        self.B, self.H, self.W, self.C, self.groups, self.stride = CASES[case]
+        _, self.H, self.W, self.C, self.groups, self.stride = CASES[case]
+        self.B = x.shape[0]
+        assert x.shape[1:] == (self.C, self.H, self.W) and dy.shape[0] == self.B
         self.Ho, self.Wo = _out(self.H, self.W, self.stride)
         self.M, self.Mi = self.B * self.Ho * self.Wo, self.B * self.H * self.W
         self.geom = _geom(pkg, self.B, self.H, self.W, self.C, self.stride)
@@ -154,12 +187,97 @@ def _bits(t):
     return t.contiguous().view(torch.int16)
 
 
+def _chunks(pkg, lib, B, H, W, C, groups, stride):
+    """the weight gradient's workgroups per 64-channel bundle, from the host-only workspace query: one [C][Cg][9] f32 partial each"""
+    n = int(lib.mh_gconv_wgrad_workspace_elems(_geom(pkg, B, H, W, C, stride), groups))
+    assert n > 0 and n % (C * (C // groups) * 9) == 0
+    return n // (C * (C // groups) * 9)
+
+
+def _unit_counts(B, H, W, stride):
+    """how many units of 32 output pixels the batch has under each unit shape"""
+    Ho, Wo = _out(H, W, stride)
+    return [B * -(-Ho // rt) * -(-Wo // wt) for rt, wt in UNIT_SHAPES]
+
+
+def _walks(pkg, lib, B, H, W, C, groups, stride):
+    """fewer workgroups than units under EVERY unit shape: whichever shape the plan chose, some workgroup loops over two units or more"""
+    return _chunks(pkg, lib, B, H, W, C, groups, stride) < min(_unit_counts(B, H, W, stride))
+
+
+@CASE
+def test_gconv_cases_pin_their_walk_regime(pkg, case):
+    """No launch: the plan is host code.  The small cases are the one-unit regime (as many workgroups as units of some shape), every
+    walk_* case has fewer workgroups than units of any shape, walk_three fewer than half as many."""
+    B, H, W, C, groups, stride = CASES[case]
+    assert B * H * W * C <= 2_500_000
+    for T16 in (F16, BF16):
+        chunks, units = _chunks(pkg, _lib(pkg, T16), *CASES[case]), _unit_counts(B, H, W, stride)
+        if case in OLD_CASES:
+            assert chunks in units, f"{chunks} workgroups, units per shape {units}: no longer one unit per workgroup"
+        else:
+            assert chunks < min(units), f"{chunks} workgroups, units per shape {units}: no workgroup has to walk"
+        if case == "walk_three":
+            assert 2 * chunks < min(units), f"{chunks} workgroups, units per shape {units}: no workgroup walks three units"
+
+
+def _tower_grouped_launches(pkg, batch, size):
+    """(B, H, W, C, groups, stride) of every grouped convolution of ResNeXt-50 32x4d on `size` x `size` images, walked as
+    _ConvTower._forward_tape walks (stem, max pool, each block's chain) -- on the host, no launch"""
+    net = pkg.ResNeXt50_32x4d(num_classes=2, compute_dtype="fp16")
+    h, w = net._stem_unit.conv.out_hw(size, size)
+    h, w = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
+    out = []
+    for blk in net._block_units:
+        hh, ww = h, w
+        for u in blk.chain:
+            if u.conv.grouped:
+                assert u.conv.cin == u.conv.cout
+                out.append((batch, hh, ww, u.conv.cout, u.conv.groups, u.conv.stride))
+            hh, ww = u.conv.out_hw(hh, ww)
+        h, w = hh, ww
+    return out
+
+
+def _load_tool(name):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+BENCH_BATCH, BENCH_SIZE = 32, 224          # tools/resnext_bench.py's --batch / --image-size defaults: the measured ResNeXt step
+
+
+def test_gconv_cases_cover_what_the_benchmarked_tower_launches(pkg):
+    """No launch.  Every (Cg, stride, walks?) among the grouped layers of the real tower at the benchmark's batch and size occurs among
+    CASES: a change of the workgroup cap or of the unit rule that moves production into a regime no exact test runs fails here (as does
+    dropping the cases).  The layers come from the tower itself; tools/resnext_bench.py's table must be the same set."""
+    lib = _lib(pkg, F16)
+    launches = _tower_grouped_launches(pkg, BENCH_BATCH, BENCH_SIZE)
+    assert len(launches) == 16          # one per bottleneck: 3 + 4 + 6 + 3
+    shapes = set(launches)                # the distinct geometries: the stride-1 and the stride-2 block of each layer
+    bench = _load_tool("resnext_bench")
+    assert bench.GROUPS == 32 and sorted((C, HW, st) for _, C, HW, st in bench.LAYERS) == sorted((C, H, st) for _, H, _, C, _, st in shapes)
+    assert len(shapes) == 7 and all(g == 32 for *_, g, _ in shapes)          # (layer1's two kinds of block are one geometry: no stride there)
+    have = set()
+    for c, (B, H, W, C, g, st) in CASES.items():
+        walks = _walks(pkg, lib, B, H, W, C, g, st)
+        assert walks == (c in WALK_CASES), f"{c}: walks = {walks}, against its name (test_gconv_cases_pin_their_walk_regime)"
+        have.add((C // g, st, walks))
+    want = {(C // g, st, _walks(pkg, lib, B, H, W, C, g, st)): (B, H, W, C, g, st) for B, H, W, C, g, st in shapes}
+    missing = {k: v for k, v in want.items() if k not in have}
+    assert not missing, f"(Cg, stride, walks) of the benchmarked tower that no case of CASES runs: {missing}"
+
+
 @DTYPES
 @CASE
 def test_gconv_is_exact_on_integers(pkg, case, T16):
     """|x| <= 4, |w| <= 2, |dy| <= 3: every product and every partial sum is an integer below 2^24 (forward / dgrad: <= 9 * 32 * 8; wgrad:
-    <= 243 * 12), exact in f32 in any order -- y and dx are the float64 result rounded once, dw is the float64 result, bn_part the sums of the
-    stored values (integers; the test asserts their y^2 sums stay below 2^24 too)."""
+    <= 12 M, M <= 2275 output pixels), exact in f32 in any order -- y and dx are the float64 result rounded once, dw is the float64 result,
+    bn_part the sums of the stored values per 128-row tile and column (integers; the test asserts their y^2 sums stay below 2^24 too).
+    In the walk_* cases dw is the sum over the two or three units each workgroup walked: an accumulator reset per unit, a unit staged from
+    the wrong registers or read while the next one is being written changes integers."""
     x, w, dy, y_ref, dx_ref, dw_ref = _integer_operands(case)
     r = _Run(pkg, T16, case, x, w, dy)
     y, part = r.fwd()
@@ -180,25 +298,34 @@ def test_gconv_is_exact_on_integers(pkg, case, T16):
     assert torch.equal(dw.to(F64), dw_ref), f"wgrad: {int((dw.to(F64) != dw_ref).sum())} of {dw.numel()} elements differ"
 
 
+# the live groups of a case, beyond the rule's one (group 2, or the last of fewer than four): walk_cg4_s1 -- group 70 = channels 280..283,
+# inside the half-empty last bundle (256..287), beside group 2 in a full one; walk_cg32_s2 -- group 8 = channels 256..287, that half bundle
+LEAK_GROUPS = {"walk_cg4_s1": (70,), "walk_cg32_s2": (8,)}
+
+
 @DTYPES
-@pytest.mark.parametrize("case", ["cg4_odd", "cg8_odd_s2", "cg16_s2", "cg32_two_tiles", "layer1_s2"])
+@pytest.mark.parametrize("case", ["cg4_odd", "cg8_odd_s2", "cg16_s2", "cg32_two_tiles", "layer1_s2", "walk_cg16_s1", "walk_cg32_s2", "walk_cg4_s1"])
 def test_gconv_does_not_leak_between_groups(pkg, case, T16):
     B, H, W, C, groups, stride = CASES[case]
     Ho, Wo = _out(H, W, stride)
-    cg, grp = C // groups, groups - 1 if groups < 4 else 2
-    g = torch.Generator().manual_seed(41)
-    w = torch.randint(1, 3, (C, cg, 3, 3), generator=g).to(F64)          # no zero weight: a leak cannot hide
-    x, dy = torch.zeros((B, C, H, W), dtype=F64), torch.zeros((B, C, Ho, Wo), dtype=F64)
-    x[:, grp * cg:(grp + 1) * cg] = torch.randint(1, 5, (B, cg, H, W), generator=g).to(F64)
-    dy[:, grp * cg:(grp + 1) * cg] = torch.randint(1, 4, (B, cg, Ho, Wo), generator=g).to(F64)
-    r = _Run(pkg, T16, case, x, w, dy)
-    y, _ = r.fwd()
-    dx = r.dgrad()
-    inside = torch.zeros(C, dtype=torch.bool)
-    inside[grp * cg:(grp + 1) * cg] = True
-    assert bool((y[:, ~inside] == 0).all()), "y is nonzero outside the one group that has input"
-    assert bool((dx[:, ~inside] == 0).all()), "dx is nonzero outside the one group that has a gradient"
-    assert bool((y[:, inside] > 0).all()) and bool((dx[:, inside] > 0).all())
+    cg = C // groups
+    for grp in (groups - 1 if groups < 4 else 2,) + LEAK_GROUPS.get(case, ()):
+        g = torch.Generator().manual_seed(41)
+        w = torch.randint(1, 3, (C, cg, 3, 3), generator=g).to(F64)          # no zero weight: a leak cannot hide
+        x, dy = torch.zeros((B, C, H, W), dtype=F64), torch.zeros((B, C, Ho, Wo), dtype=F64)
+        x[:, grp * cg:(grp + 1) * cg] = torch.randint(1, 5, (B, cg, H, W), generator=g).to(F64)
+        dy[:, grp * cg:(grp + 1) * cg] = torch.randint(1, 4, (B, cg, Ho, Wo), generator=g).to(F64)
+        r = _Run(pkg, T16, case, x, w, dy)
+        y, _ = r.fwd()
+        dx = r.dgrad()
+        inside = torch.zeros(C, dtype=torch.bool)
+        inside[grp * cg:(grp + 1) * cg] = True
+        assert bool((y[:, ~inside] == 0).all()), f"group {grp}: y is nonzero outside the one group that has input"
+        assert bool((dx[:, ~inside] == 0).all()), f"group {grp}: dx is nonzero outside the one group that has a gradient"
+        assert bool((y[:, inside] > 0).all()) and bool((dx[:, inside] > 0).all()), f"group {grp}"
+        dw = r.wgrad()                                                        # (H, W >= 3 in these cases: every tap meets a pixel)
+        assert bool((dw[~inside] == 0).all()), f"group {grp}: dw is nonzero in filters whose outputs have no gradient"
+        assert bool((dw[inside] > 0).all()), f"group {grp}"
 
 
 @lru_cache(maxsize=None)
@@ -234,7 +361,7 @@ def test_gconv_random_operands_within_the_f32_sum_bound(pkg, case, T16):
 
 
 @DTYPES
-@pytest.mark.parametrize("case", ["cg8_odd_s2", "cg32_two_tiles", "layer1_s2"])
+@pytest.mark.parametrize("case", ["cg8_odd_s2", "cg32_two_tiles", "layer1_s2", "walk_cg8_s2", "walk_cg32_s1", "walk_three"])
 def test_gconv_wgrad_is_deterministic_and_accumulates(pkg, case, T16):
     (x, w, dy), (_, _, dw_ref), _ = _random_operands(case, T16)
     r = _Run(pkg, T16, case, x, w, dy)
@@ -256,6 +383,29 @@ def test_gconv_wgrad_is_deterministic_and_accumulates(pkg, case, T16):
     assert bool(((acc.to(F64) - want).abs() <= 2.0 ** -24 * want.abs() + 1e-45).all())
     half = r.wgrad(ws=ws, alpha=0.5)               # alpha scales the sum (a power of two: exactly)
     assert torch.equal(half, first * 0.5)
+
+
+@DTYPES
+@pytest.mark.parametrize("case", ["walk_cg8_s2", "walk_cg32_s2"])
+def test_gconv_wgrad_walk_equals_a_split_batch(pkg, case, T16):
+    """Integer operands, so every sum is exact whatever its order: the weight gradient of the 7 images in one launch, and that of images
+    [0, 3) followed by that of [3, 7) with accumulate = 1 -- other unit counts, so other chunk boundaries (today the parts are small enough
+    for one unit per workgroup: the walked sum against the unwalked one) -- are the same bits, those of the float64 reference."""
+    x, w, dy, _, _, dw_ref = _integer_operands(case)
+    B, H, W, C, groups, stride = CASES[case]
+    assert B == 7
+    whole = _Run(pkg, T16, case, x, w, dy)
+    a, b = _Run(pkg, T16, case, x[:3], w, dy[:3]), _Run(pkg, T16, case, x[3:], w, dy[3:])
+    lib = _lib(pkg, T16)
+    assert _walks(pkg, lib, 7, H, W, C, groups, stride)
+    assert _chunks(pkg, lib, 7, H, W, C, groups, stride) != _chunks(pkg, lib, 3, H, W, C, groups, stride) + _chunks(pkg, lib, 4, H, W, C, groups, stride)
+    dw_whole = whole.wgrad()
+    dw = torch.full((dw_ref.numel() + 64,), 12345.0, dtype=F32, device="cuda")
+    first = a.wgrad(dw=dw)
+    both = b.wgrad(dw=dw, accumulate=1)
+    assert not torch.equal(first, both)
+    assert torch.equal(dw_whole.view(torch.int32), both.view(torch.int32)), f"{int((dw_whole != both).sum())} of {both.numel()} elements differ"
+    assert torch.equal(both.to(F64), dw_ref)
 
 
 @DTYPES
@@ -323,31 +473,67 @@ def test_gconv_refusals_write_nothing(pkg, T16):
     assert bool((y[:M] == 0).all()) and bool((y[M:] == 7.0).all())
 
 
-@pytest.mark.parametrize("shape", [(4, 2048), (1, 8)], ids=["4x2048", "1x8"])
-def test_l2norm_against_float64(pkg, shape):
-    """mh_l2norm_fwd / mh_l2norm_bwd: y = x / ||x||, dx = (g - y (y . g)) / ||x||.  Bars from the f32 sums of D terms: the norm (and the dot
-    product) within D 2^-24 relative (of sum|terms|), so an element within (D + 4) 2^-24 of its own size plus the dot product's share."""
+def _l2norm_launch(pkg, x, g):
+    """mh_l2norm_fwd + mh_l2norm_bwd over f32 [B, D] -> (y, norm, dx) on the CPU, nothing written past the outputs"""
     lib = pkg._lib.load()
-    B, D = shape
-    gen = torch.Generator().manual_seed(17 + D)
-    x, g = torch.randn(shape, generator=gen), torch.randn(shape, generator=gen)
+    B, D = x.shape
     xd, gd = x.cuda(), g.cuda()
-    y, norm, dx = torch.full((B, D), 7.0, device="cuda"), torch.full((B,), 7.0, device="cuda"), torch.full((B, D), 7.0, device="cuda")
+    y, norm, dx = torch.full((B * D + 64,), 7.0, device="cuda"), torch.full((B + 64,), 7.0, device="cuda"), torch.full((B * D + 64,), 7.0, device="cuda")
     pkg._lib.check(lib.mh_l2norm_fwd(xd.data_ptr(), y.data_ptr(), norm.data_ptr(), B, D, _st()), "mh_l2norm_fwd")
     pkg._lib.check(lib.mh_l2norm_bwd(gd.data_ptr(), y.data_ptr(), norm.data_ptr(), dx.data_ptr(), B, D, _st()), "mh_l2norm_bwd")
     torch.cuda.synchronize()
+    assert bool((y[B * D:] == 7.0).all()) and bool((norm[B:] == 7.0).all()) and bool((dx[B * D:] == 7.0).all()), "mh_l2norm wrote past its outputs"
+    assert lib.mh_l2norm_fwd(None, y.data_ptr(), norm.data_ptr(), B, D, _st()) == MH_EINVAL
+    assert lib.mh_l2norm_bwd(gd.data_ptr(), y.data_ptr(), norm.data_ptr(), dx.data_ptr(), 0, D, _st()) == MH_ESHAPE
+    return y[:B * D].view(B, D).cpu(), norm[:B].cpu(), dx[:B * D].view(B, D).cpu()
+
+
+def _l2norm_misses(x, g, y, norm, dx, rows):
+    """the bars of test_l2norm_against_float64 over `rows`: what misses them"""
+    D = x.shape[1]
     x64 = x.to(F64).requires_grad_(True)
     y_ref = x64 / x64.norm(dim=1, keepdim=True)
     y_ref.backward(g.to(F64))
     u = 2.0 ** -24
     n_ref = x64.detach().norm(dim=1)
-    assert bool(((norm.cpu().to(F64) - n_ref).abs() <= (D + 2) * u * n_ref).all())
-    assert bool(((y.cpu().to(F64) - y_ref.detach()).abs() <= (D + 4) * u * y_ref.detach().abs()).all())
     yh, g64 = y_ref.detach(), g.to(F64)
     terms = (g64.abs() + yh.abs() * (yh.abs() * g64.abs()).sum(1, keepdim=True)) / n_ref[:, None]
-    assert bool(((dx.cpu().to(F64) - x64.grad).abs() <= 4 * (D + 6) * u * terms).all())          # (y enters twice, each with its own (D + 4) u; the dot product; the division)
-    assert lib.mh_l2norm_fwd(None, y.data_ptr(), norm.data_ptr(), B, D, _st()) == MH_EINVAL
-    assert lib.mh_l2norm_bwd(gd.data_ptr(), y.data_ptr(), norm.data_ptr(), dx.data_ptr(), 0, D, _st()) == MH_ESHAPE
+    out = []
+    if not bool(((norm.to(F64) - n_ref).abs() <= (D + 2) * u * n_ref)[rows].all()):
+        out.append("norm")
+    if not bool(((y.to(F64) - yh).abs() <= (D + 4) * u * yh.abs())[rows].all()):
+        out.append("y")
+    if not bool(((dx.to(F64) - x64.grad).abs() <= 4 * (D + 6) * u * terms)[rows].all()):          # (y enters twice, each with its own (D + 4) u; the dot product; the division)
+        out.append("dx")
+    return out, yh
+
+
+@pytest.mark.parametrize("shape", [(4, 2048), (1, 8), (3, 1), (3, 63), (3, 64), (3, 65), (3, 2049)],
+                         ids=["4x2048", "1x8", "3x1", "3x63", "3x64", "3x65", "3x2049"])
+def test_l2norm_against_float64(pkg, shape):
+    """mh_l2norm_fwd / mh_l2norm_bwd: y = x / ||x||, dx = (g - y (y . g)) / ||x||.  Bars from the f32 sums of D terms: the norm (and the dot
+    product) within D 2^-24 relative (of sum|terms|), so an element within (D + 4) 2^-24 of its own size plus the dot product's share.
+    D = 1, 63, 64, 65, 2049: a wave's 64-lane stride loop with idle lanes, exactly one trip, and one element into the next trip."""
+    B, D = shape
+    gen = torch.Generator().manual_seed(17 + D)
+    x, g = torch.randn(shape, generator=gen), torch.randn(shape, generator=gen)
+    y, norm, dx = _l2norm_launch(pkg, x, g)
+    misses, _ = _l2norm_misses(x, g, y, norm, dx, torch.arange(B))
+    assert not misses, misses
+
+
+def test_l2norm_of_a_zero_row_is_nan_in_that_row_only(pkg):
+    """No eps, as in the reference: a zero row is 0 / 0 = NaN, exactly what x / x.norm() gives in float64, its norm exactly 0; the rows
+    around it stay inside their bars (a NaN does not cross rows)."""
+    B, D = 3, 65
+    gen = torch.Generator().manual_seed(23)
+    x, g = torch.randn((B, D), generator=gen), torch.randn((B, D), generator=gen)
+    x[1] = 0.0
+    y, norm, dx = _l2norm_launch(pkg, x, g)
+    misses, y_ref = _l2norm_misses(x, g, y, norm, dx, torch.tensor([0, 2]))
+    assert not misses, misses
+    assert bool(torch.isnan(y_ref[1]).all()) and bool(torch.isnan(y[1]).all())
+    assert float(norm[1]) == 0.0 and bool(torch.isfinite(y[[0, 2]]).all()) and bool(torch.isfinite(dx[[0, 2]]).all())
 
 
 # ---------------------------------------------------------------------------------------------------------------------
