@@ -798,6 +798,33 @@ int mh_gconv_wgrad(const void* dy, const void* x, float* dw, float* workspace, i
                    mh_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Squeeze-and-excitation (se.hip): timm's SEModule between a bottleneck's bn3 and its residual add (seresnext50_32x4d, the first
+ * model of example_scripts/Untitled-2.py:362-371).  u = bn3(conv3(.)) [B*HW][C] 16-bit NHWC (no ReLU, no residual);
+ *   pooled = mean_hw u (mh_avgpool_fwd);  hidden = relu(w1 pooled + b1);  s = sigmoid(w2 hidden + b2);  y = relu(u * s + shortcut).
+ * w1 [R][C], b1 [R], w2 [C][R], b2 [C]: the nn.Conv2d(C, R, 1) / nn.Conv2d(R, C, 1) parameters; everything indexed [B][C] or [B][R] is f32.
+ * One shape rule: C % 8 == 0, 8 <= C <= 4096, 1 <= R <= 256, HW >= 1 with HW * C / 8 < 2^31, B >= 1 -- B is a grid dimension: x (2^31 - 1)
+ * for the two gate entry points, y (65535) for the three over the activation; anything else: MH_ESHAPE.  A NULL pointer, or a 16-bit tensor / s / dpooled not on a 16-byte boundary: MH_EINVAL.  In both cases nothing is
+ * written.  No atomics: every sum has one owner and an order fixed by the shape, so two calls give the same bits.
+ *   mh_se_gate_fwd:   hidden (stored after the ReLU) and s = 1 / (1 + expf(-a)) with the accurate expf: a saturated gate is exactly 0
+ *                     (a < ~-88.7) or 1 (a > ~16.7), never NaN.  Two launches: a wave per (image, hidden unit), a thread per (image, channel).
+ *   mh_se_apply_fwd:  y = relu(u * s[b] + shortcut), f32, rounded once to 16 bits.
+ *   mh_se_apply_bwd_reduce: g = dy where y > 0 (dy's bits) else +0 -- the gradient of the shortcut branch --, and ds[b][c] = sum_hw g * u
+ *                     in f32.  One workgroup owns 64 columns of an image over all of HW (rows ascending per thread, then a fixed tree).
+ *   mh_se_gate_bwd:   back through the sigmoid, fc2, the ReLU (mask hidden > 0) and fc1: dpooled [B][C] keeps ds's scale (the gradient
+ *                     stream's); dw1 [R][C], db1 [R], dw2 [C][R], db2 [C] = (accumulate ? target : 0) + alpha * the sum over the batch
+ *                     (b ascending; alpha * sum is rounded to f32 before the add), in the nn.Conv2d layouts -- they can BE f32 .grads.
+ *   mh_se_apply_bwd:  du = g * s[b] + dpooled[b] / HW (a true division), f32, rounded once to 16 bits.
+ * ------------------------------------------------------------------------------------------ */
+int mh_se_gate_fwd(const float* pooled, const float* w1, const float* b1, const float* w2, const float* b2, float* hidden, float* s, int B,
+                   int C, int R, mh_stream_t stream);
+int mh_se_apply_fwd(const void* u, const float* s, const void* shortcut, void* y, int B, int HW, int C, mh_stream_t stream);
+int mh_se_apply_bwd_reduce(const void* dy, const void* y, const void* u, void* g, float* ds, int B, int HW, int C, mh_stream_t stream);
+int mh_se_gate_bwd(const float* ds, const float* s, const float* hidden, const float* pooled, const float* w1, const float* w2,
+                   float* dpooled, float* dw1, float* db1, float* dw2, float* db2, int B, int C, int R, float alpha, int accumulate,
+                   mh_stream_t stream);
+int mh_se_apply_bwd(const void* g, const float* s, const float* dpooled, void* du, int B, int HW, int C, mh_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer (torch.optim.Adam / AdamW, Multimodal_example_task2C.txt:249,217; HF Trainer
  * adamw_torch + max_grad_norm, DistilBERT_example_task2A.ipynb:3211-3213,3280):
  *   mh_sumsq_f32: out[0] = sum g^2 over n elements (two-pass deterministic; workspace >= 1024 f32)

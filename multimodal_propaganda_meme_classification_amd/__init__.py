@@ -10,14 +10,15 @@ from .model import (Adam, BatchNorm1d, BCEWithLogitsLoss, CrossEntropyLoss, Grad
                     SigmoidFocalLoss, TextEncoder, balanced_class_weights, flatten_parameters, get_linear_schedule_with_warmup)
 from . import fused  # noqa: F401
 from .heads import (MCA3, ConcatAttention3, FineTuneMLP, KevinMultimodalClassifier, LinearBNReLU,  # noqa: F401
-                    OrganizersMultimodalClassifier, ResNeXt50_32x4d_BH, SequencePooling, TextClassifier, TrainerModel)
+                    OrganizersMultimodalClassifier, ResNeXt50_32x4d_BH, SEResNeXt50_32x4d_BH, SequencePooling, TextClassifier,
+                    TrainerModel)
 from .data import HashTokenizer, MultimodalDataset, id2l, l2id, normalize_images, read_data  # noqa: F401
 from .train import evaluate, test, train  # noqa: F401
 from . import kevin  # noqa: F401
 from .kevin import BlipImageCaptioning, KevinMultimodalDataset, blip_caption_fn, kevin_collate  # noqa: F401
 from .blip import BlipCaptioner  # noqa: F401
 from .resnet import (BasicBlock, Bottleneck, HFResNetForImageClassification, ResNet18, ResNet34, ResNet50, ResNetClassifier,  # noqa: F401
-                     ResNeXt50_32x4d, TowerOptions)
+                     ResNeXt50_32x4d, SEModule, SEResNeXt50_32x4d, TowerOptions)
 from .convnext import CNBlock, ConvNeXtTiny  # noqa: F401
 from .features import dump_features, get_features  # noqa: F401
 from . import svm  # noqa: F401

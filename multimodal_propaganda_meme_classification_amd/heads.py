@@ -296,7 +296,8 @@ class KevinMultimodalClassifier(_Composite):
     timm's ``reset_classifier(0)`` leaves) under ``FineTuneMLP(512, proj)``, the text tower a ``TextEncoder`` of its own
     (``text_model``), as in ``OrganizersMultimodalClassifier``; ``towers`` is then None.  ``resnet_layers`` / ``resnet_width``: the
     tower's ``layers=`` / ``width=`` overrides (tests).  ``image="resnext50_32x4d"`` (Kevin's Subtask-2B zoo, example_scripts/Untitled-2.py:210-237):
-    the same branch over ``resnet.ResNeXt50_32x4d`` -- 2048 features under ``FineTuneMLP(2048, proj)``.
+    the same branch over ``resnet.ResNeXt50_32x4d`` -- 2048 features under ``FineTuneMLP(2048, proj)``; ``image="seresnext50_32x4d"`` (:182-207):
+    ``resnet.SEResNeXt50_32x4d``, the same with a squeeze-and-excitation gate in every block.
 
     ``image="convnext_tiny"``: the organizers' own image backbone (baselines/extract_feat.py) under the submitted model's head --
     ``timm.create_model(image_model)`` takes any backbone name, and ``FineTuneMLP`` is sized from the tower here.  The image tower is
@@ -322,8 +323,9 @@ class KevinMultimodalClassifier(_Composite):
         self.fusion_method = fusion_method
         if isinstance(image, str):
             from .resnet import RESNETS
-            if image not in ("resnet18", "resnet34", "resnext50_32x4d", "convnext_tiny"):
-                raise ValueError(f"image must be an ImageConfig, 'resnext50_32x4d', 'resnet18' or 'resnet34', or 'convnext_tiny', got {image!r}")
+            if image not in ("resnet18", "resnet34", "resnext50_32x4d", "seresnext50_32x4d", "convnext_tiny"):
+                raise ValueError("image must be an ImageConfig, 'resnext50_32x4d', 'seresnext50_32x4d', 'resnet18' or 'resnet34', or 'convnext_tiny', "
+                                 f"got {image!r}")
             self.towers = None
             self.text_model = TextEncoder(tc, pool="cls", compute_dtype=compute_dtype, seed=seed, grad_stream_scale=grad_stream_scale)
             if image == "convnext_tiny":
@@ -520,6 +522,30 @@ class ResNeXt50_32x4d_BH(nn.Module):
         self.binary_head = BinaryHead(2, emb_size=self.net.feature_dim, s=1)
         self.dropout = nn.Dropout(p=0.2)
         self.fc = nn.Linear(in_features=self.net.feature_dim, out_features=2)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.binary_head(self.fea_bn(self.net.features(x)))
+
+
+class SEResNeXt50_32x4d_BH(nn.Module):
+    """``SEResNeXt50_32x4d_BH`` of Kevin's Subtask-2B image zoo (example_scripts/Untitled-2.py:182-207): the SE-ResNeXt-50 32x4d features
+    (``net``: ``resnet.SEResNeXt50_32x4d(num_classes=0)`` under the tower's own keys -- torchvision's plus timm's ``se.fc1 / se.fc2``; the
+    reference's ``nn.Sequential`` indices are not mapped) -> ``fea_bn = BatchNorm1d(2048)`` with a frozen bias -> ``binary_head`` (L2-normalised
+    features, ``Linear(2048, 2)``, times ``s = 1``) -> logits [B, 2].  The unused ``dropout`` is kept as a member; the reference has no ``fc`` here,
+    and its ``avg_pool`` (no state) is the tower's own global average pool."""
+    name = "SEResNeXt50_32x4d_BH"
+
+    def __init__(self, compute_dtype: str = "fp16", seed: int = 0, **tower_kw):
+        super().__init__()
+        from .model import BatchNorm1d
+        from .resnet import SEResNeXt50_32x4d
+        self.model_arch = "seresnext50_32x4d"
+        self.net = SEResNeXt50_32x4d(num_classes=0, compute_dtype=compute_dtype, seed=seed, **tower_kw)
+        torch.manual_seed(seed + 1)
+        self.fea_bn = BatchNorm1d(self.net.feature_dim)
+        self.fea_bn.bias.requires_grad_(False)
+        self.binary_head = BinaryHead(2, emb_size=self.net.feature_dim, s=1)
+        self.dropout = nn.Dropout(p=0.2)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.binary_head(self.fea_bn(self.net.features(x)))

@@ -21,6 +21,11 @@ submodules only HOLD the parameters and running statistics; the arithmetic runs 
   bottleneck's grouped 3x3 (``_Conv.grouped``) packs with ``mh_gconv_weight_pack`` and runs ``mh_gconv_fwd`` (BatchNorm partials in its
   epilogue too) / ``mh_gconv_dgrad`` / ``mh_gconv_wgrad`` (straight into the f32 ``.grad``); ``dgrad_route`` names that route ``GROUPED``, so
   it takes no BatchNorm epilogue and no pairing by the existing rules;
+* ``SEResNeXt50_32x4d`` (timm ``seresnext50_32x4d``, the zoo's first entry: example_scripts/Untitled-2.py:182-207) adds a squeeze-and-excitation
+  gate (``SEModule``) between every bottleneck's bn3 and the residual add.  An SE block takes the plain routes around five small kernels
+  (csrc/se.hip): bn3 stores ``u`` with no residual and no ReLU, then ``mh_avgpool_fwd`` / ``mh_se_gate_fwd`` / ``mh_se_apply_fwd``; backward
+  ``mh_se_apply_bwd_reduce`` / ``mh_se_gate_bwd`` / ``mh_se_apply_bwd`` and the ordinary unmasked ``mh_bn2d_bwd``.  The conv1 ABOVE an SE
+  block never takes the block-out epilogue (``epilogue_takes_bn(..., below_se=True)``): no BatchNorm sits directly under that ReLU;
 * the 16-bit gradient stream carries ``grad_stream_scale`` (8192 for fp16), removed where parameter gradients are produced.
 
 ``_ConvTower`` holds that machinery -- ONE forward and ONE backward walk over (conv, BatchNorm) units; a family (``_ResNet``: torchvision's
@@ -82,10 +87,13 @@ def pairs_with(cv, ds, H, W, opts: TowerOptions) -> bool:
             and cv.stride == 2 and cv.kh > 1 and dgrad_route(cv, H, W, opts) == IMPLICIT and cv.out_hw(H, W) == (H // 2, W // 2))
 
 
-def epilogue_takes_bn(cv, H, W, opts: TowerOptions, block_out: bool = False) -> bool:
+def epilogue_takes_bn(cv, H, W, opts: TowerOptions, block_out: bool = False, below_se: bool = False) -> bool:
     """Whether cv's dgrad epilogue does the backward masking + statistics of the BatchNorm (+ReLU) that produced cv's input (only
-    the implicit route has that epilogue); `block_out`: cv is a block's conv1, the BatchNorm the bn3 + residual of the block below."""
-    return opts.bn_bwd_fuse and (opts.block_out_fuse or not block_out) and dgrad_route(cv, H, W, opts) == IMPLICIT
+    the implicit route has that epilogue); `block_out`: cv is a block's conv1, the BatchNorm the bn3 + residual of the block below.
+    `below_se`: that block is a squeeze-and-excitation block -- its output is relu(u * s + shortcut), so the ReLU's mask and the statistics
+    do not belong to a BatchNorm directly under it and the gate needs the FULL gradient of the output: never the block_out form."""
+    return (opts.bn_bwd_fuse and (opts.block_out_fuse or not block_out) and not (block_out and below_se)
+            and dgrad_route(cv, H, W, opts) == IMPLICIT)
 
 
 def _stream():
@@ -100,6 +108,18 @@ def _grad_target(p: nn.Parameter, grads: dict):
     g = g if acc else torch.empty_like(p)
     grads[id(p)] = None if acc else g
     return g, acc
+
+
+def _grad_targets(params, grads: dict):
+    """_grad_target for parameters that ONE launch writes with one accumulate flag: (targets, accumulate) -- in place only when every one of
+    them has a usable .grad, else fresh tensors for all."""
+    out = [_grad_target(p, grads) for p in params]
+    if len({acc for _, acc in out}) == 1:
+        return [g for g, _ in out], out[0][1]
+    fresh = [torch.empty_like(p) for p in params]
+    for p, g in zip(params, fresh):
+        grads[id(p)] = g
+    return fresh, False
 
 
 def _bn_epilogue(below, part, addend=None, y_mask=None):
@@ -343,13 +363,26 @@ class ConvBnRec:
 
 
 @dataclass
+class SERec:
+    """A block's squeeze-and-excitation gate: `mod` alone is the parameter holder (_ConvTower._block_units); every field: what one forward left
+    on the tape.  out = relu(u * s + shortcut) with u the y of the chain's last record (bn3: no residual, no ReLU)."""
+    mod: "SEModule"
+    pooled: torch.Tensor = None    # [B, C] f32, mean_hw u
+    hidden: torch.Tensor = None    # [B, R] f32, after the ReLU
+    s: torch.Tensor = None         # [B, C] f32, the gate
+    out: torch.Tensor = None       # [B*Ho*Wo, C] 16-bit, the block's output
+
+
+@dataclass
 class BlockRec:
     """One residual block's layers (bottleneck: conv1-3; basic block: conv1-2) + downsample: _ResNet._block_units, and on the tape their
-    records of one forward.  `chain`: the main branch in order; its last unit takes the residual and the block's ReLU."""
+    records of one forward.  `chain`: the main branch in order; its last unit takes the residual and the block's ReLU -- unless the block
+    has a squeeze-and-excitation gate (`se`): then the last unit stores bn3 alone and the gate's `out` is the block's output."""
     conv1: ConvBnRec
     conv2: ConvBnRec
     conv3: Optional[ConvBnRec] = None
     downsample: Optional[ConvBnRec] = None
+    se: Optional[SERec] = None
 
     @property
     def chain(self) -> List[ConvBnRec]:
@@ -379,12 +412,30 @@ class Tape:
     dtype: torch.dtype
 
 
+def se_reduced_channels(channels: int) -> int:
+    """timm's ``make_divisible(channels / 16, 8, round_limit=0.)``, the hidden width of a ResNet block's SEModule: 16 / 32 / 64 / 128 for
+    256 / 512 / 1024 / 2048 channels"""
+    return max(8, int(channels / 16 + 4) // 8 * 8)
+
+
+class SEModule(nn.Module):
+    """timm.layers.SEModule (``fc1``: Conv2d(C, R, 1) -> ReLU -> ``fc2``: Conv2d(R, C, 1) -> sigmoid, both with bias; its ``bn`` / ``act`` /
+    ``gate`` members hold no state): parameter holder, the arithmetic is mh_se_*."""
+
+    def __init__(self, channels: int, rd_channels: int):
+        super().__init__()
+        self.fc1 = nn.Conv2d(channels, rd_channels, 1, bias=True)
+        self.fc2 = nn.Conv2d(rd_channels, channels, 1, bias=True)
+
+
 class Bottleneck(nn.Module):
     """torchvision.models.resnet.Bottleneck (v1.5: the stride sits on the 3x3 convolution): parameter holder.  ``groups`` / ``base_width``:
-    ResNeXt's grouped conv2 over ``width = int(planes * base_width / 64) * groups`` channels."""
+    ResNeXt's grouped conv2 over ``width = int(planes * base_width / 64) * groups`` channels.  ``se``: timm's ``attn_layer='se'`` -- a member
+    ``se`` (SEModule) between bn3 and the residual add; without it the module has no such member."""
     expansion = 4
 
-    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: bool = False, groups: int = 1, base_width: int = 64):
+    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: bool = False, groups: int = 1, base_width: int = 64,
+                 se: bool = False):
         super().__init__()
         width = int(planes * base_width / 64) * groups      # torchvision's rule; the defaults give width = planes (ResNet-50)
         self.conv1 = nn.Conv2d(inplanes, width, 1, bias=False)
@@ -393,6 +444,8 @@ class Bottleneck(nn.Module):
         self.bn2 = nn.BatchNorm2d(width)
         self.conv3 = nn.Conv2d(width, planes * 4, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * 4)
+        if se:
+            self.se = SEModule(planes * 4, se_reduced_channels(planes * 4))
         self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes * 4, 1, stride=stride, bias=False), nn.BatchNorm2d(planes * 4)) if downsample else None
         self.stride = stride
 
@@ -467,7 +520,9 @@ class _ConvTower(nn.Module):
         for b in blocks:
             chain, shortcut = b.conv_bn_pairs()
             c = [unit(*cb) for cb in chain]
-            self._block_units.append(BlockRec(c[0], c[1], c[2] if len(c) > 2 else None, None if shortcut is None else unit(*shortcut)))
+            se = getattr(b, "se", None)
+            self._block_units.append(BlockRec(c[0], c[1], c[2] if len(c) > 2 else None, None if shortcut is None else unit(*shortcut),
+                                              None if se is None else SERec(se)))
         self._units = [self._stem_unit] + [u for b in self._block_units for u in b.units]
         self.feature_dim = self._block_units[-1].chain[-1].conv.cout
 
@@ -504,14 +559,45 @@ class _ConvTower(nn.Module):
                 recs.append(conv_bn(v, y, hh, ww))
                 y, hh, ww = recs[-1].y, recs[-1].Ho, recs[-1].Wo
             ds = None if u.downsample is None else conv_bn(u.downsample, x, h, w, relu=False)
-            recs.append(conv_bn(last, y, hh, ww, residual=x if ds is None else ds.y, relu=True))
-            blocks.append(BlockRec(*recs, downsample=ds))
-            x, h, w = recs[-1].y, recs[-1].Ho, recs[-1].Wo
+            shortcut, se = (x if ds is None else ds.y), None
+            if u.se is None:
+                recs.append(conv_bn(last, y, hh, ww, residual=shortcut, relu=True))
+            else:      # squeeze-and-excitation: bn3 alone, then the gate and out = relu(u * s + shortcut)
+                recs.append(conv_bn(last, y, hh, ww, residual=None, relu=False))
+                se = self._se_forward(lib, u.se.mod, recs[-1], shortcut, B)
+            blocks.append(BlockRec(*recs, downsample=ds, se=se))
+            x, h, w = (recs[-1].y if se is None else se.out), recs[-1].Ho, recs[-1].Wo
         pooled = torch.empty((B, self.feature_dim), dtype=F32, device=image.device)
         check(lib.mh_avgpool_fwd(x.data_ptr(), pooled.data_ptr(), B, h * w, self.feature_dim, _stream()), "mh_avgpool_fwd")
         if training:      # nn.BatchNorm2d's step counter, all of them (53 in ResNet-50) in one multi-tensor launch
             torch._foreach_add_([u.bn.mod.num_batches_tracked for u in self._units], 1)
         return Tape(B, stem, PoolRec(arg, stem.Ho, stem.Wo, C1), blocks, pooled, (h, w), T16)
+
+    @staticmethod
+    def _se_forward(lib, mod, rec: ConvBnRec, shortcut: torch.Tensor, B: int) -> SERec:
+        """The gate of one SE block over u = rec.y [B*HW, C]: squeeze (the global average pool), excite, scale + shortcut + ReLU."""
+        u, HW, C, R = rec.y, rec.Ho * rec.Wo, mod.fc1.in_channels, mod.fc1.out_channels
+        pooled, s = torch.empty((B, C), dtype=F32, device=u.device), torch.empty((B, C), dtype=F32, device=u.device)
+        hidden, out = torch.empty((B, R), dtype=F32, device=u.device), torch.empty_like(u)
+        check(lib.mh_avgpool_fwd(u.data_ptr(), pooled.data_ptr(), B, HW, C, _stream()), "mh_avgpool_fwd")
+        check(lib.mh_se_gate_fwd(pooled.data_ptr(), mod.fc1.weight.data_ptr(), mod.fc1.bias.data_ptr(), mod.fc2.weight.data_ptr(),
+                                 mod.fc2.bias.data_ptr(), hidden.data_ptr(), s.data_ptr(), B, C, R, _stream()), "mh_se_gate_fwd")
+        check(lib.mh_se_apply_fwd(u.data_ptr(), s.data_ptr(), shortcut.data_ptr(), out.data_ptr(), B, HW, C, _stream()), "mh_se_apply_fwd")
+        return SERec(mod, pooled, hidden, s, out)
+
+    def _se_backward(self, lib, se: SERec, rec: ConvBnRec, dy: torch.Tensor, B: int, grads: dict):
+        """dy: the FULL gradient of an SE block's output -> (du, the gradient of u = rec.y; g, the gradient of the shortcut branch)."""
+        mod, HW, (_, C), R = se.mod, rec.Ho * rec.Wo, se.s.shape, se.hidden.shape[1]
+        g, du = torch.empty_like(dy), torch.empty_like(dy)
+        ds, dpooled = torch.empty_like(se.s), torch.empty_like(se.s)
+        check(lib.mh_se_apply_bwd_reduce(dy.data_ptr(), se.out.data_ptr(), rec.y.data_ptr(), g.data_ptr(), ds.data_ptr(), B, HW, C, _stream()),
+              "mh_se_apply_bwd_reduce")
+        (dw1, db1, dw2, db2), acc = _grad_targets([mod.fc1.weight, mod.fc1.bias, mod.fc2.weight, mod.fc2.bias], grads)
+        check(lib.mh_se_gate_bwd(ds.data_ptr(), se.s.data_ptr(), se.hidden.data_ptr(), se.pooled.data_ptr(), mod.fc1.weight.data_ptr(),
+                                 mod.fc2.weight.data_ptr(), dpooled.data_ptr(), dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(),
+                                 B, C, R, 1.0 / self.gscale, int(acc), _stream()), "mh_se_gate_bwd")
+        check(lib.mh_se_apply_bwd(g.data_ptr(), se.s.data_ptr(), dpooled.data_ptr(), du.data_ptr(), B, HW, C, _stream()), "mh_se_apply_bwd")
+        return du, g
 
     def _convs(self):
         """(conv module, input channels of its NHWC activation) in a fixed order"""
@@ -583,7 +669,11 @@ class _ConvTower(nn.Module):
             # every unit's dgrad epilogue already does the masking + statistics of the BatchNorm below it in the chain
             *body, last = blk.chain
             c1, ds = blk.conv1, blk.downsample
-            d_o, d_ident, part, _ = conv_bn_bwd(last, dx, want_dres=True, below=body[-1], pre_part=dx_part)
+            if blk.se is None:
+                d_o, d_ident, part, _ = conv_bn_bwd(last, dx, want_dres=True, below=body[-1], pre_part=dx_part)
+            else:      # the gate first (dx is the full gradient of the block's output: see below_se), then bn3 with no mask and no residual
+                du, d_ident = self._se_backward(lib, blk.se, last, dx, B, grads)
+                d_o, _, part, _ = conv_bn_bwd(last, du, below=body[-1])
             # a basic block's 3x3 / 2 conv1 next to the 1x1 / 2 downsample: both read the block input -- the downsample leaves only its dz here,
             # its input gradient is a second K segment of conv1's dgrad (mh_conv_dgrad_pair)
             pair = None
@@ -593,7 +683,7 @@ class _ConvTower(nn.Module):
                 pair = (ds, dz_ds) if paired else None
             for j in range(len(body) - 1, 0, -1):
                 d_o, _, part, _ = conv_bn_bwd(body[j], d_o, below=body[j - 1], pre_part=part)
-            if below is not None and epilogue_takes_bn(c1.conv, c1.H, c1.W, opts, block_out=True):
+            if below is not None and epilogue_takes_bn(c1.conv, c1.H, c1.W, opts, block_out=True, below_se=below.se is not None):
                 # conv1's input is the output y = relu(bn(z) + residual) of the block below: its dgrad epilogue adds the gradient arriving
                 # through the other branch (d_ident; paired: already in the accumulators), masks by y > 0 and takes that BatchNorm's statistics
                 # -- no mh_add_h16 pass, no statistics pass (round 4)
@@ -637,6 +727,7 @@ class _ResNet(_ConvTower):
     block = None
     default_layers = None
     groups, width_per_group = 1, 64      # (Bottleneck only: ResNeXt)
+    se = False                           # (Bottleneck only: a squeeze-and-excitation gate in every block)
 
     def __init__(self, num_classes: int = 1000, compute_dtype: str = "fp16", layers=None, width: int = 64,
                  grad_stream_scale: float = 0.0, seed: int = 0, options: TowerOptions = TowerOptions()):
@@ -649,11 +740,12 @@ class _ResNet(_ConvTower):
         outs = [width * m * block.expansion for m in (1, 2, 4, 8)]
         stages = list(zip(layers, [width] + outs[:-1], outs, (1, 2, 2, 2)))      # (blocks, in, out, stride); four `layerN` at the most
         extra = dict(groups=self.groups, base_width=self.width_per_group) if self.groups > 1 else {}
+        se_kw = dict(se=True) if self.se else {}
         for _, _, cout, _ in stages if extra else ():
             cg = int(cout // block.expansion * self.width_per_group / 64)
             if cg not in (4, 8, 16, 32):
                 raise ValueError(f"{type(self).__name__}: width={width} gives grouped convolutions of {cg} channels per group; the kernels have 4, 8, 16 and 32")
-        built = stage_blocks(stages, lambda cin, cout, stride, shortcut: block(cin, cout // block.expansion, stride, downsample=shortcut, **extra))
+        built = stage_blocks(stages, lambda cin, cout, stride, shortcut: block(cin, cout // block.expansion, stride, downsample=shortcut, **extra, **se_kw))
         for li, blocks in enumerate(built, 1):
             setattr(self, f"layer{li}", nn.Sequential(*blocks))
         inplanes = stages[-1][2]
@@ -692,7 +784,17 @@ class ResNeXt50_32x4d(_ResNet):
     groups, width_per_group = 32, 4
 
 
-RESNETS = {"resnet50": ResNet50, "resnet18": ResNet18, "resnet34": ResNet34, "resnext50_32x4d": ResNeXt50_32x4d}
+class SEResNeXt50_32x4d(_ResNet):
+    """timm ``seresnext50_32x4d`` (the first model of Kevin's Subtask-2B image zoo, example_scripts/Untitled-2.py:182-207): ``ResNeXt50_32x4d``
+    with a squeeze-and-excitation gate (``layerN.i.se.fc1 / fc2``, hidden width 16 / 32 / 64 / 128) in every bottleneck; 27 559 896 parameters
+    with the 1000-way ``fc``.  Every other key is torchvision's, as for the ResNeXt tower.  The gates run on mh_se_* (csrc/se.hip)."""
+    block, default_layers = Bottleneck, (3, 4, 6, 3)
+    groups, width_per_group = 32, 4
+    se = True
+
+
+RESNETS = {"resnet50": ResNet50, "resnet18": ResNet18, "resnet34": ResNet34, "resnext50_32x4d": ResNeXt50_32x4d,
+           "seresnext50_32x4d": SEResNeXt50_32x4d}
 
 
 # ---- transformers' ResNet (models/resnet/modeling_resnet.py): the same network under transformers' module names ----------------------
@@ -826,7 +928,7 @@ class HFResNetForImageClassification(nn.Module):
 class ResNetClassifier(nn.Module):
     """The ResNet-50 surface of BASELINE config 2 under the Subtask-2B Trainer protocol (ResNet_example_task2B.py:206-221):
     ``model(pixel_values=..., labels=...)`` -> ``(loss, logits)``; without labels ``logits``.  ``arch``: "resnet50" (default) | "resnet18" |
-    "resnet34" | "resnext50_32x4d", torchvision's keys.  The model the 2B example itself builds (a ``ResNetConfig``) is ``HFResNetForImageClassification``."""
+    "resnet34" | "resnext50_32x4d" | "seresnext50_32x4d", torchvision's keys (+ timm's ``se.*``).  The model the 2B example itself builds (a ``ResNetConfig``) is ``HFResNetForImageClassification``."""
 
     def __init__(self, num_labels: int = 2, compute_dtype: str = "fp16", arch: str = "resnet50", **kw):
         super().__init__()
