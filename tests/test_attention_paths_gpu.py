@@ -30,8 +30,26 @@ sequences of 200 and 300 rows; an empty mask row still keeps its pooled position
 a hand-built plan gives sequences of zero rows (Sb == 0).  Adversarial values (sharp, monotonically rising scores, a V with
 a large common offset) push the lazy running maximum and the delta = rowsum(dO o O) cancellation.
 
-Tolerances are today's of tests/test_kernels_gpu.py::test_attention_fwd_bwd (out 1e-2 / 6e-3, lse 1e-3 / 2e-3, dqkv
-2e-2 / 1.5e-2 * max |dqkv|); measured errors go through conftest.parity_log.
+Every row of the table is held to three things (tests/attention_restatement.py holds the case generator, the bound and its
+derivation; tests/test_attention_bounds.py validates both without a GPU):
+
+  old bars      those of tests/test_kernels_gpu.py::test_attention_fwd_bwd (out 1e-2 / 6e-3, lse 1e-3 / 2e-3, dqkv 2e-2 / 1.5e-2 *
+                max |dqkv|), unchanged.  They let through a few percent of error on a subset of elements.
+  derived bound out, lse, dQ, dK and dV each against their own per-element first-order bound, computed in float64 from the
+                reference's intermediates (one term per rounding of the kernels, doubled once): every random and adversarial test
+                below.  The worst error / bound per tensor goes through conftest.parity_log.
+  exact case    tied scores (every query's best score shared by 1, 2 or 4 keys, every other key >= 128 below): out, dQ, dK, dV
+                must equal the float64 reference bit for bit in fp16 and in bf16 (torch.equal), lse stays on the bound.  The
+                test_exact_* twins of every row: the dense table plus S = 577 under the same onepass modes, dropout at p = 0.5
+                (multiplier exactly 2), the packed masks and zero-length plans, every grouped pair in both orders under onepass
+                2 / 1 / 0 with the S_a = 240 refusal, and two wide-head geometries (B = 2, H = 12, S = 197 and B = 1, H = 16,
+                S = 577: the row pitches of BERT-base and ViT-L).  Rounding points that keep it exact, read in attn_fwd_body,
+                attn_bwd_dq_body, attn_bwd_dkv_body and attn_bwd_onepass_body (the dual and merged kernels call these bodies):
+                tied keys see identical arithmetic, so exp2(st - m) = 1 and the others exp2(<= -184) = 0; a lazy-maximum move
+                rescales by alpha = 0 exactly; l and the PV sums are small integers, 1 / l a power of two; the backward's
+                p = exp2(s c - lse log2(e)) is 1/n to ~2^-16, and p o M and p (dP - delta) are rounded to the 16-bit operand
+                (acc_frag, the one-pass mailbox), whose true values are representable; delta is summed from an exact stored O.
+                No path needed the 1-ulp fallback.
 """
 import contextlib
 import math
@@ -40,6 +58,7 @@ import numpy as np
 import pytest
 import torch
 
+import attention_restatement as R
 from conftest import parity_log
 
 pytestmark = pytest.mark.gpu
@@ -48,6 +67,7 @@ F32, F64 = torch.float32, torch.float64
 DTYPES = pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
 TOL = dict(out=(1e-2, 6e-3), lse=(1e-3, 2e-3), dqkv=(2e-2, 1.5e-2))
 P_DROP = 0.1
+P_TIED = 0.5            # the exact case's dropout: mh_drop_ctx's scale 1.0f / (1.0f - p) is exactly 2
 
 
 @pytest.fixture(scope="module")
@@ -58,24 +78,21 @@ def ops():
     return _ops
 
 
-def _randn(shape, seed, scale=1.0):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    return torch.randn(shape, generator=g, device="cuda") * scale
-
-
 def _rng_words(seed):
     return torch.tensor([seed & 0x7FFFFFFF, 0, 3, 0], dtype=torch.int32, device="cuda")
 
 
 def _prefix_mask(B, S, lens):
-    return (torch.arange(S)[None] < torch.tensor(lens)[:, None]).to(torch.int64).cuda()
+    return torch.from_numpy(R.prefix_mask(S, lens)).cuda()
 
 
 def _drop_probs(ops, B, H, S, drop):
     """the kernels' dropout multipliers of the probabilities, [B, H, S(query), S(key)] by unpacked position"""
     if drop is None:
         return None
-    return ops.dropout_mask(B * H * S * S, drop, "cuda").to(F64).cpu().view(B, H, S, S) / (1.0 - drop[1])
+    keep = ops.dropout_mask(B * H * S * S, drop, "cuda")
+    assert bool((keep <= 1).all()), "dropout_mask returns something other than 0 and 1"
+    return keep.to(F64).cpu().view(B, H, S, S) / (1.0 - drop[1])
 
 
 @contextlib.contextmanager
@@ -88,27 +105,19 @@ def _onepass(ops, t, mode):
         lib.mh_attn_set_onepass(2)
 
 
-def _reference(qkv, mask, dout, B, S, H, pm=None):
-    """float64 out [B*S, H*64], lse [B, H, S], dqkv [B*S, 3*H*64] from the 16-bit inputs (dense positions)."""
-    x = qkv.detach().cpu().to(F64).requires_grad_(True)
-    q, k, v = x.view(B, S, 3, H, 64).permute(2, 0, 3, 1, 4)
-    sc = q @ k.transpose(-1, -2) / 8.0
-    dead = torch.zeros(B, dtype=torch.bool)
-    if mask is not None:
-        m = mask.detach().cpu().to(F64).view(B, S)
-        sc = sc + (1.0 - m)[:, None, None, :] * torch.finfo(torch.float32).min
-        dead = m.sum(1) == 0
-    p = torch.softmax(sc, -1)
-    lse = torch.logsumexp(sc, -1)
-    if pm is not None:
-        p = p * pm
-    o = (p @ v).permute(0, 2, 1, 3).reshape(B * S, H * 64)
-    d = dout.detach().cpu().to(F64)
-    rows = dead.repeat_interleave(S)[:, None]
-    o = o.masked_fill(rows, 0.0)                          # no key to attend to: out = 0, lse = -inf, no gradient
-    lse = lse.masked_fill(dead[:, None, None], -math.inf)
-    o.backward(d.masked_fill(rows, 0.0))
-    return o.detach(), lse.detach(), x.grad
+def _reference(qkv, mask, dout, B, S, H, pm=None, exact=False):
+    """float64 out [B*S, H*64], lse [B, H, S], dqkv [B*S, 3*H*64] from the 16-bit inputs (dense positions), and the derived bound
+    of each in the same layout (R.bounds); exact: the tied case, whose reference the kernels must reproduce bit for bit."""
+    r = R.reference(qkv, dout, B, S, H, mask, pm, flush=exact)
+    if exact:
+        for n in ("O", "dQ", "dK", "dV"):
+            assert R.representable(getattr(r, n).contiguous(), qkv.dtype), f"tied case: {n} is not exact in {qkv.dtype}"
+        z = torch.zeros_like(r.O)
+        bd = dict(R.bounds(r, qkv.dtype, lse_only=True), out=z, dQ=z, dK=z, dV=z)
+    else:
+        bd = R.bounds(r, qkv.dtype)
+    return dict(out=R.rows(r.O), lse=r.lse, dqkv=R.rows3(r.dQ, r.dK, r.dV), b_out=R.rows(bd["out"]), b_lse=bd["lse"],
+                b_dqkv=R.rows3(bd["dQ"], bd["dK"], bd["dV"]), exact=exact, dtype=qkv.dtype)
 
 
 def _check(what, got, want, kind, scale=None):
@@ -132,65 +141,102 @@ def _check(what, got, want, kind, scale=None):
 
 
 def _check_all(tag, out, lse, dqkv, ref, H):
-    """out / lse / dqkv against the reference; dQ, dK, dV reported separately, tolerance scaled by max |dqkv| as today"""
-    r_out, r_lse, r_dqkv = ref
-    e_out = _check(f"{tag} out", out, r_out, "out")
-    e_lse = _check(f"{tag} lse", lse, r_lse, "lse")
-    scale = max(float(r_dqkv.abs().max()), 1e-30)
-    g = dqkv.detach().cpu().to(F64).view(-1, 3, H * 64)
-    w = r_dqkv.view(-1, 3, H * 64)
+    """the exact case: out / dQ / dK / dV bit for bit, lse on its bound.  Every other case: the old bars (dQ, dK, dV reported
+    separately, tolerance scaled by max |dqkv| as before), then each tensor against its own derived bound."""
+    g = dqkv.detach().cpu().view(-1, 3, H * 64)
+    w = ref["dqkv"].view(-1, 3, H * 64)
+    bw = ref["b_dqkv"].view(-1, 3, H * 64)
+    if ref["exact"]:
+        dt = ref["dtype"]
+        for n, got, want in [("out", out.detach().cpu(), ref["out"])] + [(f"d{n}", g[:, i], w[:, i]) for i, n in enumerate("QKV")]:
+            if not torch.equal(got, want.to(dt)):
+                diff = got.to(F64) != want
+                raise AssertionError(f"{tag} {n}: {int(diff.sum())}/{diff.numel()} elements differ from the exact result, "
+                                     f"max |diff| {float((got.to(F64) - want).abs().max()):.4g}")
+        r_lse = R.ratio(lse, ref["lse"], ref["b_lse"])
+        parity_log(f"[attention {tag}] out dQ dK dV bit-exact; lse error / bound {r_lse:.3f}")
+        assert r_lse <= 1.0, f"{tag} lse: {r_lse:.3f} of the derived bound"
+        return
+    e_out = _check(f"{tag} out", out, ref["out"], "out")
+    e_lse = _check(f"{tag} lse", lse, ref["lse"], "lse")
+    scale = max(float(ref["dqkv"].abs().max()), 1e-30)
     e = [_check(f"{tag} d{n}", g[:, i], w[:, i], "dqkv", scale) for i, n in enumerate("QKV")]
     parity_log(f"[attention {tag}] max err out {e_out:.3e} lse {e_lse:.3e} dQ {e[0]:.3e} dK {e[1]:.3e} dV {e[2]:.3e} "
                f"(max |dqkv| {scale:.3e})")
+    rt = dict(out=R.ratio(out, ref["out"], ref["b_out"]), lse=R.ratio(lse, ref["lse"], ref["b_lse"]))
+    for i, n in enumerate("QKV"):
+        rt[f"d{n}"] = R.ratio(g[:, i], w[:, i], bw[:, i])
+    parity_log(f"[attention bound {tag}] worst error / bound " + " ".join(f"{n} {v:.3f}" for n, v in rt.items()))
+    for n, v in rt.items():
+        assert v <= 1.0, f"{tag} {n}: {v:.3f} of the derived bound"
 
 
-def _dense_inputs(B, S, H, dtype, seed):
-    qkv = _randn((B * S, 3 * H * 64), seed).to(dtype)
-    dout = _randn((B * S, H * 64), seed + 1).to(dtype)
-    return qkv, dout
+def _inputs(data, B, S, H, dtype, seed, mask=None):
+    """'random': N(0, 1) rounded to dtype; 'tied': the exact case over the keys `mask` keeps"""
+    if data == "tied":
+        m = None if mask is None else mask.detach().cpu().numpy()
+        qkv, dout = R.tied_case(B, S, H, m, R.tied_seed(B, S, H))
+        return qkv.to(dtype).cuda(), dout.to(dtype).cuda()
+    return R.dense_inputs(B, S, H, dtype, seed, "cuda")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # 1. dense dispatch table
 # ---------------------------------------------------------------------------------------------------------------------
 
-S_TABLE = [1, 31, 32, 33, 64, 65, 127, 128, 129, 160, 197, 223, 224, 225, 255, 256, 257, 300]
+S_TABLE = R.S_TABLE
+_lens = R.lens
+NAME = {"random": "", "tied": "exact "}
 
 
-def _lens(S):
-    return [S, max(1, S - 1), max(1, (S + 1) // 2)]          # full, last key masked, half
+def _dense_case(ops, B, S, H, dtype, masked, data, seed, p_drop=None, rng=None, site=21):
+    mask = _prefix_mask(B, S, _lens(S)) if masked else None
+    qkv, dout = _inputs(data, B, S, H, dtype, seed, mask)
+    drop = (_rng_words(S if rng is None else rng), p_drop, site) if p_drop else None
+    ref = _reference(qkv, mask, dout, B, S, H, _drop_probs(ops, B, H, S, drop), exact=data == "tied")
+    out, lse = ops.attn_fwd(qkv, mask, B, S, H, drop=drop)
+    modes = (2, 0) if (129 <= S <= 224 and not masked and not drop) else (2,)
+    for mode in modes:
+        with _onepass(ops, qkv, mode):
+            dqkv = ops.attn_bwd(qkv, mask, out, dout, lse, B, S, H, drop=drop)
+            torch.cuda.synchronize()
+        tag = f"{NAME[data]}dense{' dropout' if drop else ''} B={B} H={H} S={S} {'masked' if masked else 'unmasked'} {dtype}"
+        _check_all(tag + ("" if drop else f" onepass={mode}"), out, lse, dqkv, ref, H)
 
 
 @DTYPES
 @pytest.mark.parametrize("masked", [False, True], ids=["unmasked", "masked"])
 @pytest.mark.parametrize("S", S_TABLE)
 def test_dense_dispatch_table(ops, S, masked, dtype):
-    B, H = 3, 2
-    qkv, dout = _dense_inputs(B, S, H, dtype, seed=S)
-    mask = _prefix_mask(B, S, _lens(S)) if masked else None
-    ref = _reference(qkv, mask, dout, B, S, H)
-    out, lse = ops.attn_fwd(qkv, mask, B, S, H)
-    modes = (2, 0) if (129 <= S <= 224 and not masked) else (2,)
-    for mode in modes:
-        with _onepass(ops, qkv, mode):
-            dqkv = ops.attn_bwd(qkv, mask, out, dout, lse, B, S, H)
-            torch.cuda.synchronize()
-        _check_all(f"dense S={S} {'masked' if masked else 'unmasked'} {dtype} onepass={mode}", out, lse, dqkv, ref, H)
+    _dense_case(ops, 3, S, 2, dtype, masked, "random", seed=S)
 
 
 @DTYPES
 @pytest.mark.parametrize("masked", [False, True], ids=["unmasked", "masked"])
-@pytest.mark.parametrize("S", [33, 128, 160, 224, 256, 257])
+@pytest.mark.parametrize("S", S_TABLE + [577])
+def test_exact_dense(ops, S, masked, dtype):
+    _dense_case(ops, 3, S, 2, dtype, masked, "tied", seed=None)
+
+
+@DTYPES
+@pytest.mark.parametrize("masked", [False, True], ids=["unmasked", "masked"])
+@pytest.mark.parametrize("S", R.S_DROPOUT)
 def test_dense_dropout(ops, S, masked, dtype):
-    B, H = 3, 2
-    qkv, dout = _dense_inputs(B, S, H, dtype, seed=S + 500)
-    mask = _prefix_mask(B, S, _lens(S)) if masked else None
-    drop = (_rng_words(S), P_DROP, 21)
-    ref = _reference(qkv, mask, dout, B, S, H, _drop_probs(ops, B, H, S, drop))
-    out, lse = ops.attn_fwd(qkv, mask, B, S, H, drop=drop)
-    dqkv = ops.attn_bwd(qkv, mask, out, dout, lse, B, S, H, drop=drop)
-    torch.cuda.synchronize()
-    _check_all(f"dense dropout S={S} {'masked' if masked else 'unmasked'} {dtype}", out, lse, dqkv, ref, H)
+    _dense_case(ops, 3, S, 2, dtype, masked, "random", seed=S + 500, p_drop=P_DROP)
+
+
+@DTYPES
+@pytest.mark.parametrize("masked", [False, True], ids=["unmasked", "masked"])
+@pytest.mark.parametrize("S", R.S_DROPOUT)
+def test_exact_dense_dropout(ops, S, masked, dtype):
+    _dense_case(ops, 3, S, 2, dtype, masked, "tied", seed=None, p_drop=P_TIED)
+
+
+@DTYPES
+@pytest.mark.parametrize("B,H,S", [(2, 12, 197), (1, 16, 577)], ids=["bert-base-pitch", "vit-l-pitch"])
+def test_exact_wide_heads(ops, B, H, S, dtype):
+    """row pitches 3 * 768 and 3 * 1024 elements instead of the 384 / 576 of H = 2 / 3 everywhere else in this module"""
+    _dense_case(ops, B, S, H, dtype, False, "tied", seed=None)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -198,30 +244,9 @@ def test_dense_dropout(ops, S, masked, dtype):
 # ---------------------------------------------------------------------------------------------------------------------
 
 def _packed_mask(case):
-    """[B, S] int64 masks; empty rows are all zeros"""
-    if case == "edges":                      # empty first / middle / last, one token, the 32 / 64 boundaries
-        S, lens = 80, [0, 1, 31, 0, 32, 33, 64, 65, 0]
-        m = np.arange(S)[None] < np.array(lens)[:, None]
-    elif case == "holes":
-        S = 96
-        g = np.random.default_rng(7)
-        m = g.random((5, S)) < 0.5
-        m[0, 0] = m[2, 0] = True
-        m[1, 0] = False                      # the pooled row (position 0) is kept as a query but is no key
-        m[3] = False                         # empty
-        m[4, 40:] = False
-    elif case == "s200":
-        S, lens = 200, [200, 0, 129, 161]
-        m = np.arange(S)[None] < np.array(lens)[:, None]
-    elif case == "s300":
-        S = 300
-        g = np.random.default_rng(9)
-        m = np.arange(S)[None] < np.array([300, 1, 0, 257])[:, None]
-        m[0] &= g.random(S) < 0.7
-        m[0, 0] = True
-    else:
-        raise ValueError(case)
-    return torch.from_numpy(m.astype(np.int64)).cuda()
+    """[B, S] int64 masks; empty rows are all zeros (R.packed_mask: empty first / middle / last, one token, the 32 / 64
+    boundaries, holes, sequences of 200 and 300 rows)"""
+    return torch.from_numpy(R.packed_mask(case)).cuda()
 
 
 def _check_packed(tag, ops, plan, out_p, lse_p, dqkv_p, ref, B, S, H):
@@ -229,48 +254,55 @@ def _check_packed(tag, ops, plan, out_p, lse_p, dqkv_p, ref, B, S, H):
     n = int(plan["n_rows"])
     rm = plan["row_map"][:n].long().cpu()
     cu = plan["cu"].long().cpu()
-    r_out, r_lse, r_dqkv = ref
     b = rm // S
     pos = rm % S
     local = torch.arange(n) - cu[b]
     lse_c = lse_p.detach().cpu().view(B, H, S)
     got_lse = lse_c[b, :, local]                              # [n, H]
-    want_lse = r_lse[b, :, pos]
-    _check_all(tag, out_p[:n], got_lse, dqkv_p[:n], (r_out[rm], want_lse, r_dqkv[rm]), H)
+    sub = dict(ref, out=ref["out"][rm], lse=ref["lse"][b, :, pos], dqkv=ref["dqkv"][rm], b_out=ref["b_out"][rm],
+               b_lse=ref["b_lse"][b, :, pos], b_dqkv=ref["b_dqkv"][rm])
+    _check_all(tag, out_p[:n], got_lse, dqkv_p[:n], sub, H)
     if n < out_p.shape[0]:
         assert float(out_p[n:].float().abs().max()) == 0.0, f"{tag}: out rows past n_rows written"
         assert float(dqkv_p[n:].float().abs().max()) == 0.0, f"{tag}: dqkv rows past n_rows written"
 
 
-@DTYPES
-@pytest.mark.parametrize("dropout", [False, True], ids=["nodrop", "drop"])
-@pytest.mark.parametrize("case", ["edges", "holes", "s200", "s300"])
-def test_packed_vs_reference(ops, case, dropout, dtype):
+def _packed_case(ops, case, dropout, dtype, data):
     mask = _packed_mask(case)
     B, S = mask.shape
     H = 2
     plan = ops.pack_plan(mask, 0)
-    qkv, dout = _dense_inputs(B, S, H, dtype, seed=B * S)
+    qkv, dout = _inputs(data, B, S, H, dtype, B * S, mask)
     keep = (mask != 0).clone()
     keep[:, 0] = True                                        # the pooled position is always a row of the packed stream
     dout = dout * keep.reshape(-1, 1).to(dtype)              # nothing downstream reads the dropped rows
-    drop = (_rng_words(B + S), P_DROP, 33) if dropout else None
-    ref = _reference(qkv, mask, dout, B, S, H, _drop_probs(ops, B, H, S, drop))
+    drop = (_rng_words(B + S), P_TIED if data == "tied" else P_DROP, 33) if dropout else None
+    ref = _reference(qkv, mask, dout, B, S, H, _drop_probs(ops, B, H, S, drop), exact=data == "tied")
     qkv_p, dout_p = ops.pack_rows(qkv, plan, 3 * H * 64), ops.pack_rows(dout, plan, H * 64)
     out_p, lse_p = ops.attn_fwd_packed(qkv_p, plan, B, S, H, drop=drop)
     dqkv_p = ops.attn_bwd_packed(qkv_p, plan, out_p, dout_p, lse_p, B, S, H, drop=drop)
     torch.cuda.synchronize()
-    _check_packed(f"packed {case} {'drop' if dropout else 'nodrop'} {dtype}", ops, plan, out_p, lse_p, dqkv_p, ref, B, S, H)
+    _check_packed(f"{NAME[data]}packed {case} {'drop' if dropout else 'nodrop'} {dtype}", ops, plan, out_p, lse_p, dqkv_p, ref,
+                  B, S, H)
 
 
 @DTYPES
 @pytest.mark.parametrize("dropout", [False, True], ids=["nodrop", "drop"])
-@pytest.mark.parametrize("S", [40, 200, 300])
-def test_packed_zero_length_sequences(ops, S, dropout, dtype):
-    """A hand-built plan (no pooled row kept) with sequences of zero rows first, in the middle and last: those workgroups
-    write nothing, read no key mask word, and the neighbours are exact.  The packed key mask holds exactly n_rows words."""
+@pytest.mark.parametrize("case", R.PACKED_CASES)
+def test_packed_vs_reference(ops, case, dropout, dtype):
+    _packed_case(ops, case, dropout, dtype, "random")
+
+
+@DTYPES
+@pytest.mark.parametrize("dropout", [False, True], ids=["nodrop", "drop"])
+@pytest.mark.parametrize("case", R.PACKED_CASES)
+def test_exact_packed(ops, case, dropout, dtype):
+    _packed_case(ops, case, dropout, dtype, "tied")
+
+
+def _zero_length_case(ops, S, dropout, dtype, data):
     B, H = 5, 2
-    lens = [0, S, 0, max(1, S // 3), 0]
+    lens = R.zero_length_lens(S)
     mask = _prefix_mask(B, S, lens)
     m = mask.cpu().numpy().reshape(-1)
     dense = np.flatnonzero(m)
@@ -281,10 +313,10 @@ def test_packed_zero_length_sequences(ops, S, dropout, dtype):
     row_map[:n] = dense
     plan = dict(cu=torch.from_numpy(cu).cuda(), row_map=torch.from_numpy(row_map).cuda(),
                 pmask=torch.ones(n, dtype=torch.int64, device="cuda"), n_rows=torch.tensor([n], dtype=torch.int32))
-    qkv, dout = _dense_inputs(B, S, H, dtype, seed=S + 77)
+    qkv, dout = _inputs(data, B, S, H, dtype, S + 77, mask)
     dout = dout * mask.reshape(-1, 1).to(dtype)
-    drop = (_rng_words(S + 5), P_DROP, 45) if dropout else None
-    ref = _reference(qkv, mask, dout, B, S, H, _drop_probs(ops, B, H, S, drop))
+    drop = (_rng_words(S + 5), P_TIED if data == "tied" else P_DROP, 45) if dropout else None
+    ref = _reference(qkv, mask, dout, B, S, H, _drop_probs(ops, B, H, S, drop), exact=data == "tied")
     idx = torch.from_numpy(dense).long().cuda()
     qkv_p = torch.zeros_like(qkv)
     qkv_p[:n] = qkv[idx]
@@ -293,38 +325,45 @@ def test_packed_zero_length_sequences(ops, S, dropout, dtype):
     out_p, lse_p = ops.attn_fwd_packed(qkv_p, plan, B, S, H, drop=drop)
     dqkv_p = ops.attn_bwd_packed(qkv_p, plan, out_p, dout_p, lse_p, B, S, H, drop=drop)
     torch.cuda.synchronize()
-    _check_packed(f"packed Sb=0 S={S} {'drop' if dropout else 'nodrop'} {dtype}", ops, plan, out_p, lse_p, dqkv_p, ref,
-                  B, S, H)
+    _check_packed(f"{NAME[data]}packed Sb=0 S={S} {'drop' if dropout else 'nodrop'} {dtype}", ops, plan, out_p, lse_p, dqkv_p,
+                  ref, B, S, H)
     lse_c = lse_p.cpu().view(B, H, S)
     for b in (0, 2, 4):
         assert float(lse_c[b].abs().max()) == 0.0, f"lse of the empty sequence {b} written"
+
+
+@DTYPES
+@pytest.mark.parametrize("dropout", [False, True], ids=["nodrop", "drop"])
+@pytest.mark.parametrize("S", [40, 200, 300])
+def test_packed_zero_length_sequences(ops, S, dropout, dtype):
+    """A hand-built plan (no pooled row kept) with sequences of zero rows first, in the middle and last: those workgroups
+    write nothing, read no key mask word, and the neighbours are exact.  The packed key mask holds exactly n_rows words."""
+    _zero_length_case(ops, S, dropout, dtype, "random")
+
+
+@DTYPES
+@pytest.mark.parametrize("dropout", [False, True], ids=["nodrop", "drop"])
+@pytest.mark.parametrize("S", [40, 200, 300])
+def test_exact_packed_zero_length_sequences(ops, S, dropout, dtype):
+    _zero_length_case(ops, S, dropout, dtype, "tied")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. grouped pairs (dual kernels) vs the reference
 # ---------------------------------------------------------------------------------------------------------------------
 
-@DTYPES
-@pytest.mark.parametrize("text", ["masked", "packed", "packed_drop"])
-@pytest.mark.parametrize("St", [1, 77, 128])
-@pytest.mark.parametrize("Sa", [129, 197, 224, 240])
-def test_grouped_pair_vs_reference(ops, Sa, St, text, dtype):
-    """ViT-like problem A (unmasked) + text problem B in one grouped call, both orders, under onepass 2 / 1 / 0.
-    Sa = 240 is refused by dual_pair: the separate launches."""
+def _grouped_case(ops, Sa, St, text, dtype, data):
     Ba, Ha, Bt, Ht = 2, 3, 3, 2
-    qa, da = _dense_inputs(Ba, Sa, Ha, dtype, seed=Sa)
-    qt, dt = _dense_inputs(Bt, St, Ht, dtype, seed=1000 + St)
-    lens = [St, max(1, St // 2), max(1, St - 1)]
-    mask = _prefix_mask(Bt, St, lens)
-    if St > 2:
-        mask[2, 1] = 0                   # a hole: packed index != position from there on (the dropout position table)
+    mask = torch.from_numpy(R.text_mask(St)).cuda()          # a hole: packed index != position from there on
+    qa, da = _inputs(data, Ba, Sa, Ha, dtype, Sa)
+    qt, dt = _inputs(data, Bt, St, Ht, dtype, 1000 + St, mask)
     if text != "masked":                                     # packed: the dropped (padding) rows carry no gradient
         keep = (mask != 0).clone()
         keep[:, 0] = True
         dt = dt * keep.reshape(-1, 1).to(dtype)
-    drop = (_rng_words(St + Sa), P_DROP, 17) if text == "packed_drop" else None
-    ref_a = _reference(qa, None, da, Ba, Sa, Ha)
-    ref_t = _reference(qt, mask, dt, Bt, St, Ht, _drop_probs(ops, Bt, Ht, St, drop))
+    drop = (_rng_words(St + Sa), P_TIED if data == "tied" else P_DROP, 17) if text == "packed_drop" else None
+    ref_a = _reference(qa, None, da, Ba, Sa, Ha, exact=data == "tied")
+    ref_t = _reference(qt, mask, dt, Bt, St, Ht, _drop_probs(ops, Bt, Ht, St, drop), exact=data == "tied")
     if text == "masked":
         extra = dict(key_mask=mask)
         qt_in, dt_in = qt, dt
@@ -347,7 +386,7 @@ def test_grouped_pair_vs_reference(ops, Sa, St, text, dtype):
                 ops.attn_grouped(order, backward=False)
                 ops.attn_grouped(order, backward=True)
                 torch.cuda.synchronize()
-            tag = f"grouped Sa={Sa} St={St} {text} {dtype} onepass={mode} {oname}"
+            tag = f"{NAME[data]}grouped Sa={Sa} St={St} {text} {dtype} onepass={mode} {oname}"
             _check_all(tag + " A", pa["out"], pa["lse"], pa["dqkv"], ref_a, Ha)
             if text == "masked":
                 _check_all(tag + " B", pt["out"], pt["lse"], pt["dqkv"], ref_t, Ht)
@@ -355,36 +394,39 @@ def test_grouped_pair_vs_reference(ops, Sa, St, text, dtype):
                 _check_packed(tag + " B", ops, plan, pt["out"], pt["lse"], pt["dqkv"], ref_t, Bt, St, Ht)
 
 
+@DTYPES
+@pytest.mark.parametrize("text", ["masked", "packed", "packed_drop"])
+@pytest.mark.parametrize("St", [1, 77, 128])
+@pytest.mark.parametrize("Sa", [129, 197, 224, 240])
+def test_grouped_pair_vs_reference(ops, Sa, St, text, dtype):
+    """ViT-like problem A (unmasked) + text problem B in one grouped call, both orders, under onepass 2 / 1 / 0.
+    Sa = 240 is refused by dual_pair: the separate launches."""
+    _grouped_case(ops, Sa, St, text, dtype, "random")
+
+
+@DTYPES
+@pytest.mark.parametrize("text", ["masked", "packed", "packed_drop"])
+@pytest.mark.parametrize("St", [1, 77, 128])
+@pytest.mark.parametrize("Sa", [129, 197, 224, 240])
+def test_exact_grouped_pair(ops, Sa, St, text, dtype):
+    _grouped_case(ops, Sa, St, text, dtype, "tied")
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 4. adversarial values
 # ---------------------------------------------------------------------------------------------------------------------
-
-def _adversarial(kind, B, S, H, dtype, seed):
-    x = _randn((B * S, 3, H, 64), seed)
-    if kind == "sharp":              # |score| up to ~60, rows near one-hot
-        x[:, :2] *= 4.5
-    elif kind == "rising":           # score rises ~5 (natural log units) per 32 keys: the running maximum moves on every sub-tile
-        x[:, 0] = 1.0 + 0.3 * x[:, 0]
-        j = torch.arange(S, device="cuda", dtype=F32).repeat(B)
-        x[:, 1] = (5.0 / 256.0) * j[:, None, None] + 0.3 * x[:, 1]
-    elif kind == "offset":           # V = offset + noise: delta = rowsum(dO o O) is a difference of large terms
-        # delta is summed from the STORED 16-bit O, so its error grows with offset * ulp(offset): the offset is scaled to the
-        # storage type (8 in fp16, 2 in bf16: the same rounding step 2^-7 in both, 8 resp. 2 standard deviations of V)
-        x[:, 2] += 8.0 if dtype == torch.float16 else 2.0
-    else:
-        raise ValueError(kind)
-    return x.reshape(B * S, 3 * H * 64).to(dtype), _randn((B * S, H * 64), seed + 1).to(dtype)
-
 
 @DTYPES
 @pytest.mark.parametrize("kind", ["sharp", "rising", "offset"])
 @pytest.mark.parametrize("S", [64, 197, 577])
 def test_adversarial_scores(ops, S, kind, dtype):
+    """R.adversarial: sharp (|score| up to ~60), rising (the running maximum moves on every sub-tile), offset (delta from the
+    stored O is a difference of large terms; the bound's delta term is the one that holds it)"""
     B, H = 2, 3
-    qkv, dout = _adversarial(kind, B, S, H, dtype, seed=S * 7 + len(kind))
+    qkv, dout = R.adversarial(kind, B, S, H, dtype, S * 7 + len(kind), "cuda")
     ref = _reference(qkv, None, dout, B, S, H)
     if kind == "sharp":
-        assert float(ref[1].max()) > 30.0
+        assert float(ref["lse"].max()) > 30.0
     out, lse = ops.attn_fwd(qkv, None, B, S, H)
     dqkv = ops.attn_bwd(qkv, None, out, dout, lse, B, S, H)
     torch.cuda.synchronize()
@@ -402,7 +444,7 @@ def test_fully_masked_dense_row(ops, S, dropout, dtype):
     """Batch row 1's key mask is all zeros: its out and dqkv rows are exactly 0 and its lse is -inf (include/memehip.h);
     no NaN reaches the other rows or heads."""
     B, H = 3, 2
-    qkv, dout = _dense_inputs(B, S, H, dtype, seed=S + 300)
+    qkv, dout = _inputs("random", B, S, H, dtype, S + 300)
     mask = _prefix_mask(B, S, [S, 0, max(1, S // 2)])
     drop = (_rng_words(S + 9), P_DROP, 9) if dropout else None
     ref = _reference(qkv, mask, dout, B, S, H, _drop_probs(ops, B, H, S, drop))
