@@ -238,34 +238,148 @@ def n_params(cfg: OracleConfig) -> int:
     return sum(int(torch.tensor(s).prod()) for s in param_shapes(cfg).values())
 
 
+
+# --------------------------------------------------------------------------
+# 16-bit storage points of the HIP engine (``storage=``; see oracle/resnet_oracle.py for the convention)
+# --------------------------------------------------------------------------
+
+class _RoundSTE(torch.autograd.Function):
+    """x -> x rounded to the storage type and back, straight-through gradient: a value the engine keeps in 16 bits whose
+    gradient it keeps in f32 (the weight shadows) or does not need (the patches)."""
+
+    @staticmethod
+    def forward(ctx, x, dtype):
+        return x.to(dtype).to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+class _RoundGrad(torch.autograd.Function):
+    """Identity whose GRADIENT is rounded to the storage type at ``scale``: a buffer of the 16-bit gradient stream (the engine
+    stores scale * gradient; ModelConfig.stream_scale, 8192 for fp16 and 1 for bf16)."""
+
+    @staticmethod
+    def forward(ctx, x, dtype, scale):
+        ctx.dtype, ctx.scale = dtype, scale
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (g * ctx.scale).to(ctx.dtype).to(g.dtype) / ctx.scale, None, None
+
+
+class _ActStored(torch.autograd.Function):
+    """FFN-up epilogue: round(act(z)) forward; the backward multiplies by the ROUNDED derivative act'(z) the forward epilogue
+    stored (MH_GEMM_DERIV_AUX, engine buffers "t{l}.h" / "i{l}.h"), and the product is a buffer of the gradient stream
+    ("t.dh*" / "i.dh*").  z itself is never stored."""
+
+    @staticmethod
+    def forward(ctx, z, quick, dtype, scale):
+        if quick:
+            sg = torch.sigmoid(1.702 * z)
+            y, d = z * sg, sg + 1.702 * z * sg * (1.0 - sg)
+        else:
+            cdf = 0.5 * (1.0 + torch.erf(z / math.sqrt(2.0)))
+            y, d = z * cdf, cdf + z * torch.exp(-0.5 * z * z) / math.sqrt(2.0 * math.pi)
+        ctx.save_for_backward(d.to(dtype).to(z.dtype))
+        ctx.dtype, ctx.scale = dtype, scale
+        return y.to(dtype).to(z.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        d, = ctx.saved_tensors
+        return (g * d * ctx.scale).to(ctx.dtype).to(g.dtype) / ctx.scale, None, None, None
+
+
+class _EmbedLNStored(torch.autograd.Function):
+    """mh_bert_embed_fwd: the LayerNorm reads the f32 sum of the three table rows, and stores that sum in 16 bits ("t.pre0") for
+    the backward only: mean and rstd come from the f32 sum, the backward's x-hat from the rounded copy."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, dtype):
+        mean = x.mean(-1, keepdim=True)
+        rstd = torch.rsqrt(x.var(-1, unbiased=False, keepdim=True) + eps)
+        ctx.save_for_backward((x.to(dtype).to(x.dtype) - mean) * rstd, rstd, gamma)
+        return (x - mean) * rstd * gamma + beta
+
+    @staticmethod
+    def backward(ctx, dy):
+        xh, rstd, gamma = ctx.saved_tensors
+        dxh = dy * gamma
+        dx = rstd * (dxh - dxh.mean(-1, keepdim=True) - xh * (dxh * xh).mean(-1, keepdim=True))
+        red = tuple(range(dy.dim() - 1))
+        return dx, (dy * xh).sum(red), dy.sum(red), None, None
+
+
+class Storage:
+    """The three kinds of storage point.  ``storage=None``: every method is the identity and no autograd node is added, so the
+    plain oracle stays bit-identical; ``torch.float32`` runs the same hooks with roundings that change nothing."""
+
+    def __init__(self, storage, scale=None):
+        self.dtype = storage
+        self.sixteen = storage in (torch.float16, torch.bfloat16)
+        self.scale = float(scale) if scale is not None else (8192.0 if storage == torch.float16 else 1.0)
+
+    def value(self, x):       # 16-bit value, f32 gradient
+        return x if self.dtype is None else _RoundSTE.apply(x, self.dtype)
+
+    def grad(self, x):        # f32 value (or none kept), 16-bit gradient
+        return x if self.dtype is None else _RoundGrad.apply(x, self.dtype, self.scale)
+
+    def both(self, x):        # a 16-bit activation whose gradient is a 16-bit buffer too
+        return x if self.dtype is None else _RoundGrad.apply(_RoundSTE.apply(x, self.dtype), self.dtype, self.scale)
+
+    def linear(self, x, w, b=None):
+        """A tower GEMM: 16-bit activation operand (rounded where it was stored), the 16-bit weight shadow (Engine.SH), f32 bias
+        and f32 accumulation; the weight gradient stays f32 (flat gradient buffer)."""
+        return F.linear(x, self.value(w), b)
+
+    def act(self, z, quick):
+        if self.sixteen:
+            return _ActStored.apply(z, quick, self.dtype, self.scale)
+        # (None / float32: no rounding changes the derivative, autograd's own stands)
+        return z * torch.sigmoid(1.702 * z) if quick else F.gelu(z)
+
 # --------------------------------------------------------------------------
 # towers
 # --------------------------------------------------------------------------
 
 def _mha(x_q: torch.Tensor, wq, bq, wk, bk, wv, bv, heads: int,
-         add_mask: Optional[torch.Tensor], p_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+         add_mask: Optional[torch.Tensor], p_mask: Optional[torch.Tensor] = None,
+         st: Optional["Storage"] = None) -> torch.Tensor:
+    st = st or Storage(None)
     B, S, D = x_q.shape
     dh = D // heads
-    q = F.linear(x_q, wq, bq).view(B, S, heads, dh).transpose(1, 2)
-    k = F.linear(x_q, wk, bk).view(B, S, heads, dh).transpose(1, 2)
-    v = F.linear(x_q, wv, bv).view(B, S, heads, dh).transpose(1, 2)
+    # storage: the fused q/k/v projection writes "t{l}.qkv" / "i{l}.qkv", the attention input; its gradient is "t.dqkv*" / "i.dqkv*"
+    q = st.both(st.linear(x_q, wq, bq)).view(B, S, heads, dh).transpose(1, 2)
+    k = st.both(st.linear(x_q, wk, bk)).view(B, S, heads, dh).transpose(1, 2)
+    v = st.both(st.linear(x_q, wv, bv)).view(B, S, heads, dh).transpose(1, 2)
     scores = torch.matmul(q, k.transpose(-1, -2)) / math.sqrt(dh)
     if add_mask is not None:
         scores = scores + add_mask
+    scores = st.grad(scores)          # storage: dS, rounded to the MFMA operand of the dQ / dK products (never in memory)
     p = torch.softmax(scores, dim=-1)
     if p_mask is not None:            # nn.Dropout on the probabilities, mask given as 0 or 1/(1-p)
         p = p * p_mask
-    ctx = torch.matmul(p, v).transpose(1, 2).reshape(B, S, D)
+    p = st.value(p)                   # storage: P o M, rounded to the MFMA operand of the P V and P^T dO products
+    # storage: the attention output "t{l}.ctx" / "i{l}.ctx"; its gradient is "t.dctx" / "i.dctx"
+    ctx = st.both(torch.matmul(p, v).transpose(1, 2).reshape(B, S, D))
     return ctx
 
 
 def text_tower(p: Params, ids: torch.Tensor, mask: torch.Tensor, c: TextConfig,
-               pfx: str = "bert.", masks: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+               pfx: str = "bert.", masks: Optional[Dict[str, torch.Tensor]] = None, storage=None) -> torch.Tensor:
     """BERT / DistilBERT encoder -> last_hidden_state [B,S,D].
     ``masks`` injects dropout masks (values 0 or 1/(1-p)) at BERT's four dropout sites -- "emb" [B,S,D],
     "attn{l}" [B,H,S,S], "so{l}" (BertSelfOutput) and "ffn{l}" (BertOutput) [B,S,D] -- so that a
-    training-mode run can be compared element for element; None = p 0 everywhere."""
+    training-mode run can be compared element for element; None = p 0 everywhere.
+    ``storage`` = torch.float16 / torch.bfloat16 inserts the 16-bit STORAGE rounding of the HIP engine, straight-through, at the
+    points where engine.py allocates a 16-bit buffer (named in the comments below; all arithmetic stays in the dtype of ``p``);
+    the gradient-stream buffers are rounded at ModelConfig.stream_scale on the way back.  None: the plain oracle, bit for bit."""
     masks = masks or {}
+    st = storage if isinstance(storage, Storage) else Storage(storage)
     B, S = ids.shape
     pos = torch.arange(S, device=ids.device)
     # transformers builds word_embeddings with padding_idx=pad_token_id: forward is a plain
@@ -274,10 +388,15 @@ def text_tower(p: Params, ids: torch.Tensor, mask: torch.Tensor, c: TextConfig,
         + p[pfx + "embeddings.position_embeddings.weight"][pos][None]
     if c.type_vocab > 0:
         x = x + p[pfx + "embeddings.token_type_embeddings.weight"][0][None, None]
-    x = F.layer_norm(x, (c.hidden,), p[pfx + "embeddings.LayerNorm.weight"],
-                     p[pfx + "embeddings.LayerNorm.bias"], c.ln_eps)
+    x = st.grad(x)                    # storage: "t.dpre", the gradient the three table gradients are summed from (f32 sums)
+    if st.sixteen:                    # storage: "t.pre0", read by the backward only
+        x = _EmbedLNStored.apply(x, p[pfx + "embeddings.LayerNorm.weight"], p[pfx + "embeddings.LayerNorm.bias"], c.ln_eps, st.dtype)
+    else:
+        x = F.layer_norm(x, (c.hidden,), p[pfx + "embeddings.LayerNorm.weight"],
+                         p[pfx + "embeddings.LayerNorm.bias"], c.ln_eps)
     if "emb" in masks:
         x = x * masks["emb"]
+    x = st.both(x)                    # storage: "t.x0" (packed: "t.x0p"); gradient "t.dX*" / "t.dX_dense"
     # transformers' extended attention mask: (1 - mask) * finfo(dtype).min
     add_mask = (1.0 - mask.to(x.dtype))[:, None, None, :] * torch.finfo(x.dtype).min
     for i in range(c.layers):
@@ -286,18 +405,25 @@ def text_tower(p: Params, ids: torch.Tensor, mask: torch.Tensor, c: TextConfig,
                    p[L + "attention.self.query.weight"], p[L + "attention.self.query.bias"],
                    p[L + "attention.self.key.weight"], p[L + "attention.self.key.bias"],
                    p[L + "attention.self.value.weight"], p[L + "attention.self.value.bias"],
-                   c.heads, add_mask, masks.get(f"attn{i}"))
-        a = F.linear(ctx, p[L + "attention.output.dense.weight"], p[L + "attention.output.dense.bias"])
+                   c.heads, add_mask, masks.get(f"attn{i}"), st)
+        a = st.linear(ctx, p[L + "attention.output.dense.weight"], p[L + "attention.output.dense.bias"])
         if f"so{i}" in masks:
             a = a * masks[f"so{i}"]
-        x = F.layer_norm(x + a, (c.hidden,), p[L + "attention.output.LayerNorm.weight"],
-                         p[L + "attention.output.LayerNorm.bias"], c.ln_eps)
-        h = F.gelu(F.linear(x, p[L + "intermediate.dense.weight"], p[L + "intermediate.dense.bias"]))
-        o = F.linear(h, p[L + "output.dense.weight"], p[L + "output.dense.bias"])
+        # storage: "t{l}.a", the residual sum written by the out-proj epilogue (the LayerNorm's input); gradient "t.da*"
+        # storage: "t{l}.y", the LayerNorm output; gradient "t.dy"
+        x = st.both(F.layer_norm(st.both(x + a), (c.hidden,), p[L + "attention.output.LayerNorm.weight"],
+                                 p[L + "attention.output.LayerNorm.bias"], c.ln_eps))
+        # storage: "t{l}.g" = gelu, "t{l}.h" = gelu' (both from the FFN-up epilogue); gradient at the GELU input "t.dh*"
+        h = st.act(st.linear(x, p[L + "intermediate.dense.weight"], p[L + "intermediate.dense.bias"]), False)
+        o = st.linear(h, p[L + "output.dense.weight"], p[L + "output.dense.bias"])
         if f"ffn{i}" in masks:
             o = o * masks[f"ffn{i}"]
-        x = F.layer_norm(x + o, (c.hidden,), p[L + "output.LayerNorm.weight"],
+        # storage: "t{l}.f", the residual sum written by the FFN-down epilogue; gradient "t.df*"
+        x = F.layer_norm(st.both(x + o), (c.hidden,), p[L + "output.LayerNorm.weight"],
                          p[L + "output.LayerNorm.bias"], c.ln_eps)
+        # storage: "t.x{l+1}"; gradient "t.dX*".  The last layer's output is read by the head unrounded ("t.xlast32", f32);
+        # the head writes its gradient into the 16-bit stream ("t.dXrows" / "t.dX0")
+        x = st.both(x) if i < c.layers - 1 else st.grad(x)
     return x
 
 
@@ -311,30 +437,40 @@ def patchify(image: torch.Tensor, patch: int) -> torch.Tensor:
 
 
 def image_tower(p: Params, image: torch.Tensor, c: ImageConfig,
-                pfx: str = "image_model.") -> torch.Tensor:
-    """ViT encoder -> final-LayerNorm'd sequence [B,N+1,D]."""
+                pfx: str = "image_model.", storage=None) -> torch.Tensor:
+    """ViT encoder -> final-LayerNorm'd sequence [B,N+1,D].  ``storage``: see text_tower."""
+    st = storage if isinstance(storage, Storage) else Storage(storage)
     B = image.shape[0]
     D = c.hidden
     w = p[pfx + "embeddings.patch_embeddings.projection.weight"].reshape(D, -1)
-    x = F.linear(patchify(image, c.patch), w, p.get(pfx + "embeddings.patch_embeddings.projection.bias"))
+    # storage: "i.patches" (mh_patchify) and the weight shadow; "i.proj" is the projection's output, "i.dproj" its gradient
+    x = st.both(st.linear(st.value(patchify(image, c.patch)), w, p.get(pfx + "embeddings.patch_embeddings.projection.bias")))
     x = torch.cat([p[pfx + "embeddings.cls_token"].expand(B, -1, -1), x], dim=1)
     x = x + p[pfx + "embeddings.position_embeddings"]
+    x = st.both(x)        # storage: "i.x0" ("i.x0pre" with pre_ln), written by mh_vit_assemble_fwd; gradient "i.dX*" ("i.dx0pre")
     if c.pre_ln:      # CLIPVisionTransformer.pre_layrnorm
-        x = F.layer_norm(x, (D,), p[pfx + "pre_layernorm.weight"], p[pfx + "pre_layernorm.bias"], c.ln_eps)
-    act = (lambda z: z * torch.sigmoid(1.702 * z)) if c.act == "quick_gelu" else F.gelu
+        # storage: "i.x0", here a LayerNorm output; gradient "i.dX*"
+        x = st.both(F.layer_norm(x, (D,), p[pfx + "pre_layernorm.weight"], p[pfx + "pre_layernorm.bias"], c.ln_eps))
+    quick = c.act == "quick_gelu"
     for i in range(c.layers):
         L = f"{pfx}encoder.layer.{i}."
-        h = F.layer_norm(x, (D,), p[L + "layernorm_before.weight"], p[L + "layernorm_before.bias"], c.ln_eps)
+        # storage: "i{l}.u", the LayerNorm output that feeds the q/k/v projection; gradient "i.du"
+        h = st.both(F.layer_norm(x, (D,), p[L + "layernorm_before.weight"], p[L + "layernorm_before.bias"], c.ln_eps))
         ctx = _mha(h,
                    p[L + "attention.attention.query.weight"], p[L + "attention.attention.query.bias"],
                    p[L + "attention.attention.key.weight"], p[L + "attention.attention.key.bias"],
                    p[L + "attention.attention.value.weight"], p[L + "attention.attention.value.bias"],
-                   c.heads, None)
-        x = x + F.linear(ctx, p[L + "attention.output.dense.weight"], p[L + "attention.output.dense.bias"])
-        h = F.layer_norm(x, (D,), p[L + "layernorm_after.weight"], p[L + "layernorm_after.bias"], c.ln_eps)
-        h = act(F.linear(h, p[L + "intermediate.dense.weight"], p[L + "intermediate.dense.bias"]))
-        x = x + F.linear(h, p[L + "output.dense.weight"], p[L + "output.dense.bias"])
-    return F.layer_norm(x, (D,), p[pfx + "layernorm.weight"], p[pfx + "layernorm.bias"], c.ln_eps)
+                   c.heads, None, None, st)
+        # storage: "i{l}.xp", the residual sum written by the out-proj epilogue; gradient "i.dxp*"
+        x = st.both(x + st.linear(ctx, p[L + "attention.output.dense.weight"], p[L + "attention.output.dense.bias"]))
+        # storage: "i{l}.w", the LayerNorm output that feeds the FFN; gradient "i.dw"
+        h = st.both(F.layer_norm(x, (D,), p[L + "layernorm_after.weight"], p[L + "layernorm_after.bias"], c.ln_eps))
+        # storage: "i{l}.g" = act, "i{l}.h" = act' (FFN-up epilogue); gradient at the activation's input "i.dh*"
+        h = st.act(st.linear(h, p[L + "intermediate.dense.weight"], p[L + "intermediate.dense.bias"]), quick)
+        # storage: "i.x{l+1}", the residual sum written by the FFN-down epilogue; gradient "i.dX*" (into the last layer: "i.dXrows")
+        x = st.both(x + st.linear(h, p[L + "output.dense.weight"], p[L + "output.dense.bias"]))
+    # the final LayerNorm's output goes to the head unrounded ("i.xf32", f32); the head writes its gradient into the stream ("i.dXf")
+    return st.grad(F.layer_norm(x, (D,), p[pfx + "layernorm.weight"], p[pfx + "layernorm.bias"], c.ln_eps))
 
 
 def pool_text(hidden: torch.Tensor, pool: str) -> torch.Tensor:
@@ -346,15 +482,16 @@ def pool_text(hidden: torch.Tensor, pool: str) -> torch.Tensor:
 
 
 def forward(p: Params, text: torch.Tensor, image: torch.Tensor, mask: torch.Tensor,
-            cfg: OracleConfig, masks: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+            cfg: OracleConfig, masks: Optional[Dict[str, torch.Tensor]] = None, storage=None) -> torch.Tensor:
     """MultimodalClassifier.forward(text, image, mask) -> logits [B,num_classes]
     (...task2C.txt:172-197; argument order text, image, mask).  ``masks``: see text_tower, plus "head" [B,D]
-    for ``bert_drop`` (...task2C.txt:160,178)."""
-    t = pool_text(text_tower(p, text, mask, cfg.text, masks=masks), cfg.pool)
+    for ``bert_drop`` (...task2C.txt:160,178).  ``storage``: the towers' 16-bit storage points (text_tower); the head, the
+    loss, every bias, LayerNorm parameter and weight gradient stay in the dtype of ``p``, as they stay f32 in the engine."""
+    t = pool_text(text_tower(p, text, mask, cfg.text, masks=masks, storage=storage), cfg.pool)
     if masks and "head" in masks:
         t = t * masks["head"]
     t = F.linear(t, p["bert_fc.weight"], p["bert_fc.bias"])
-    v = image_tower(p, image, cfg.image)[:, 0]
+    v = image_tower(p, image, cfg.image, storage=storage)[:, 0]
     v = F.linear(v, p["image_fc.weight"], p["image_fc.bias"])
     f = F.linear(torch.cat((t, v), dim=1), p["fusion_fc.weight"], p["fusion_fc.bias"])
     return F.linear(f, p["output_fc.weight"], p["output_fc.bias"])
@@ -378,9 +515,9 @@ def sigmoid_focal_loss(inputs: torch.Tensor, targets: torch.Tensor, alpha: float
     return loss.mean()
 
 
-def loss_and_grads(p: Params, text, image, mask, labels, cfg: OracleConfig, masks=None):
+def loss_and_grads(p: Params, text, image, mask, labels, cfg: OracleConfig, masks=None, storage=None):
     leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    logits = forward(leaves, text, image, mask, cfg, masks=masks)
+    logits = forward(leaves, text, image, mask, cfg, masks=masks, storage=storage)
     loss = cross_entropy(logits, labels)
     loss.backward()
     grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
